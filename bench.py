@@ -13,8 +13,12 @@ With N > 1 GPUs each rank holds its own contiguous 1 GiB shard of one corpus str
 scaling); the per-iteration pair-count exchange is an RCCL all-reduce enqueued on the engine's
 stream between the selection and apply kernels (the rank loop, bpe-tokenizer_amd/sharded.py).
 
-Prints ONE JSON line (rank 0), right after the timed region (the CPU baseline is measured before
-any GPU work).  --incremental adds a second line: the same workload in the incremental mode.
+A plain run sets up, warms up, times the K merges and prints ONE JSON line (rank 0).  Everything
+else the benchmark measures or checks is behind --full: the CPU baseline (measured before any GPU
+work), the merge list against the CPU restatement's fixture, and two further lines, the same
+workload in the incremental mode and the device encoder over the run's merges.
+--dump-outputs DIR writes what the timed call returned and left behind (dump_outputs below), so
+that two builds can be compared output for output: the inputs are the same from run to run.
 """
 import argparse
 import hashlib
@@ -303,6 +307,34 @@ def fixture_check(args, merges):
             'merges_match_fixture': got == want[:n]}
 
 
+DUMP_SAMPLES = 4   # corpus samples (1 MiB of input each) written by --dump-outputs
+
+
+def dump_outputs(path, trainer, merges):
+    """What a caller of the timed path holds after its last step, as float64 / float32 .npy files
+    (about 16 MB for C3):
+      merges.npy          [K, 3] the timed call's return value: (a, b, W) of every timed merge, the
+                          last row the last step's
+      sample_lengths.npy  [n_samples] live tokens of every sample of the corpus the last step left
+      sample_index.npy    the DUMP_SAMPLES samples read back (a fixed choice: numpy default_rng(0))
+      sample_offsets.npy  their offsets into sample_ids.npy
+      sample_ids.npy      their token ids (float32: ids stay below MAX_VOCAB = 55296)"""
+    os.makedirs(path, exist_ok=True)
+    eng = trainer.engine
+    lens = eng.sample_lengths()
+    k = min(DUMP_SAMPLES, len(lens))
+    idx = np.sort(np.random.default_rng(0).choice(len(lens), size=k, replace=False))
+    idx = idx.astype(np.int64)
+    ids, off = eng.read_samples(idx)
+    out = {'merges': np.asarray(merges, dtype=np.float64).reshape(-1, 3),
+           'sample_lengths': lens.astype(np.float64),
+           'sample_index': idx.astype(np.float64),
+           'sample_offsets': off.astype(np.float64),
+           'sample_ids': ids.astype(np.float32)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -314,17 +346,20 @@ def main():
                     help='uniform: the C3 byte stream; zipf: the skewed variant (Zipf 1.1 words)')
     ap.add_argument('--cpu-sample-mib', type=int, default=256)
     ap.add_argument('--cpu-budget-s', type=float, default=20.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: leave the CPU baseline out (a plain run never measures it)')
+    ap.add_argument('--full', action='store_true',
+                    help='also everything beside the headline figure: the CPU baseline, the merge '
+                         'list against the CPU restatement\'s fixture, and two further JSON lines: '
+                         'the same workload in the incremental mode, and the device encoder '
+                         '(encodeToCode, bpe_encode_batch) with the merges of the timed run over '
+                         '100 000 texts of 16-1024 chars of the same stream')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed call returned and a fixed '
+                         'sample of the corpus it left as DIR/<name>.npy (rank 0)')
     ap.add_argument('--device-warmup-ms', type=float, default=100.0,
                     help='plain count passes over the resident corpus (no merge) before the warmup '
                          'merges, so that the timed window starts at steady clocks (0: none)')
-    ap.add_argument('--incremental', action='store_true',
-                    help='also run the incremental mode on the same workload, printed as a second '
-                         'JSON line after the bench line')
-    ap.add_argument('--encode', action='store_true',
-                    help='also run the device encoder (encodeToCode, bpe_encode_batch) with the '
-                         'merges of the timed run over 100 000 texts of 16-1024 chars of the same '
-                         'stream, printed as a further JSON line')
     args = ap.parse_args()
 
     import torch
@@ -336,7 +371,7 @@ def main():
     # the CPU baseline first (host cores only, before any GPU work), so that nothing but the print
     # follows the timed region
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_sample_mib, args.cpu_budget_s, args.corpus)
     torch.cuda.set_device(local_rank)
     dist = None
@@ -449,8 +484,10 @@ def main():
             # triples as int64, warmup merges included)
             'merges_sha256': hashlib.sha256(
                 np.asarray(trainer.merges, dtype=np.int64).tobytes()).hexdigest(),
-            # (the merges of the whole run, warmup included, against the CPU restatement's run)
-            'fixture_check': fixture_check(args, trainer.merges) if world == 1 else None,
+            # (--full: the merges of the whole run, warmup included, against the CPU restatement's
+            # run)
+            'fixture_check': (fixture_check(args, trainer.merges)
+                              if args.full and world == 1 else None),
             'device_warmup': heat,
             'breakdown_ms_per_step': {
                 'stream_pass': k1_ms * st['step_launches'] / max(1, args.steps),
@@ -465,13 +502,14 @@ def main():
         }
         if cpu is not None:
             out['cpu_baseline'] = cpu
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, trainer, merges)
         print(json.dumps(out), flush=True)
-        if world == 1 and args.incremental:
+        if world == 1 and args.full:
             trainer.engine.close()
             inc = incremental_mode(args, merges)
             inc['speedup_vs_stream_loop'] = (dt * 1e3 / args.steps) / inc['ms_per_step']
             print(json.dumps({'incremental_mode': inc}), flush=True)
-        if world == 1 and args.encode:
             print(json.dumps({'encode': encode_line(args, trainer.merges)}), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -7,8 +7,9 @@
 #   smoke      __graft_entry__.smoke()
 #   driver     the driver's exact bench command (bench.py --gpus 1 --steps 20 --warmup 5), timed
 #   bench      full C3 bench line + the incremental mode's and the encoder's lines
-#              (bench.py --incremental --encode)
-#   zipf       full zipf C3 bench line (bench.py --corpus zipf)
+#              (bench.py --full)
+#   zipf       full zipf C3 bench line with its fixture check and further lines
+#              (bench.py --corpus zipf --full --no-cpu-baseline)
 #   prof       rocprofv3 --kernel-trace --stats of the full C3 bench (kernel stats CSV)
 #   profzipf   the same for zipf C3
 #   profpix    the same for the incremental mode (tools/pix_bench.py, full C3)
@@ -65,11 +66,11 @@ for step in "$@"; do
     t1=$(date +%s.%N)
     cat "$OUT/driver.jsonl"; python3 -c "print('driver wall: %.1f s' % ($t1 - $t0))" | tee "$OUT/driver.wall" ;;
   bench)
-    timeout -k 10 700 python3 bench.py --incremental --encode $BENCH_EXTRA > "$OUT/bench.jsonl" 2> "$OUT/bench.err" \
+    timeout -k 10 700 python3 bench.py --full $BENCH_EXTRA > "$OUT/bench.jsonl" 2> "$OUT/bench.err" \
         || fail bench "$OUT/bench.err"
     cat "$OUT/bench.jsonl" ;;
   zipf)
-    timeout -k 10 600 python3 bench.py --corpus zipf --no-cpu-baseline $BENCH_EXTRA > "$OUT/zipf.jsonl" \
+    timeout -k 10 700 python3 bench.py --corpus zipf --full --no-cpu-baseline $BENCH_EXTRA > "$OUT/zipf.jsonl" \
         2> "$OUT/zipf.err" || fail zipf "$OUT/zipf.err"
     head -c 1500 "$OUT/zipf.jsonl" ;;
   prof)
