@@ -84,6 +84,7 @@ class Stats(ctypes.Structure):
         ('cold_rebuilds', ctypes.c_int64), ('incr_ms', ctypes.c_double),
         ('incr_timed', ctypes.c_int64), ('incr_launches', ctypes.c_int64),
         ('incr_live', ctypes.c_int64), ('unscreened_passes', ctypes.c_int64),
+        ('delta_passes', ctypes.c_int64), ('delta_chunks', ctypes.c_int64),
     ]
 
     def as_dict(self):

@@ -21,6 +21,9 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
                                   int64_t cpr, int R, const void *carry, const void *ctl,
                                   uint32_t *partials, unsigned long long *spill, const void *ct,
                                   void *sums, unsigned long long *replaced);
+hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
+                             int64_t cpr, int R, const void *carry, const void *ctl, void *sums,
+                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n);
 hipError_t launch_step_table(int merge, unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, int32_t ma, int32_t mb,
                              int32_t mc, uint32_t *partials, unsigned long long *spill,
@@ -163,6 +166,10 @@ struct bpe_ctx {
     // device-resident mergeUntil loop: control block + merge log (pinned host mirrors)
     LoopCtl *d_ctl = nullptr, *h_ctl = nullptr;
     long long *d_log = nullptr, *h_log = nullptr;
+    // the delta form of the table-state loop: the chunks a pass rewrote, a segment of cpr entries
+    // per region (d_sites, sites_cap entries) and each region's count (d_site_n)
+    uint32_t *d_sites = nullptr, *d_site_n = nullptr;
+    int64_t sites_cap = 0;
     unsigned int *d_ticket = nullptr;   // last-block tickets (k_tie_fused, k_select_maint; zero between launches)
     BlockBest *d_brec = nullptr;        // k_select_maint's per-block bests
     // apply-only replay: per-merge replacement counts
@@ -1000,6 +1007,10 @@ int do_apply(bpe_ctx *c, int32_t a, int32_t b, int32_t cc, int64_t *replaced) {
 // Up to n mergeUntil iterations with the decisions kept on the device (core.ts:367-384): per
 // iteration k_select_multi, k_decide, [k_tie, k_decide] and the pass (k_step_loop, k_runs,
 // k_reduce_table), every kernel reading the merge from the LoopCtl, and one host sync at the end.
+// In the table state an iteration may take the delta form instead (LoopCtl::delta, decided on the
+// device): k_apply_loop streams the merge in without counting and lists the rewritten chunks,
+// k_site_delta adds the sites' deltas to the table, and k_reduce_table only scans it.  The launch
+// list is fixed; the kernels of the form not taken return on the flag.
 // With a maintained cold table (skewed corpora) the selection is k_argmax_cold + k_collect over
 // that table and the pass is the fused one (k_cold_invalidate, k_step_loop<MODE_FUSED>,
 // k_runs<MODE_FUSED>), as in the host path.
@@ -1032,6 +1043,18 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         c->len16_lo = base;
     }
     geometry(c);
+    // The table state may take the delta form (LoopCtl::delta; BPE_DELTA=0 turns it off, for A/B
+    // and checking; read per batch): the site list holds a segment of cpr entries per region.
+    const char *dknob = getenv("BPE_DELTA");
+    const bool delta_ok = !maint && !(dknob && atoi(dknob) == 0);
+    if (delta_ok && c->sites_cap < (int64_t)c->R * c->cpr) {
+        dfree(c->d_sites);
+        c->d_sites = nullptr;
+        c->sites_cap = 0;
+        const int64_t cap = (int64_t)c->R * c->cpr;
+        if ((rc = dev_alloc(&c->d_sites, (size_t)cap))) return rc;
+        c->sites_cap = cap;
+    }
     hipStream_t s = c->stream;
     if (maint) {
         // (k_select_maint takes the best over the hot bins itself)
@@ -1052,6 +1075,7 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
     h->max_id = BPE_MAX_VOCAB;
     h->maintained = maint ? 1 : 0;
     h->cold_cap = c->cold_cap;
+    h->allow_delta = delta_ok ? 1 : 0;
     HIP_TRY(hipMemcpyAsync(c->d_ctl, h, sizeof *h, hipMemcpyHostToDevice, s));
     TieArgs A;
     memset(&A, 0, sizeof A);
@@ -1105,10 +1129,16 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
                                                         c->d_spill, c->cold, c->d_sums,
                                                         &c->d_res->replaced);
         } else {
+            // (the full pass, or the delta form's apply-only stream: the one whose form the
+            // decision did not take returns at once)
             HIP_TRY(bpe_step::launch_step_loop_table(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
                                                      c->d_carry, c->d_ctl, c->d_partials,
                                                      c->d_spill, &c->cold, c->d_sums,
                                                      &c->d_res->replaced));
+            if (delta_ok)
+                HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
+                                                    c->d_carry, c->d_ctl, c->d_sums,
+                                                    &c->d_res->replaced, c->d_sites, c->d_site_n));
         }
         HIP_TRY(hipGetLastError());
         if ((rc = span_end(c, e_step, maint && c->use_incr ? 2 : 0))) return rc;
@@ -1124,10 +1154,20 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
                 k_runs<MODE_FUSED><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
                                                                       c->d_spill, c->cold,
                                                                       c->d_heavy, c->d_ctl);
-            else
+            else if (!delta_ok)
                 k_runs<MODE_TABLE><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
                                                                       c->d_spill, c->cold,
                                                                       c->d_heavy, c->d_ctl);
+            if (delta_ok) {
+                // either form's stitch in one launch; after the apply-only stream the sites'
+                // deltas into the table (after a full pass k_site_delta returns at once)
+                k_runs_loop<<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
+                                                               c->d_spill, c->cold, c->d_heavy,
+                                                               c->d_ctl, c->d_site_n);
+                k_site_delta<<<c->R, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_sites,
+                                                  c->d_site_n, c->d_hot, c->d_ctl);
+            }
+            // (after a delta iteration it sums nothing: the scan of the table alone)
             k_reduce_table<<<HIST_WORDS / REDUCE_WORDS_PER_BLOCK, REDUCE_THREADS, 0, s>>>(
                 c->d_partials, c->G, c->d_spill, c->d_hot, c->d_len16, max_length, c->d_res,
                 c->d_ctl);
@@ -1143,8 +1183,10 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
     HIP_TRY(hipStreamSynchronize(s));
     const int64_t nd = h->n_done;
     if (h->status == LOOP_ERROR)
-        return fail(BPE_ERR_STATE, "bpe native: device loop: replacement count != W, or a tie "
-                                   "pass found no occurrence");
+        return fail(BPE_ERR_STATE,
+                    h->err == 3 ? "bpe native: device loop: the table's bin of the merged pair != W"
+                                : "bpe native: device loop: replacement count != W, or a tie "
+                                  "pass found no occurrence");
     if (nd < 0 || nd > n) return fail(BPE_ERR_STATE, "bpe native: device loop: bad merge count");
     // the last merge's replacement count is checked here (the others were, on the device)
     if (h->status == LOOP_RUN && nd > 0 && c->h_res->replaced != (unsigned long long)h->w)
@@ -1197,6 +1239,8 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         c->stats.tie_tail += h->n_tail;
         c->stats.tie_lone += h->n_lone;
         c->stats.loop_host += h->n_host;
+        c->stats.delta_passes += h->n_delta;
+        c->stats.delta_chunks += (int64_t)h->delta_chunks;
     }
     c->last_replaced = nd ? c->h_log[LOG_WORDS * (nd - 1) + 2] : c->last_replaced;
     // every early-ended batch of the table state leaves the last reduce's best key in the Result
@@ -2581,6 +2625,7 @@ int bpe_create(bpe_ctx **out, int device) {
     if ((rc = dev_alloc(&c->d_ctl, 1))) return bail(rc);
     if ((rc = dev_alloc(&c->d_ticket, TICKET_WORDS))) return bail(rc);
     if ((rc = dev_alloc(&c->d_brec, COLD_GRID))) return bail(rc);
+    if ((rc = dev_alloc(&c->d_site_n, MAX_REGIONS))) return bail(rc);
     if (hipMemset(c->d_ticket, 0, TICKET_WORDS * sizeof(unsigned int)) != hipSuccess)
         return bail(fail(BPE_ERR_HIP, "bpe native: memset failed"));
     if ((rc = dev_alloc(&c->d_repl, REPLAY_BATCH))) return bail(rc);
@@ -2636,7 +2681,8 @@ int bpe_destroy(bpe_ctx *c) {
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
                     c->cold.bmax, c->cold.bdirty, c->cold.blist,
-                    c->d_ctl, c->d_log, c->d_repl, c->d_ticket, c->d_brec};
+                    c->d_ctl, c->d_log, c->d_repl, c->d_ticket, c->d_brec, c->d_sites,
+                    c->d_site_n};
     for (void *p : ptrs) dfree(p);
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_cand) (void)hipHostFree(c->h_cand);

@@ -216,7 +216,20 @@ struct LoopCtl {
     // the pair).  0 (screened) in the maintained state and for the first pass of a batch.
     int32_t unscreened;
     int32_t n_unscreened;   // decisions that set it, in this batch
+    // The delta form of a table-state iteration (single-context loop): the merge is applied by an
+    // apply-only stream (k_apply_loop) that lists the chunks it rewrites, and the table is kept by
+    // the deltas of the merge's sites (k_site_delta) instead of a recount.  Set by the decision
+    // for a merge of two distinct ids in fewer than 1/16 of the chunks, when the host allows it
+    // (allow_delta: the table state, BPE_DELTA != 0); every kernel of the form not taken returns
+    // at once.  err 3: the table's bin of (a, b) did not hold W.
+    int32_t delta;
+    int32_t allow_delta;
+    int32_t n_delta;        // decisions that set it, in this batch
+    int32_t pad_;
+    unsigned long long delta_chunks;   // chunks listed by the delta iterations of this batch
 };
+
+
 
 // Merge log entry of the device loop: (a, b, W, this corpus's replacement count).
 constexpr int LOG_WORDS = 4;
@@ -1256,6 +1269,11 @@ struct Apply {
     int32_t par;         // its run-offset parity (X X merges only)
     int32_t match;       // it is an `a` matched with the chunk's first live token
     uint32_t n_match;
+    // SITES (the delta form's apply-only stream): the region's segment of the site list, the
+    // entries written so far, and the region's first chunk (entries are corpus chunk indices)
+    uint32_t *sites;
+    uint32_t n_sites;
+    uint32_t c0;
 };
 
 // What a k_step pass does before counting: nothing, a merge of two distinct ids, or an X X merge
@@ -1270,7 +1288,8 @@ __device__ __forceinline__ void tag_tail(int32_t (&y)[4], int total, int32_t las
 // Applies the merge (a, b) -> c to one pre-merge chunk (w.len > 0) at chunk index c of the region,
 // in place: nxt = the first pre-merge live token after it (the next region's first for the last
 // chunk).  A touched chunk is re-packed and written back.
-template <int MERGE, bool PREP = false>
+// SITES: every chunk written back is appended to the wave's own segment of the site list.
+template <int MERGE, bool PREP = false, bool SITES = false>
 __device__ __forceinline__ void apply_chunk(Chunk &w, int32_t nxt, int32_t ma, int32_t mb,
                                             int32_t mc,
                                             const __amdgpu_buffer_rsrc_t rs, int c, int lane,
@@ -1374,6 +1393,11 @@ __device__ __forceinline__ void apply_chunk(Chunk &w, int32_t nxt, int32_t ma, i
                                make_uint4((unsigned)y[0], (unsigned)y[1], (unsigned)y[2], (unsigned)y[3])),
             rs, lane * 16, c * (CHUNK * 4), 0);
         ap.n_match += (uint32_t)(__popcll(M0) + __popcll(M1) + __popcll(M2) + __popcll(M3));
+        if (SITES) {
+            // (a chunk is rewritten at most once per pass, so the segment of cpr entries holds)
+            if (lane == 0) ap.sites[ap.n_sites] = ap.c0 + (uint32_t)c;
+            ++ap.n_sites;
+        }
         w.len = total;
         w.last = last;
         pp.ok = 0;   // (the count makes the rewritten chunk's slots)
@@ -1388,7 +1412,7 @@ __device__ __forceinline__ void apply_chunk(Chunk &w, int32_t nxt, int32_t ma, i
 
 // hist: the kernel's static LDS table (so, once inlined, LDS addresses are plain constants with no
 // symbol base to add per access)
-template <int MERGE, int MODE, bool SCREEN = true, bool SLOTS = true>
+template <int MERGE, int MODE, bool SCREEN = true, bool SLOTS = true, bool SITES = false>
 __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ ids,
                                           int64_t n_chunks, int64_t cpr, int R,
                                           const RegionCarry *__restrict__ carry, int32_t ma,
@@ -1398,7 +1422,10 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
                                           RegionSum *__restrict__ sums,
                                           unsigned long long *__restrict__ replaced,
                                           unsigned long long *__restrict__ hot_g = nullptr,
-                                          unsigned long long *__restrict__ delta = nullptr) {
+                                          unsigned long long *__restrict__ delta = nullptr,
+                                          uint32_t *__restrict__ site_list = nullptr,
+                                          uint32_t *__restrict__ site_n = nullptr) {
+    // (SITES: site_list holds a segment of cpr entries per region, site_n the entries written)
     // (MODE_INCR: `spill` holds the rows' spill, 4 * INCR_RLIM u64; hot_g the maintained table;
     // delta: a sharded rank's delta rows, which then take the touched pairs instead of the tables)
     unsigned long long *rspill = spill;
@@ -1461,6 +1488,9 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
         ap.par = (int32_t)(rc.carry_off & 1) ^ 1;   // the token before the region (if linked)
         ap.match = 0;
         ap.n_match = 0;
+        ap.sites = SITES ? site_list + c0 : nullptr;
+        ap.n_sites = 0;
+        ap.c0 = (uint32_t)c0;
         // the region through a range-checked buffer descriptor (loads past its end return 0 and
         // are never consumed)
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -1571,7 +1601,7 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
             if (MERGE && cur.len) {
                 const int32_t nx = live_from(c + 1, MODE == MODE_TABLE ? f_next : bcast(nxt_slot.t[0], 0));
                 if (PREP) prep_pairs(cur.t, cur.len, cur.last, nx, k, pcur);
-                apply_chunk<MERGE, PREP>(cur, nx, ma, mb, mc, rs, c, lane, ap, pcur, akey);
+                apply_chunk<MERGE, PREP, SITES>(cur, nx, ma, mb, mc, rs, c, lane, ap, pcur, akey);
             }
             if (cur.len) {
                 if (prv.len) count_chunk<MODE, false, SCREEN, PREP>(prv, cur.first, lane, s, k, df, pprv);
@@ -1627,6 +1657,7 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
             o.trail_odd = s.par ^ 1;   // trail run length = offset of the last token + 1
             sums[r] = o;
             if (MERGE && ap.n_match) atomicAdd(replaced, (unsigned long long)ap.n_match);
+            if (SITES) site_n[r] = ap.n_sites;
         }
     }
     if (MODE == MODE_TABLE || MODE == MODE_FUSED) {
@@ -1703,7 +1734,10 @@ k_step_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
             unsigned long long *__restrict__ hot_g = nullptr,
             unsigned long long *__restrict__ delta = nullptr) {
     __shared__ __attribute__((aligned(16))) uint32_t hist[HIST_WORDS];
-    if (ctl->status != LOOP_RUN) return;
+    // (a delta iteration is k_apply_loop's; both words loaded before either is tested: one
+    // memory latency)
+    const int32_t status = ctl->status, form = MODE == MODE_TABLE ? ctl->delta : 0;
+    if ((status != LOOP_RUN) | (form != 0)) return;
     const int32_t ma = ctl->a, mb = ctl->b, mc = ctl->c;
     if (ma == mb)
         step_body<MERGE_XX, MODE>(hist, ids, n_chunks, cpr, R, carry, ma, mb, mc, partials, spill,
@@ -1720,6 +1754,157 @@ k_step_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
     else
         step_body<MERGE_XY, MODE>(hist, ids, n_chunks, cpr, R, carry, ma, mb, mc, partials, spill,
                                   ct, nullptr, sums, replaced, hot_g, delta);
+}
+
+// The delta form's apply-only stream: the merge in the LoopCtl applied as by k_apply<MERGE_XY> (no
+// LDS table, no slab, no pair counted; the region sums kept, so k_runs<MODE_NONE> rebuilds the
+// carries and a full pass can follow), every rewritten chunk listed for k_site_delta.
+__global__ void __launch_bounds__(WG)
+k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
+             const RegionCarry *__restrict__ carry, const LoopCtl *__restrict__ ctl,
+             RegionSum *__restrict__ sums, unsigned long long *__restrict__ replaced,
+             uint32_t *__restrict__ site_list, uint32_t *__restrict__ site_n) {
+    if (ctl->status != LOOP_RUN || !ctl->delta) return;
+    step_body<MERGE_XY, MODE_NONE, true, true, true>(
+        nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,
+        ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n);
+}
+
+// ---- the delta form's site kernel -----------------------------------------------------------
+// A live slot of the corpus as (chunk, slot, the chunk's live length), walked one live slot at a
+// time by a single lane: over dead tails and empty chunks, across chunk and region boundaries.
+struct Cursor {
+    int64_t q;
+    int k, len;
+};
+
+__device__ __forceinline__ int chunk_live_len(const int32_t *ids, int64_t q) {
+    const int32_t v = ids[q * CHUNK + (CHUNK - 1)];
+    return v >= SEP ? CHUNK : ((LEN_TAG - v) & 255);
+}
+
+// The live slot before p (p moves there); SEP before the corpus start.
+__device__ __forceinline__ int32_t live_prev(const int32_t *ids, Cursor &p) {
+    for (;;) {
+        if (p.k > 0) {
+            --p.k;
+            return ids[p.q * CHUNK + p.k];
+        }
+        if (p.q == 0) return SEP;
+        --p.q;
+        p.len = chunk_live_len(ids, p.q);
+        p.k = p.len;
+    }
+}
+
+// The live slot after p (p moves there); SEP past the corpus end.
+__device__ __forceinline__ int32_t live_next(const int32_t *ids, int64_t n_chunks, Cursor &p) {
+    for (;;) {
+        if (p.k + 1 < p.len) {
+            ++p.k;
+            return ids[p.q * CHUNK + p.k];
+        }
+        if (p.q + 1 >= n_chunks) return SEP;
+        ++p.q;
+        p.len = chunk_live_len(ids, p.q);
+        p.k = -1;
+    }
+}
+
+// The table's deltas of one site of the merge (a, b) -> c, a != b, from the post-merge corpus: the
+// site is the token c at p (c is a fresh id, so every c is a site).  x, y = the live tokens before
+// and after it (SEP ends a sample: no pair across it).  Before the merge the site read a b, so:
+//  - left, removed: (x, a); when x == c the site before ended in b, so (b, a); when x == a the
+//    site's a ended a run of M + 1 a's that is now M long, and a run of L counts floor(L / 2):
+//    one (a, a) less iff M is odd;
+//  - left, added: (x, c); when x == c the sites form a chain, counted floor(n / 2) once, by the
+//    chain's last site (n = the c's up to and including this one);
+//  - right, only when y != c (the next site's left side covers that adjacency): removed (b, y),
+//    or, y == b, one (b, b) less iff the M' b's that follow are odd in number; added (c, y).
+// The pair (a, b) itself loses W, once for the whole merge (k_site_delta).
+__device__ void site_deltas(const int32_t *ids, int64_t n_chunks, const Cursor &p, int32_t a,
+                            int32_t b, int32_t c, unsigned long long *table) {
+    auto add = [&](int32_t x, int32_t y, long long d) {
+        atomicAdd(&table[table_index(x, y)], (unsigned long long)d);
+    };
+    Cursor l = p, r = p;
+    const int32_t x = live_prev(ids, l);
+    const int32_t y = live_next(ids, n_chunks, r);
+    if (x >= 0) {
+        if (x == c) {
+            add(b, a, -1);
+        } else if (x == a) {
+            long long m = 1;
+            for (Cursor t = l; live_prev(ids, t) == a;) ++m;
+            if (m & 1) add(a, a, -1);
+            add(a, c, 1);
+        } else {
+            add(x, a, -1);
+            add(x, c, 1);
+        }
+    }
+    if (y == c) return;
+    if (x == c) {
+        long long n = 2;
+        for (Cursor t = l; live_prev(ids, t) == c;) ++n;
+        add(c, c, n >> 1);
+    }
+    if (y >= 0) {
+        if (y == b) {
+            long long m = 1;
+            for (Cursor t = r; live_next(ids, n_chunks, t) == b;) ++m;
+            if (m & 1) add(b, b, -1);
+        } else {
+            add(b, y, -1);
+        }
+        add(c, y, 1);
+    }
+}
+
+// After a delta iteration's apply-only stream, on the consistent post-merge corpus: one workgroup
+// per region, one wave per listed chunk (k_apply_loop's site list), every token c of the chunk a
+// site (a site across two chunks lists both; the chunk holding the c owns it).  The deltas go
+// into the u64 table with 64-bit atomic adds (negative ones as two's complement), bins from
+// table_index: hot bins and sketch buckets alike.  The bin of (a, b) loses W; a hot bin must have
+// held exactly W, a sketch bucket at least W (it sums every pair it holds), else LOOP_ERROR.
+__global__ void __launch_bounds__(256)
+k_site_delta(const int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
+             const uint32_t *__restrict__ site_list, const uint32_t *__restrict__ site_n,
+             unsigned long long *__restrict__ table, LoopCtl *ctl) {
+    if (ctl->status != LOOP_RUN || !ctl->delta) return;
+    const int32_t a = ctl->a, b = ctl->b, c = ctl->c;
+    const unsigned long long W = (unsigned long long)ctl->w;
+    const int r = blockIdx.x;
+    if (r >= R) return;
+    if (r == 0 && threadIdx.x == 0) {
+        const int bin = table_index(a, b);
+        const unsigned long long old = atomicAdd(&table[bin], 0ull - W);
+        if (bin < HOT_BINS ? old != W : old < W) {
+            ctl->status = LOOP_ERROR;
+            ctl->err = 3;
+            ctl->err_got = old;
+            ctl->err_want = W;
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = min(site_n[r], (uint32_t)cpr);
+    const uint32_t *seg = site_list + (int64_t)r * cpr;
+    for (uint32_t i = threadIdx.x >> 6; i < n; i += 4) {
+        const int64_t q = seg[i];
+        if (q >= n_chunks) continue;
+        const int4 v = reinterpret_cast<const int4 *>(ids)[q * (CHUNK / 4) + lane];
+        const int32_t l3 = bcast(v.w, 63);
+        Cursor p;
+        p.q = q;
+        p.len = l3 >= SEP ? CHUNK : ((LEN_TAG - l3) & 255);
+        const int32_t t[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (t[e] == c) {
+                p.k = 4 * lane + e;
+                site_deltas(ids, n_chunks, p, a, b, c, table);
+            }
+    }
 }
 
 __device__ __forceinline__ int prev_nonempty(const RegionSum *s, int q) {
@@ -1740,12 +1925,22 @@ __device__ __forceinline__ int next_nonempty(const RegionSum *s, int q, int R) {
 //    = floor(#odd segments / 2) more X X pairs;
 //  - the RegionCarry the next pass needs (neighbour tokens, run-offset parity of the first token).
 template <int MODE>
-__global__ void k_runs(const RegionSum *__restrict__ s, int R, RegionCarry *__restrict__ carry,
-                       unsigned long long *__restrict__ spill, ColdTable ct,
-                       const uint32_t *__restrict__ heavy, const LoopCtl *ctl, int32_t ma = -1,
-                       int32_t mb = -1, int32_t mc = -1, unsigned long long *hot = nullptr,
-                       unsigned long long *delta = nullptr) {
+__device__ __forceinline__ void runs_body(const RegionSum *__restrict__ s, int R,
+                                          RegionCarry *__restrict__ carry,
+                                          unsigned long long *__restrict__ spill, ColdTable ct,
+                                          const uint32_t *__restrict__ heavy, const LoopCtl *ctl,
+                                          int32_t ma, int32_t mb, int32_t mc,
+                                          unsigned long long *hot, unsigned long long *delta,
+                                          const uint32_t *__restrict__ site_n = nullptr,
+                                          unsigned long long *n_listed = nullptr) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (site_n && !loop_off(ctl)) {
+        // the delta form's statistic: chunks listed by the pass, one atomic per wave
+        unsigned n = r < R ? site_n[r] : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
+        if ((threadIdx.x & 63) == 0 && n) atomicAdd(n_listed, (unsigned long long)n);
+    }
     if (r >= R) return;
     // the region and its two neighbours, loaded together before anything else (the loop's state
     // included): one memory latency for the common case, where both neighbours are non-empty and
@@ -1842,6 +2037,29 @@ __global__ void k_runs(const RegionSum *__restrict__ s, int R, RegionCarry *__re
     if (segs > 1 && odd >= 2) add_pairs_global<MODE>(k, x, x, (unsigned long long)(odd >> 1));
 }
 
+template <int MODE>
+__global__ void k_runs(const RegionSum *__restrict__ s, int R, RegionCarry *__restrict__ carry,
+                       unsigned long long *__restrict__ spill, ColdTable ct,
+                       const uint32_t *__restrict__ heavy, const LoopCtl *ctl, int32_t ma = -1,
+                       int32_t mb = -1, int32_t mc = -1, unsigned long long *hot = nullptr,
+                       unsigned long long *delta = nullptr) {
+    runs_body<MODE>(s, R, carry, spill, ct, heavy, ctl, ma, mb, mc, hot, delta);
+}
+
+// The table state's stitch when the delta form is allowed, one launch for either form of the
+// iteration: after a full pass k_runs<MODE_TABLE>; after the apply-only stream the carries alone
+// (k_runs<MODE_NONE>) and the count of the chunks it listed (LoopCtl::delta_chunks).
+__global__ void k_runs_loop(const RegionSum *__restrict__ s, int R, RegionCarry *__restrict__ carry,
+                            unsigned long long *__restrict__ spill, ColdTable ct,
+                            const uint32_t *__restrict__ heavy, LoopCtl *ctl,
+                            const uint32_t *__restrict__ site_n) {
+    if (ctl->delta)
+        runs_body<MODE_NONE>(s, R, carry, nullptr, ct, nullptr, ctl, -1, -1, -1, nullptr, nullptr,
+                             site_n, &ctl->delta_chunks);
+    else
+        runs_body<MODE_TABLE>(s, R, carry, spill, ct, heavy, ctl, -1, -1, -1, nullptr, nullptr);
+}
+
 // Sums the per-workgroup 16-bit LDS partials and the spill table into the u64 table (hot bins
 // [0, 64K), sketch buckets [64K, TABLE_BINS)), zeroes the spill for the next pass, and leaves the
 // best hot key (max_length filter applied) in res->best.  A block owns 128 words (256 bins):
@@ -1873,7 +2091,13 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
                const unsigned long long *__restrict__ rep = nullptr,
                unsigned long long *__restrict__ bin_max = nullptr) {
     __shared__ uint32_t s_sum[REDUCE_GROUPS][32][8];
-    if (loop_off(ctl)) return;
+    // A delta iteration of the device loop (LoopCtl::delta, uniform over the grid): the table is
+    // already current (k_site_delta), so nothing is summed or written; the block only scans its
+    // 256 bins for the best hot key and the largest bin, as after a reduce.  (Both words loaded
+    // before either is tested: one memory latency.)
+    const int32_t status = ctl ? ctl->status : LOOP_RUN;
+    const bool scan = ctl && ctl->delta;
+    if (status != LOOP_RUN) return;
     const int t = threadIdx.x;
     // (sharded: the exchange header carries this shard's replacement count, summed with the table)
     if (hdr && rep && blockIdx.x == 0 && t == 0) hdr[0] = *rep;
@@ -1892,7 +2116,7 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
         acc[7] += p.w >> 16;
     };
     constexpr int RG = REDUCE_GROUPS;
-    int g = grp;
+    int g = scan ? G : grp;
     for (; g + 15 * RG < G; g += 16 * RG) {
         uint4 p[16];
 #pragma unroll
@@ -1920,9 +2144,14 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
         for (int q = 0; q < RG; ++q) sum += s_sum[q][bl][bi];
         // dword w holds bins 2w and 2w + 1 (hot pairs and sketch buckets alike): contiguous writes
         const int bin = blockIdx.x * (2 * REDUCE_WORDS_PER_BLOCK) + t;
-        const unsigned long long v = (unsigned long long)sum + spill[bin];
-        table[bin] = v;
-        spill[bin] = 0;
+        unsigned long long v;
+        if (scan) {
+            v = table[bin];
+        } else {
+            v = (unsigned long long)sum + spill[bin];
+            table[bin] = v;
+            spill[bin] = 0;
+        }
         if (bin < HOT_BINS && v && pair_ok(bin_a(bin), bin_b(bin), len16, max_length))
             k = pack_key(v, bin_a(bin), bin_b(bin));
         vm = v;
@@ -2504,8 +2733,11 @@ __device__ int decide_r3(int tie, unsigned n, const unsigned long long *pos, con
 
 // The decision's writes: the log entry (a, b, W), the new token's UTF-16 length (core.ts:318),
 // the merge the next pass applies, and a Result cleared for the next selection.
+// n_chunks (the single-context loop only; 0: never the delta form): the iteration takes the delta
+// form when the host allows it (the table state), a != b, and the merge's W sites lie in fewer
+// than 1/16 of the chunks, the rule k_step_loop uses for a heavy merge.
 __device__ void decide_commit(LoopCtl *ctl, Result *res, const LoopCtl &C, long long W, int32_t a,
-                              int32_t b, int32_t *len16, long long *log) {
+                              int32_t b, int32_t *len16, long long *log, int64_t n_chunks = 0) {
     const int32_t c = C.next_id;
     len16[c] = len16[a] + len16[b];
     const long long i = C.n_done;
@@ -2520,7 +2752,11 @@ __device__ void decide_commit(LoopCtl *ctl, Result *res, const LoopCtl &C, long 
     ctl->next_id = c + 1;
     ctl->n_done = i + 1;
     const unsigned long long bm = res->bin_max;
-    const int32_t uns = !C.maintained && bm &&
+    const int32_t dl = C.allow_delta && !C.maintained && a != b && (int64_t)W * 16 < n_chunks;
+    ctl->delta = dl;
+    ctl->n_delta = C.n_delta + dl;
+    // (a delta iteration counts nothing: unscreened describes the full passes only)
+    const int32_t uns = !dl && !C.maintained && bm &&
                         (bm - 1) + 2 * (unsigned long long)W < 0x10000ull;
     ctl->unscreened = uns;
     ctl->n_unscreened = C.n_unscreened + uns;
@@ -3188,10 +3424,11 @@ __global__ void __launch_bounds__(256) k_tie(TieArgs A) {
 // the control block, the Result and the candidates (nothing writes them until every block has
 // taken its ticket), scans for rule R3, and the last block to finish (the ticket) commits the
 // decision with the positions every block left.  `ticket` is zero between launches.
-__device__ void fused_commit(const TieArgs &A, const LoopCtl &C, const Result &R, const int2 *sc,
-                             int prop, int32_t *len16, long long *log) {
-    LoopCtl *ctl = const_cast<LoopCtl *>(A.ctl);
-    Result *res = A.res;
+// (the kernel's argument block is not passed on by reference: that pinned it to the stack and cost
+// k_tie_fused 45 registers and 64 bytes of scratch)
+__device__ void fused_commit(LoopCtl *ctl, Result *res, int64_t n_chunks, const LoopCtl &C,
+                             const Result &R, const int2 *sc, int prop, int32_t *len16,
+                             long long *log) {
     if (!decide_check_replaced(ctl, C, R, nullptr, log)) return;
     ctl->w = -1;
     if (prop == 4) {
@@ -3227,7 +3464,7 @@ __device__ void fused_commit(const TieArgs &A, const LoopCtl &C, const Result &R
             return;
         }
     }
-    decide_commit(ctl, res, C, (long long)(R.best >> 17), a, b, len16, log);
+    decide_commit(ctl, res, C, (long long)(R.best >> 17), a, b, len16, log, n_chunks);
 }
 
 __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, long long *log,
@@ -3258,7 +3495,7 @@ __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, lo
     const int prop = s_prop;
     if (prop == 0) return;   // (the batch has ended, or block 0 decides alone)
     if (prop != 1 && prop != 2) {
-        if (threadIdx.x == 0) fused_commit(A, sC, sR, sc, prop, len16, log);   // (block 0 only)
+        if (threadIdx.x == 0) fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log);   // (block 0 only)
         return;
     }
     tie_body(A, (int)sR.n_cand, prop == 1, sc);
@@ -3269,7 +3506,7 @@ __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, lo
     __syncthreads();
     if (!s_last || threadIdx.x != 0) return;
     __threadfence();
-    fused_commit(A, sC, sR, sc, prop, len16, log);
+    fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log);
 }
 
 // Sharded loop: this shard's last tie positions as corpus-wide ones (rank << 40 | position; 0:

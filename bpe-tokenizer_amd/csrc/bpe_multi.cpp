@@ -1037,6 +1037,8 @@ int multi_get_stats(bpe_multi *m, bpe_stats *out) {
         acc.incr_launches += x.incr_launches;
         acc.incr_live += x.incr_live;
         acc.unscreened_passes += x.unscreened_passes;
+        acc.delta_passes += x.delta_passes;
+        acc.delta_chunks += x.delta_chunks;
         acc.xchg_iters = std::max(acc.xchg_iters, x.xchg_iters);
     }
     acc.pix_fallbacks = m->pix_fallbacks;

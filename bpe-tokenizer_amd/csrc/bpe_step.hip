@@ -34,6 +34,17 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
     return hipGetLastError();
 }
 
+// The delta form's apply-only stream (k_apply_loop): the same ring, built with the same flags.
+hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
+                             int64_t cpr, int R, const void *carry, const void *ctl, void *sums,
+                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n) {
+    using namespace bpe;
+    k_apply_loop<<<grid, WG, 0, s>>>(ids, n_chunks, cpr, R, static_cast<const RegionCarry *>(carry),
+                                     static_cast<const LoopCtl *>(ctl),
+                                     static_cast<RegionSum *>(sums), replaced, site_list, site_n);
+    return hipGetLastError();
+}
+
 // The host path's passes of the table state (findNextMerge / applyMerge one call each, the counts
 // after a compaction, core.ts:247-360): k_step<NO_MERGE | MERGE_XY | MERGE_XX, MODE_TABLE>, built
 // here with the same flags as the device loop's pass (in the engine's translation unit, with its

@@ -324,7 +324,11 @@ typedef struct {
     int64_t incr_live;        /* ... and the live corpus tokens summed over them (pair-scans) */
     int64_t unscreened_passes;/* device loop, table state: merge passes whose LDS adds return nothing
                                  and skip the overflow screen (no counter can reach 16 bits: the
-                                 largest table bin + 2 W < 2^16) */
+                                 largest table bin + 2 W < 2^16); full passes only */
+    int64_t delta_passes;     /* device loop, table state: iterations in the delta form (an apply-only
+                                 stream, then the table kept by the deltas of the merge's sites
+                                 instead of a recount; BPE_DELTA=0 turns the form off) */
+    int64_t delta_chunks;     /* ... and the rewritten chunks those streams listed for the site kernel */
 } bpe_stats;
 
 int bpe_stats_enable(bpe_ctx *ctx, int on);
