@@ -33,6 +33,7 @@ C_API = [
     'bpe_read_samples', 'bpe_find_next_merge',
     'bpe_apply_merge', 'bpe_apply_merges', 'bpe_merge_until', 'bpe_stats_enable', 'bpe_get_stats', 'bpe_reset_stats',
     'bpe_get_stream', 'bpe_synth_latin1', 'bpe_synth_zipf', 'bpe_recount', 'bpe_export_counts',
+    'bpe_digest',
     'bpe_heavy_counts', 'bpe_select_counts', 'bpe_tie_positions', 'bpe_rank_loop_begin',
     'bpe_rank_loop_select', 'bpe_rank_loop_decide', 'bpe_rank_loop_count', 'bpe_rank_loop_end',
     'bpe_cold_counts', 'bpe_set_global_counts',
@@ -42,6 +43,9 @@ C_API = [
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
+DIGEST_MOD = 254    # BPE_DIGEST_MOD: the digest plane's code of a token id t >= 0 is t % DIGEST_MOD
+DIGEST_SEP = 254    # BPE_DIGEST_SEP: ... of a sample separator (-1)
+DIGEST_DEAD = 255   # BPE_DIGEST_DEAD: ... of a dead slot (anything below -1)
 MAX_CAND = 16       # BPE_MAX_CAND
 REDUCE_RCCL = 0     # BPE_REDUCE_RCCL
 REDUCE_HOST = 1     # BPE_REDUCE_HOST
@@ -85,6 +89,8 @@ class Stats(ctypes.Structure):
         ('incr_timed', ctypes.c_int64), ('incr_launches', ctypes.c_int64),
         ('incr_live', ctypes.c_int64), ('unscreened_passes', ctypes.c_int64),
         ('delta_passes', ctypes.c_int64), ('delta_chunks', ctypes.c_int64),
+        ('digest_passes', ctypes.c_int64), ('digest_hits', ctypes.c_int64),
+        ('digest_builds', ctypes.c_int64),
     ]
 
     def as_dict(self):
@@ -188,6 +194,7 @@ def lib():
         'bpe_encode_batch': ([vp, i32p, i64p, ctypes.c_int64, i32p, i64p], ctypes.c_int),
         'bpe_encoder_get_stats': ([vp, ctypes.POINTER(EncoderStats)], ctypes.c_int),
         'bpe_encoder_reset_stats': ([vp], ctypes.c_int),
+        'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
         'bpe_synth_latin1': ([ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
@@ -239,6 +246,16 @@ def synth_zipf(n, seed=12345, s=1.1, n_words=32768, sample_bytes=1 << 20, first_
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def digest(ids):
+    """The digest plane's byte of each slot value in `ids` (bpe_digest: the engine's own function;
+    DIGEST_MOD, DIGEST_SEP and DIGEST_DEAD are its parameters)."""
+    x = _i32(ids).ravel()
+    out = np.empty(x.size, dtype=np.uint8)
+    _check(lib().bpe_digest(x.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), x.size,
+                            out.ctypes.data), 'bpe_digest')
+    return out
 
 
 class Engine:

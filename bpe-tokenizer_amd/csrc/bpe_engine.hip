@@ -22,8 +22,10 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
                                   uint32_t *partials, unsigned long long *spill, const void *ct,
                                   void *sums, unsigned long long *replaced);
 hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
-                             int64_t cpr, int R, const void *carry, const void *ctl, void *sums,
-                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n);
+                             int64_t cpr, int R, const void *carry, void *ctl, void *sums,
+                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
+                             uint32_t *plane);
+hipError_t launch_digest_build(hipStream_t s, const int32_t *ids, int64_t n_chunks, uint32_t *plane);
 hipError_t launch_step_table(int merge, unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, int32_t ma, int32_t mb,
                              int32_t mc, uint32_t *partials, unsigned long long *spill,
@@ -66,12 +68,18 @@ inline void dfree(void *p) {
 constexpr int64_t LOOP_BATCH = 64;
 // apply-only replay: merges per host round trip (their replacement counts come back together)
 constexpr int64_t REPLAY_BATCH = 256;
+// a digest plane that went stale inside a batch is rebuilt for the next one only if that batch
+// took the delta form in at least this many iterations, and in at least half of its iterations
+constexpr int64_t DIGEST_REBUILD_MIN = 4;
 
 static_assert(TABLE_BINS == BPE_TABLE_BINS && HOT_BINS == BPE_HOT_BINS, "include/bpe.h table layout");
 static_assert(MAX_CAND == BPE_MAX_CAND && LOOP_BATCH == BPE_LOOP_BATCH, "include/bpe.h rank loop sizes");
 static_assert(XCHG_HDR == BPE_XCHG_HDR && XCHG_WORDS == BPE_XCHG_WORDS && TIE_WORDS == BPE_TIE_WORDS &&
                   DELTA_ROWS == BPE_DELTA_ROWS,
               "include/bpe.h exchange layout");
+static_assert(DIGEST_MOD == BPE_DIGEST_MOD && DIGEST_SEP == BPE_DIGEST_SEP &&
+                  DIGEST_DEAD == BPE_DIGEST_DEAD,
+              "include/bpe.h digest plane");
 
 template <typename T>
 int dev_alloc(T **p, size_t n) {
@@ -170,6 +178,16 @@ struct bpe_ctx {
     // per region (d_sites, sites_cap entries) and each region's count (d_site_n)
     uint32_t *d_sites = nullptr, *d_site_n = nullptr;
     int64_t sites_cap = 0;
+    // the digest plane of the delta form's stream: one byte per slot of d_ids (digest_cap bytes).
+    // Stale unless proven fresh: digest_valid says it matches d_ids, and everything that writes
+    // d_ids outside the loop batch's delta iterations clears it (digest_stale).  digest_changed:
+    // stale by such a write since the last batch (the next batch rebuilds); otherwise a stale
+    // plane is rebuilt only after a batch that took the delta form in at least DIGEST_REBUILD_MIN
+    // and at least half of its iterations (last_delta of last_done).
+    uint32_t *d_digest = nullptr;
+    int64_t digest_cap = 0;
+    bool digest_valid = false, digest_changed = true;
+    int64_t last_delta = 0, last_done = 0;
     unsigned int *d_ticket = nullptr;   // last-block tickets (k_tie_fused, k_select_maint; zero between launches)
     BlockBest *d_brec = nullptr;        // k_select_maint's per-block bests
     // apply-only replay: per-merge replacement counts
@@ -241,6 +259,12 @@ int leave_global(bpe_ctx *c) {
         if (lg_) return lg_;              \
     } while (0)
 
+// d_ids is about to be written (or replaced) by something that does not keep the digest plane.
+void digest_stale(bpe_ctx *c) {
+    c->digest_valid = false;
+    c->digest_changed = true;
+}
+
 void geometry(bpe_ctx *c) {
     const int64_t nc = std::max<int64_t>(1, c->n_chunks);
     c->cpr = (nc + MAX_REGIONS - 1) / MAX_REGIONS;
@@ -285,6 +309,7 @@ int seal_packed(bpe_ctx *c) {
     }
     c->packed = true;
     c->counts_valid = c->carry_valid = false;
+    digest_stale(c);   // (ingest, add, compaction, the position index's write-back, a new corpus)
     c->cold_exact = false;
     c->rl_global = c->rl_delta_pending = false;
     c->cold_list = false;
@@ -548,6 +573,7 @@ int run_pass(bpe_ctx *c, bool merge, int32_t a, int32_t b, int32_t cc, int64_t *
     int rc;
     if (merge && c->pending)
         if ((rc = settle(c))) return rc;
+    if (merge) c->digest_valid = false;   // (a host-path merge; see compact)
     if ((rc = ensure_partials(c))) return rc;
     c->cold_list = false;   // (fused and incremental passes update the cold table)
     if ((rc = sync_len16(c, c->opt_max_length))) return rc;   // the reduce's max_length filter
@@ -684,9 +710,13 @@ int compact(bpe_ctx *c) {
     if ((int64_t)total != c->live_slots)
         return fail(BPE_ERR_STATE, "bpe native: compaction lost slots");
     std::swap(c->d_ids, c->d_tmp);
+    // (the plane goes stale, but the merge loop goes on as before: whether the next batch
+    // rebuilds it is up to the last batch's delta share, as after a host-path merge)
+    const bool dchg = c->digest_changed;
     const bool counts = c->counts_valid, cold_exact = c->cold_exact, sketch = c->sketch_valid;
     const bool glob = c->rl_global, pend = c->rl_delta_pending, list = c->cold_list;
     if ((rc = seal_packed(c))) return rc;
+    c->digest_changed = dchg;
     c->counts_valid = counts;
     c->sketch_valid = sketch;
     c->cold_exact = cold_exact;
@@ -1056,6 +1086,42 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         c->sites_cap = cap;
     }
     hipStream_t s = c->stream;
+    // The delta form's stream reads the digest plane when it is fresh (BPE_DIGEST=0 keeps the int32
+    // stream everywhere, for A/B and checking; read per batch).  A stale plane is rebuilt here when
+    // the corpus was replaced or written from outside the merge loop since the last batch (ingest,
+    // a replay, the position index: the first batch after such a change always builds), and
+    // otherwise (the plane went stale by a full-form merge inside a batch, by a host-path merge
+    // or by a compaction) only if the last batch took the delta form in at least
+    // DIGEST_REBUILD_MIN and at least half of its iterations: a build costs about 1.3 int32
+    // streams, and a batch of heavy merges would clear the plane again at once.  If the plane
+    // cannot be allocated the batch runs on the int32 stream.
+    const char *gknob = getenv("BPE_DIGEST");
+    bool digest = delta_ok && !(gknob && atoi(gknob) == 0) && c->n_chunks > 0;
+    if (digest && c->digest_cap < c->n_chunks * CHUNK) {
+        dfree(c->d_digest);
+        c->d_digest = nullptr;
+        c->digest_cap = 0;
+        c->digest_valid = false;
+        const int64_t cap = (c->cap_slots > 0 ? c->cap_slots : c->n_chunks * CHUNK);
+        void *p = nullptr;
+        if (hipMalloc(&p, (size_t)cap) == hipSuccess) {
+            c->d_digest = static_cast<uint32_t *>(p);
+            c->digest_cap = cap;
+        } else {
+            (void)hipGetLastError();
+            digest = false;
+        }
+    }
+    if (digest && !c->digest_valid) {
+        if (c->digest_changed ||
+            (c->last_delta >= DIGEST_REBUILD_MIN && 2 * c->last_delta >= c->last_done)) {
+            HIP_TRY(bpe_step::launch_digest_build(s, c->d_ids, c->n_chunks, c->d_digest));
+            c->digest_valid = true;
+            if (c->stats_on) c->stats.digest_builds += 1;
+        }
+        c->digest_changed = false;
+    }
+    digest = digest && c->digest_valid;
     if (maint) {
         // (k_select_maint takes the best over the hot bins itself)
         HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
@@ -1076,6 +1142,7 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
     h->maintained = maint ? 1 : 0;
     h->cold_cap = c->cold_cap;
     h->allow_delta = delta_ok ? 1 : 0;
+    h->digest_ok = digest ? 1 : 0;
     HIP_TRY(hipMemcpyAsync(c->d_ctl, h, sizeof *h, hipMemcpyHostToDevice, s));
     TieArgs A;
     memset(&A, 0, sizeof A);
@@ -1138,7 +1205,8 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
             if (delta_ok)
                 HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
                                                     c->d_carry, c->d_ctl, c->d_sums,
-                                                    &c->d_res->replaced, c->d_sites, c->d_site_n));
+                                                    &c->d_res->replaced, c->d_sites, c->d_site_n,
+                                                    c->d_digest));
         }
         HIP_TRY(hipGetLastError());
         if ((rc = span_end(c, e_step, maint && c->use_incr ? 2 : 0))) return rc;
@@ -1181,6 +1249,11 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
     HIP_TRY(hipMemcpyAsync(c->h_log, c->d_log, LOG_WORDS * n * sizeof(long long),
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    // (a batch without the plane's stream may have rewritten chunks: whatever plane there is is
+    // stale; so is one a full-form merge of this batch passed by)
+    if (!h->digest_ok) c->digest_valid = false;
+    c->last_delta = h->n_delta;
+    c->last_done = h->n_done;
     const int64_t nd = h->n_done;
     if (h->status == LOOP_ERROR)
         return fail(BPE_ERR_STATE,
@@ -1241,6 +1314,8 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         c->stats.loop_host += h->n_host;
         c->stats.delta_passes += h->n_delta;
         c->stats.delta_chunks += (int64_t)h->delta_chunks;
+        c->stats.digest_passes += h->n_digest;
+        c->stats.digest_hits += (int64_t)h->digest_hits;
     }
     c->last_replaced = nd ? c->h_log[LOG_WORDS * (nd - 1) + 2] : c->last_replaced;
     // every early-ended batch of the table state leaves the last reduce's best key in the Result
@@ -1434,6 +1509,7 @@ int rank_loop_decide(bpe_ctx *c) {
 int rank_loop_count(bpe_ctx *c) {
     if (!c->rl_open) return fail(BPE_ERR_STATE, "bpe native: rank loop not begun");
     if (c->rl_pix) return pix_rank_count(c);
+    digest_stale(c);   // (the rank loop's passes keep no plane)
     hipStream_t s = c->stream;
     unsigned long long *x = c->rl_table;
     hipEvent_t e_step = span_begin(c);
@@ -1701,6 +1777,7 @@ int replay(bpe_ctx *c, const int32_t *abc, int64_t n, int64_t *replaced, bool co
             if ((rc = register_merge(c, m[0], m[1], m[2]))) return rc;
         }
         geometry(c);
+        digest_stale(c);   // (k_apply rewrites chunks without the plane)
         hipStream_t s = c->stream;
         HIP_TRY(hipMemsetAsync(c->d_repl, 0, nb * sizeof(unsigned long long), s));
         for (int64_t j = 0; j < nb; ++j) {
@@ -1932,6 +2009,7 @@ int pix_build_timed(bpe_ctx *c, int64_t max_length) {
     const uint32_t N = (uint32_t)n;
     PixCorpus &C = P->C;
     C.tok = c->d_ids;
+    digest_stale(c);   // (the index merges in place in d_ids)
     C.n = N;
     if ((rc = pix_alloc(P, &C.nxt, N)) || (rc = pix_alloc(P, &C.prv, N))) return rc;
     const uint64_t pool_cap = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)N + std::max<uint64_t>(N / 2, 1u << 22));
@@ -2077,6 +2155,7 @@ int pix_finish(bpe_ctx *c) {
             return fail(BPE_ERR_STATE, "bpe native: position index: live slots lost");
     }
     std::swap(c->d_ids, c->d_tmp);
+    digest_stale(c);
     pix_free(c);
     return seal_packed(c);
 }
@@ -2573,6 +2652,12 @@ extern "C" {
 
 int bpe_version(void) { return 200; }
 
+int bpe_digest(const int32_t *ids, int64_t n, uint8_t *out) {
+    if (n < 0 || (n > 0 && (!ids || !out))) return fail(BPE_ERR_ARG, "bpe native: bad digest arguments");
+    for (int64_t i = 0; i < n; ++i) out[i] = (uint8_t)digest_of(ids[i]);
+    return BPE_OK;
+}
+
 int bpe_last_error(char *buf, size_t cap) {
     if (!buf || !cap) return BPE_ERR_ARG;
     snprintf(buf, cap, "%s", g_err.c_str());
@@ -2682,7 +2767,7 @@ int bpe_destroy(bpe_ctx *c) {
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
                     c->cold.bmax, c->cold.bdirty, c->cold.blist,
                     c->d_ctl, c->d_log, c->d_repl, c->d_ticket, c->d_brec, c->d_sites,
-                    c->d_site_n};
+                    c->d_site_n, c->d_digest};
     for (void *p : ptrs) dfree(p);
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_cand) (void)hipHostFree(c->h_cand);

@@ -225,8 +225,16 @@ struct LoopCtl {
     int32_t delta;
     int32_t allow_delta;
     int32_t n_delta;        // decisions that set it, in this batch
-    int32_t pad_;
+    // The digest plane (one byte per slot, digest_of) matches the corpus: a delta iteration then
+    // finds its sites through the plane (digest_body) instead of streaming the int32 slots.  Set
+    // by the host at the batch start, cleared by the decision that commits a merge with W > 0 in
+    // the full form (the full pass rewrites chunks without the plane): stale for the rest of the
+    // batch.
+    int32_t digest_ok;
     unsigned long long delta_chunks;   // chunks listed by the delta iterations of this batch
+    unsigned long long digest_hits;    // chunks the digest stream took to the exact path
+    int32_t n_digest;       // delta iterations on the plane, in this batch
+    int32_t pad_;
 };
 
 
@@ -1756,18 +1764,375 @@ k_step_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
                                   ct, nullptr, sums, replaced, hot_g, delta);
 }
 
+// ---- the digest plane -----------------------------------------------------------------------
+// One byte per corpus slot, in the chunk geometry (chunk j's 256 digests are bytes [256 j,
+// 256 j + 256) of the plane): a token id t >= 0 maps to t % DIGEST_MOD (merged ids are allocated
+// in sequence, so the codes fill evenly), SEP to DIGEST_SEP, every dead slot (TOMB, TOMB_ODD, a
+// tail tag: anything below SEP) to DIGEST_DEAD.  The int32 corpus stays the record; only the delta
+// form's stream reads the plane, to find the few chunks that can hold a site of the merge.
+// (include/bpe.h BPE_DIGEST_*, mirrored by the package's DIGEST_* and digest())
+constexpr uint32_t DIGEST_MOD = 254, DIGEST_SEP = 254, DIGEST_DEAD = 255;
+
+__host__ __device__ __forceinline__ uint32_t digest_of(int32_t t) {
+    return t >= 0 ? (uint32_t)t % DIGEST_MOD : t == SEP ? DIGEST_SEP : DIGEST_DEAD;
+}
+
+__device__ __forceinline__ uint32_t digest4(const int32_t (&t)[4]) {
+    return digest_of(t[0]) | (digest_of(t[1]) << 8) | (digest_of(t[2]) << 16) |
+           (digest_of(t[3]) << 24);
+}
+
+// The plane of the whole corpus in one pass: 4 B read and 1 B written per slot.
+__global__ void __launch_bounds__(256)
+k_digest_build(const int32_t *__restrict__ ids, int64_t n_chunks, uint32_t *__restrict__ plane) {
+    const int64_t n = n_chunks * (CHUNK / 4);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int4 v = reinterpret_cast<const int4 *>(ids)[i];
+        const int32_t t[4] = {v.x, v.y, v.z, v.w};
+        plane[i] = digest4(t);
+    }
+}
+
+// The digest stream's ring: wave-loads of 16 B per lane (1 KiB: the digests of four chunks, lane L
+// holding bytes 16 (L & 15) .. + 15 of chunk L >> 4), DG_RING of them per round, loaded DG_LEAD
+// ahead.  A round covers 32 chunks: one bit each in the round's hit mask.
+constexpr int DG_RING = 8;
+constexpr int DG_LEAD = 6;
+static_assert(DG_LEAD >= 2 && DG_LEAD <= DG_RING - 1, "digest ring lead");
+static_assert(4 * DG_RING == 32, "a round's chunks fill a 32-bit hit mask");
+// Chunks the region sums' walks read from either end of a rewritten region before its wave
+// tallies the whole region instead (region_tally).
+constexpr int DG_WALK = 2;
+
+// Zero-halfword test of y, before the 0x80008000 mask (exact as an any-test: a borrow reaches a
+// halfword only from a zero halfword below it).
+__device__ __forceinline__ uint32_t hz16(uint32_t y) { return (y - 0x00010001u) & ~y; }
+
+// The sums of one region tallied from its int32 slots (the apply-only pass's count, chunk by
+// chunk with synchronous loads): the digest stream's slow path, for a region whose first or last
+// run is longer than the walks below read.
+__device__ __forceinline__ RegionSum region_tally(const __amdgpu_buffer_rsrc_t rs, int nc, int lane) {
+    Sink k{};
+    k.ma = -1;
+    Tally s;
+    s.n_live = 0;
+    s.lead_len = 0;
+    s.prev = NONE;
+    s.par = 0;
+    s.first_tok = NONE;
+    s.in_lead = 1;
+    s.seen = 0;
+    Defer df;
+    Prep pp;
+    pp.ok = 0;
+    Chunk prv;
+    prv.len = 0;
+    for (int c = 0; c < nc; ++c) {
+        Chunk cur;
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, c * (CHUNK * 4), 0);
+        cur.t[0] = (int)x[0];
+        cur.t[1] = (int)x[1];
+        cur.t[2] = (int)x[2];
+        cur.t[3] = (int)x[3];
+        finish_load(cur);
+        if (cur.len == 0) continue;
+        if (prv.len) count_chunk<MODE_NONE, false>(prv, cur.first, lane, s, k, df, pp);
+        prv = cur;
+    }
+    if (prv.len) count_chunk<MODE_NONE, true>(prv, NONE, lane, s, k, df, pp);
+    RegionSum o;
+    o.n_live = s.n_live;
+    o.first_tok = s.n_live ? s.first_tok : NONE;
+    o.last_tok = s.n_live ? s.prev : NONE;
+    o.uniform = s.n_live && s.in_lead ? 1 : 0;
+    o.lead_len = s.in_lead ? s.n_live : s.lead_len;
+    o.trail_odd = s.par ^ 1;
+    return o;
+}
+
+// The sums of a region the digest stream rewrote (n_live = its live slots now): the first run from
+// the first non-empty chunk on, the last run from the last non-empty chunk back, each walk reading
+// at most DG_WALK non-empty chunks; past that, the whole region's tally.  Field for field what the
+// int32 stream's count leaves (step_body).
+__device__ __forceinline__ RegionSum region_resum(const __amdgpu_buffer_rsrc_t rs, int nc, int lane,
+                                                  int64_t n_live) {
+    RegionSum o;
+    o.n_live = n_live;
+    o.lead_len = 0;
+    o.first_tok = NONE;
+    o.last_tok = NONE;
+    o.uniform = 0;
+    o.trail_odd = 1;
+    if (n_live <= 0) return o;
+    auto load = [&](Chunk &q, int c) __attribute__((always_inline)) {
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, c * (CHUNK * 4), 0);
+        q.t[0] = (int)x[0];
+        q.t[1] = (int)x[1];
+        q.t[2] = (int)x[2];
+        q.t[3] = (int)x[3];
+        finish_load(q);
+    };
+    // live slots of q that differ from t, per plane e
+    auto differ = [&](const Chunk &q, int32_t t, unsigned long long (&m)[4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = __ballot(q.t[e] != t) & lanes_upto(q.len, e);
+    };
+    // forward: the first live token and the length of its run
+    int64_t lead = 0;
+    bool open = true, slow = false;
+    int walked = 0;
+    for (int c = 0; c < nc && open; ++c) {
+        Chunk q;
+        load(q, c);
+        if (q.len == 0) continue;
+        if (walked == DG_WALK) {
+            slow = true;
+            break;
+        }
+        ++walked;
+        if (lead == 0) o.first_tok = q.first;
+        if (o.first_tok < 0) {   // (a separator is a run of its own)
+            lead = 1;
+            break;
+        }
+        unsigned long long m[4];
+        differ(q, o.first_tok, m);
+        int f = q.len;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (m[e]) f = min(f, 4 * (int)__builtin_ctzll(m[e]) + e);
+        lead += f;
+        if (f < q.len) open = false;
+        if (lead == n_live) break;
+    }
+    o.lead_len = lead;
+    if (!slow && lead == n_live) {   // one single run
+        o.last_tok = o.first_tok;
+        o.uniform = 1;
+        o.trail_odd = (int32_t)(n_live & 1);
+        return o;
+    }
+    // backward: the last live token and the length of its run (it starts inside the region)
+    int64_t trail = 0;
+    walked = 0;
+    for (int c = nc - 1; c >= 0 && !slow; --c) {
+        Chunk q;
+        load(q, c);
+        if (q.len == 0) continue;
+        if (walked == DG_WALK) {
+            slow = true;
+            break;
+        }
+        ++walked;
+        if (trail == 0) o.last_tok = q.last;
+        if (o.last_tok < 0) {
+            trail = 1;
+            break;
+        }
+        unsigned long long m[4];
+        differ(q, o.last_tok, m);
+        int kmax = -1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (m[e]) kmax = max(kmax, 4 * (63 - (int)__builtin_clzll(m[e])) + e);
+        trail += q.len - 1 - kmax;
+        if (kmax >= 0) break;
+    }
+    o.trail_odd = (int32_t)(trail & 1);
+    if (slow) return region_tally(rs, nc, lane);
+    return o;
+}
+
+// The delta form's stream over the digest plane: the structure of step_body<MERGE_XY, MODE_NONE,
+// .., SITES> (one wave per region, its chunks in order, RegionCarry for the region's edges) with
+// digest words in the ring.  With (da, db) the digests of (a, b), a chunk goes to the exact path
+// (its 1 KiB of int32 slots loaded, apply_chunk as in the int32 stream) when
+//  - some byte equals da and the byte to its right equals db (the right of a chunk's byte 255 is
+//    byte 0 of the next chunk, already in the ring; of the region's last byte, next_tok's digest);
+//  - some byte equals da and the byte to its right is DIGEST_DEAD: that a-alike is the chunk's
+//    last live token, its true neighbour lies beyond a dead tail or an empty chunk;
+//  - a match is pending (ap.match): the chunk before ended in a real `a` whose neighbour, a real
+//    `b`, is this chunk's first live token and has to go (an empty chunk hands the match on).
+// Complete for a != b: a site is a live `a` whose next live token is `b`, and that `b` is either
+// the next byte of the same chunk or `a` is its chunk's last live token.  A false hit (a digest
+// alias) costs one chunk load.  The halfword pairs of a dword and of the dword shifted down one
+// byte are compared with the two keys at once: xor, then the zero-halfword test.
+// A rewritten chunk's digests are stored with it and the chunk is listed for k_site_delta.  The
+// region's sums are left as the last pass wrote them unless a chunk was rewritten; then n_live
+// loses the removed slots and the edge fields are read again (region_resum).
+__device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t *__restrict__ plane,
+                                            int64_t n_chunks, int64_t cpr, int R,
+                                            const RegionCarry *__restrict__ carry, int32_t ma,
+                                            int32_t mb, int32_t mc, RegionSum *__restrict__ sums,
+                                            unsigned long long *__restrict__ replaced,
+                                            uint32_t *__restrict__ site_list,
+                                            uint32_t *__restrict__ site_n,
+                                            unsigned long long *__restrict__ n_hits) {
+    const int lane = threadIdx.x & 63;
+    const int r = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6)));
+    if (r >= R) return;
+    const int64_t c0 = (int64_t)r * cpr;
+    const int64_t c1 = min(c0 + cpr, n_chunks);
+    const int nc = (int)(c1 > c0 ? c1 - c0 : 0);
+    const RegionCarry rc = carry[r];
+    Apply ap;
+    ap.prev = rc.prev_tok;
+    ap.par = 0;
+    ap.match = 0;
+    ap.n_match = 0;
+    ap.sites = site_list + c0;
+    ap.n_sites = 0;
+    ap.c0 = (uint32_t)c0;
+    Prep pp;
+    pp.ok = 0;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        ids + c0 * CHUNK, 0, nc * CHUNK * 4, 0x00020000);
+    // (the plane's loads past the region return 0 and are masked off below)
+    const __amdgpu_buffer_rsrc_t ps = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<uint8_t *>(plane) + c0 * CHUNK, 0, nc * CHUNK, 0x00020000);
+    auto live_from = [&](int c, int32_t f0) -> int32_t {
+        int32_t v = c < nc ? f0 : rc.next_tok;
+        if (__builtin_expect(v < SEP, 0)) {
+            int q = c + 1;
+            for (; q < nc; ++q) {
+                v = __builtin_amdgcn_readfirstlane(
+                    (int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, q * (CHUNK * 4), 0));
+                if (v >= SEP) break;
+            }
+            if (q >= nc) v = rc.next_tok;
+        }
+        return v;
+    };
+    auto slot0 = [&](int c) -> int32_t {
+        return __builtin_amdgcn_readfirstlane(
+            (int)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, c * (CHUNK * 4), 0));
+    };
+    uint32_t hits = 0;
+    int32_t removed = 0;
+    // the exact path of chunk c: what the int32 stream's stage does for it
+    auto exact = [&](int c) {
+        Chunk q;
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, c * (CHUNK * 4), 0);
+        // (slot 0 of the next chunk in the same round trip; past the region the load returns 0
+        // and live_from takes next_tok)
+        const int32_t f1 = slot0(c + 1);
+        q.t[0] = (int)x[0];
+        q.t[1] = (int)x[1];
+        q.t[2] = (int)x[2];
+        q.t[3] = (int)x[3];
+        finish_load(q);
+        ++hits;
+        if (q.len == 0) return;   // (an empty chunk hands the pending match on)
+        const int32_t nx = live_from(c + 1, f1);
+        const int len0 = q.len;
+        const uint32_t ns0 = ap.n_sites;
+        apply_chunk<MERGE_XY, false, true>(q, nx, ma, mb, mc, rs, c, lane, ap, pp, 0u);
+        if (ap.n_sites != ns0) {
+            removed += len0 - q.len;
+            __builtin_amdgcn_raw_buffer_store_b32(digest4(q.t), ps, lane * 4, c * CHUNK, 0);
+        }
+    };
+    if (nc > 0) {
+        // does the token before the region match the region's first live token?
+        const int32_t f = live_from(0, slot0(0));
+        ap.match = ((uint32_t)(ap.prev ^ ma) | (uint32_t)(f ^ mb)) == 0u;
+        const uint32_t da = digest_of(ma), db = digest_of(mb);
+        const uint32_t K1 = (da | (db << 8)) * 0x00010001u;
+        const uint32_t K2 = (da | (DIGEST_DEAD << 8)) * 0x00010001u;
+        // the byte after the region's last: the digest of the first live token after the region,
+        // in byte 0 of lane lp of wave-load gp
+        const uint32_t dnext = digest_of(rc.next_tok);
+        const int gp = nc >> 2, lp = (nc & 3) * 16;
+        auto load = [&](uint4 &q, int g) __attribute__((always_inline)) {
+            const auto x = __builtin_amdgcn_raw_buffer_load_b128(ps, lane * 16, g * (4 * CHUNK), BPE_LOAD_AUX);
+            q.x = x[0];
+            q.y = x[1];
+            q.z = x[2];
+            q.w = x[3];
+        };
+        uint32_t rm = 0;   // the round's hit chunks
+        auto stage = [&](const uint4 &cur, const uint4 &nxt, uint4 &fre, int g, int i)
+                         __attribute__((always_inline)) {
+            load(fre, g + DG_LEAD);
+            uint32_t d0 = cur.x;
+            if (g == gp) d0 = lane == lp ? dnext : d0;
+            const uint32_t fill = (g + 1 == gp && lp == 0) ? dnext
+                                                           : (uint32_t)bcast((int32_t)nxt.x, 0);
+            const uint32_t d[5] = {d0, cur.y, cur.z, cur.w,
+                                   (uint32_t)from_next((int32_t)d0, (int32_t)fill)};
+            uint32_t h = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t sft = __builtin_amdgcn_alignbyte(d[e + 1], d[e], 1);
+                h |= hz16(d[e] ^ K1) | hz16(d[e] ^ K2) | hz16(sft ^ K1) | hz16(sft ^ K2);
+            }
+            // (the chunks of the wave-load that lie in the region)
+            const int v = nc - 4 * g;
+            const unsigned long long valid = v >= 4 ? ~0ull : v <= 0 ? 0ull : ((1ull << (16 * v)) - 1ull);
+            const unsigned long long H = __ballot((h & 0x80008000u) != 0u) & valid;
+            if (H != 0ull) {
+                const uint32_t lo = (uint32_t)H, hi = (uint32_t)(H >> 32);
+                const uint32_t b = (uint32_t)((lo & 0xFFFFu) != 0u) | ((uint32_t)((lo >> 16) != 0u) << 1) |
+                                   ((uint32_t)((hi & 0xFFFFu) != 0u) << 2) | ((uint32_t)((hi >> 16) != 0u) << 3);
+                rm |= b << (4 * i);
+            }
+        };
+        uint4 S[DG_RING];   // (constant indices only: the ring stays in registers)
+        static_for<0, DG_LEAD>([&](auto i) __attribute__((always_inline)) { load(S[i], i); });
+        const int ng = (nc + 3) >> 2;
+        for (int g0 = 0; g0 < ng; g0 += DG_RING) {
+            rm = 0;
+            static_for<0, DG_RING>([&](auto I) __attribute__((always_inline)) {
+                constexpr int i = decltype(I)::value;
+                stage(S[i], S[(i + 1) % DG_RING], S[(i + DG_LEAD) % DG_RING], g0 + i, i);
+            });
+            if ((rm | (uint32_t)ap.match) != 0u) {
+                // the round's hit chunks in order (a pending match takes the next chunk as it is)
+                const int cb = 4 * g0;
+                for (int k = 0; k < 32;) {
+                    if (!ap.match) {
+                        const uint32_t rest = rm >> k;
+                        if (rest == 0u) break;
+                        k += __builtin_ctz(rest);
+                    }
+                    if (cb + k >= nc) break;
+                    exact(cb + k);
+                    ++k;
+                }
+            }
+        }
+    }
+    if (ap.n_sites) {
+        const RegionSum o = region_resum(rs, nc, lane, sums[r].n_live - removed);
+        if (lane == 0) sums[r] = o;
+    }
+    if (lane == 0) {
+        if (ap.n_match) atomicAdd(replaced, (unsigned long long)ap.n_match);
+        if (hits) atomicAdd(n_hits, (unsigned long long)hits);
+        site_n[r] = ap.n_sites;
+    }
+}
+
 // The delta form's apply-only stream: the merge in the LoopCtl applied as by k_apply<MERGE_XY> (no
 // LDS table, no slab, no pair counted; the region sums kept, so k_runs<MODE_NONE> rebuilds the
-// carries and a full pass can follow), every rewritten chunk listed for k_site_delta.
+// carries and a full pass can follow), every rewritten chunk listed for k_site_delta.  With a
+// fresh digest plane (LoopCtl::digest_ok) the sites are found through it (digest_body), else by
+// streaming the int32 slots: one launch, a uniform branch between the two bodies.
 __global__ void __launch_bounds__(WG)
 k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
-             const RegionCarry *__restrict__ carry, const LoopCtl *__restrict__ ctl,
+             const RegionCarry *__restrict__ carry, LoopCtl *__restrict__ ctl,
              RegionSum *__restrict__ sums, unsigned long long *__restrict__ replaced,
-             uint32_t *__restrict__ site_list, uint32_t *__restrict__ site_n) {
+             uint32_t *__restrict__ site_list, uint32_t *__restrict__ site_n,
+             uint32_t *__restrict__ plane) {
     if (ctl->status != LOOP_RUN || !ctl->delta) return;
-    step_body<MERGE_XY, MODE_NONE, true, true, true>(
-        nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,
-        ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n);
+    if (ctl->digest_ok)
+        digest_body(ids, plane, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, sums, replaced,
+                    site_list, site_n, &ctl->digest_hits);
+    else
+        step_body<MERGE_XY, MODE_NONE, true, true, true>(
+            nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,
+            ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n);
 }
 
 // ---- the delta form's site kernel -----------------------------------------------------------
@@ -2755,6 +3120,10 @@ __device__ void decide_commit(LoopCtl *ctl, Result *res, const LoopCtl &C, long 
     const int32_t dl = C.allow_delta && !C.maintained && a != b && (int64_t)W * 16 < n_chunks;
     ctl->delta = dl;
     ctl->n_delta = C.n_delta + dl;
+    // (the plane goes stale with the first full pass that rewrites a chunk)
+    const int32_t dg = C.digest_ok && (dl || W <= 0);
+    ctl->digest_ok = dg;
+    ctl->n_digest = C.n_digest + (dl && dg);
     // (a delta iteration counts nothing: unscreened describes the full passes only)
     const int32_t uns = !dl && !C.maintained && bm &&
                         (bm - 1) + 2 * (unsigned long long)W < 0x10000ull;

@@ -1039,6 +1039,9 @@ int multi_get_stats(bpe_multi *m, bpe_stats *out) {
         acc.unscreened_passes += x.unscreened_passes;
         acc.delta_passes += x.delta_passes;
         acc.delta_chunks += x.delta_chunks;
+        acc.digest_passes += x.digest_passes;
+        acc.digest_hits += x.digest_hits;
+        acc.digest_builds += x.digest_builds;
         acc.xchg_iters = std::max(acc.xchg_iters, x.xchg_iters);
     }
     acc.pix_fallbacks = m->pix_fallbacks;

@@ -34,14 +34,26 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
     return hipGetLastError();
 }
 
-// The delta form's apply-only stream (k_apply_loop): the same ring, built with the same flags.
+// The delta form's apply-only stream (k_apply_loop): the same ring, built with the same flags,
+// and beside it the stream over the digest plane (digest_body; plane: one byte per slot, read
+// only when the LoopCtl says it is fresh).
 hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
-                             int64_t cpr, int R, const void *carry, const void *ctl, void *sums,
-                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n) {
+                             int64_t cpr, int R, const void *carry, void *ctl, void *sums,
+                             unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
+                             uint32_t *plane) {
     using namespace bpe;
     k_apply_loop<<<grid, WG, 0, s>>>(ids, n_chunks, cpr, R, static_cast<const RegionCarry *>(carry),
-                                     static_cast<const LoopCtl *>(ctl),
-                                     static_cast<RegionSum *>(sums), replaced, site_list, site_n);
+                                     static_cast<LoopCtl *>(ctl), static_cast<RegionSum *>(sums),
+                                     replaced, site_list, site_n, plane);
+    return hipGetLastError();
+}
+
+// The digest plane of the whole corpus (k_digest_build).
+hipError_t launch_digest_build(hipStream_t s, const int32_t *ids, int64_t n_chunks, uint32_t *plane) {
+    using namespace bpe;
+    const int64_t blocks = (n_chunks * (CHUNK / 4) + 255) / 256;
+    k_digest_build<<<(unsigned)(blocks < 1 ? 1 : blocks > 16384 ? 16384 : blocks), 256, 0, s>>>(
+        ids, n_chunks, plane);
     return hipGetLastError();
 }
 

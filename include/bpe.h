@@ -161,6 +161,15 @@ int bpe_merge_until(bpe_ctx *ctx, int64_t max_length, int64_t min_weight, int64_
 #define BPE_HOT_BINS 65536
 #define BPE_TABLE_BINS 81920
 
+/* The digest plane of the device loop's delta form: one byte per corpus slot.  A token id t >= 0
+ * has the digest t % BPE_DIGEST_MOD, a sample separator BPE_DIGEST_SEP, every dead slot
+ * BPE_DIGEST_DEAD; ids with equal digests alias (an alias costs a chunk load, never a result). */
+#define BPE_DIGEST_MOD 254
+#define BPE_DIGEST_SEP 254
+#define BPE_DIGEST_DEAD 255
+/* out[i] = the digest of the slot value ids[i] (host arrays; needs no context and no device). */
+int bpe_digest(const int32_t *ids, int64_t n, uint8_t *out);
+
 /* This shard's table for the current corpus (one streaming pass if none is cached). */
 int bpe_export_counts(bpe_ctx *ctx, uint64_t *table);
 
@@ -329,6 +338,12 @@ typedef struct {
                                  stream, then the table kept by the deltas of the merge's sites
                                  instead of a recount; BPE_DELTA=0 turns the form off) */
     int64_t delta_chunks;     /* ... and the rewritten chunks those streams listed for the site kernel */
+    int64_t digest_passes;    /* ... of the delta iterations, those whose stream read the digest plane
+                                 (one byte per slot) instead of the int32 slots; BPE_DIGEST=0 keeps
+                                 the int32 stream everywhere */
+    int64_t digest_hits;      /* ... the chunks those streams took to the exact path (true sites,
+                                 digest aliases, an a-alike last in its chunk, pending matches) */
+    int64_t digest_builds;    /* builds of the digest plane (one pass over the int32 corpus each) */
 } bpe_stats;
 
 int bpe_stats_enable(bpe_ctx *ctx, int on);
