@@ -179,11 +179,13 @@ struct bpe_ctx {
     uint32_t *d_sites = nullptr, *d_site_n = nullptr;
     int64_t sites_cap = 0;
     // the digest plane of the delta form's stream: one byte per slot of d_ids (digest_cap bytes).
-    // Stale unless proven fresh: digest_valid says it matches d_ids, and everything that writes
-    // d_ids outside the loop batch's delta iterations clears it (digest_stale).  digest_changed:
-    // stale by such a write since the last batch (the next batch rebuilds); otherwise a stale
-    // plane is rebuilt only after a batch that took the delta form in at least DIGEST_REBUILD_MIN
-    // and at least half of its iterations (last_delta of last_done).
+    // Stale unless proven fresh: digest_valid says it matches d_ids.  Every function that enqueues
+    // a write of d_ids clears it (digest_stale, with the writer's class: DigestWriter below); the
+    // only proof of freshness is a build, or a batch's control block that comes back with
+    // digest_ok still set (digest_end_batch).  digest_changed: stale by a write from outside the
+    // merge loop since the last batch (the next batch rebuilds); otherwise a stale plane is
+    // rebuilt only after a batch that took the delta form in at least DIGEST_REBUILD_MIN and at
+    // least half of its iterations (last_delta of last_done).
     uint32_t *d_digest = nullptr;
     int64_t digest_cap = 0;
     bool digest_valid = false, digest_changed = true;
@@ -259,10 +261,68 @@ int leave_global(bpe_ctx *c) {
         if (lg_) return lg_;              \
     } while (0)
 
+// ---- the digest plane's freshness (bpe_ctx::d_digest) ------------------------------------------
+// Who writes d_ids, by what the write means for a stale plane:
+//  WRITER_LOOP     the merge loop itself: a host-path merge (enqueue_pass), a pass of the device
+//                  loop (enqueue_loop_pass: the full form, or a batch without the plane) and a
+//                  compaction.  The loop goes on as before, so whether the next batch rebuilds is
+//                  left to the last batch's delta share.
+//  WRITER_OUTSIDE  everything else: ingest and a replaced corpus (seal_packed), a replay
+//                  (enqueue_apply), the position index (its build merges in place, pix_finish
+//                  writes the corpus back) and the rank loop's passes.  The next batch rebuilds.
+enum DigestWriter { WRITER_LOOP, WRITER_OUTSIDE };
+
 // d_ids is about to be written (or replaced) by something that does not keep the digest plane.
-void digest_stale(bpe_ctx *c) {
+void digest_stale(bpe_ctx *c, DigestWriter w) {
     c->digest_valid = false;
-    c->digest_changed = true;
+    if (w == WRITER_OUTSIDE) c->digest_changed = true;
+}
+
+// Before a batch of the device loop whose iterations may take the delta form: whether their
+// stream reads the digest plane (BPE_DIGEST=0 keeps the int32 stream everywhere, for A/B and
+// checking; read per batch).  A stale plane is rebuilt here when the corpus was written from
+// outside the merge loop since the last batch (the first batch after such a change always
+// builds), and otherwise only if the last batch took the delta form in at least
+// DIGEST_REBUILD_MIN and at least half of its iterations: a build costs about 1.3 int32 streams,
+// and a batch of heavy merges would clear the plane again at once.  If the plane cannot be
+// allocated the batch runs on the int32 stream.
+int digest_begin_batch(bpe_ctx *c, bool *fresh) {
+    *fresh = false;
+    const char *gknob = getenv("BPE_DIGEST");
+    if ((gknob && atoi(gknob) == 0) || c->n_chunks <= 0) return BPE_OK;
+    if (c->digest_cap < c->n_chunks * CHUNK) {
+        dfree(c->d_digest);
+        c->d_digest = nullptr;
+        c->digest_cap = 0;
+        c->digest_valid = false;
+        const int64_t cap = (c->cap_slots > 0 ? c->cap_slots : c->n_chunks * CHUNK);
+        void *p = nullptr;
+        if (hipMalloc(&p, (size_t)cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return BPE_OK;
+        }
+        c->d_digest = static_cast<uint32_t *>(p);
+        c->digest_cap = cap;
+    }
+    if (!c->digest_valid) {
+        if (c->digest_changed ||
+            (c->last_delta >= DIGEST_REBUILD_MIN && 2 * c->last_delta >= c->last_done)) {
+            HIP_TRY(bpe_step::launch_digest_build(c->stream, c->d_ids, c->n_chunks, c->d_digest));
+            c->digest_valid = true;
+            if (c->stats_on) c->stats.digest_builds += 1;
+        }
+        c->digest_changed = false;
+    }
+    *fresh = c->digest_valid;
+    return BPE_OK;
+}
+
+// After a batch, from its control block: fresh only if the batch began on a fresh plane and every
+// merge took its stream (a full-form merge clears digest_ok on the device); and the delta share.
+void digest_end_batch(bpe_ctx *c, const LoopCtl *h) {
+    c->digest_valid = h->digest_ok != 0;
+    c->last_delta = h->n_delta;
+    c->last_done = h->n_done;
 }
 
 void geometry(bpe_ctx *c) {
@@ -299,7 +359,8 @@ int ensure_chunks(bpe_ctx *c, int64_t chunks) {
 }
 
 // After writing live slots [0, live_slots) densely: TOMB to the end of the last chunk, SEP spare.
-int seal_packed(bpe_ctx *c) {
+// The layout is new (the carries go with it); what the corpus holds is the caller's matter.
+int seal_tail(bpe_ctx *c) {
     c->n_chunks = (c->live_slots + CHUNK - 1) / CHUNK;
     const int64_t end = c->n_chunks * CHUNK;
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(c->d_ids + end), SEP, CHUNK, c->stream));
@@ -308,13 +369,19 @@ int seal_packed(bpe_ctx *c) {
         HIP_TRY(hipGetLastError());
     }
     c->packed = true;
-    c->counts_valid = c->carry_valid = false;
-    digest_stale(c);   // (ingest, add, compaction, the position index's write-back, a new corpus)
+    c->carry_valid = false;
+    geometry(c);
+    return BPE_OK;
+}
+
+// A corpus with other contents (ingest, add, clear, the index's write-back): nothing counted holds.
+int seal_packed(bpe_ctx *c) {
+    c->counts_valid = false;
+    digest_stale(c, WRITER_OUTSIDE);
     c->cold_exact = false;
     c->rl_global = c->rl_delta_pending = false;
     c->cold_list = false;
-    geometry(c);
-    return BPE_OK;
+    return seal_tail(c);
 }
 
 void mark_len16(bpe_ctx *c, int64_t i) { c->len16_lo = std::min(c->len16_lo, i); }
@@ -566,71 +633,207 @@ int ensure_partials(bpe_ctx *c) {
     return BPE_OK;
 }
 
-// fused: a merge pass that also refreshes the maintained cold table (MODE_FUSED; the caller
-// invalidates the pairs with a side a or b before it and syncs the dense view after it)
+// ---- the launch list of each pass form, once: enqueued on c->stream for the current geometry,
+// with its kernels' grid shapes, its spans and, where it rewrites d_ids, the plane marked stale
+constexpr unsigned REDUCE_ROWS_GRID = 4 * INCR_RLIM / 2 / RR_COLS;
+constexpr unsigned REDUCE_TABLE_GRID = HIST_WORDS / REDUCE_WORDS_PER_BLOCK;
+unsigned runs_grid(const bpe_ctx *c) { return (c->R + 255) / 256; }
+unsigned regions_grid(const bpe_ctx *c) { return (c->R + 3) / 4; }   // (one wave per region)
+
+// (The code object lays the kernel templates out in the order the unit first names them: named
+// here in the order they have always had, rearranging the host code below moves no device code.)
+[[maybe_unused]] const void *const KERNEL_ORDER[] = {
+    (void *)k_step<MERGE_XX, MODE_INCR>, (void *)k_step<MERGE_XY, MODE_INCR>,
+    (void *)k_step<MERGE_XX, MODE_FUSED>, (void *)k_step<MERGE_XY, MODE_FUSED>,
+    (void *)k_runs<MODE_INCR>, (void *)k_runs<MODE_FUSED>, (void *)k_runs<MODE_TABLE>,
+    (void *)k_step<NO_MERGE, MODE_EXACT>, (void *)k_runs<MODE_EXACT>,
+    (void *)k_step_loop<MODE_INCR>, (void *)k_step_loop<MODE_FUSED>,
+    (void *)k_apply<NO_MERGE>, (void *)k_runs<MODE_NONE>, (void *)k_apply<MERGE_XX>,
+    (void *)k_apply<MERGE_XY>};
+
+// The form of a counting pass: the table state (MODE_TABLE: every pair counted into d_hot, which
+// the reduce also scans for the best hot key) or refreshing the maintained tables, MODE_INCR (the
+// pairs touching a or b lose their count first, the pass recounts the pairs with a side in
+// {a, b, c}) or MODE_FUSED (the full hot recount with the cold refresh riding along).
+struct Pass {
+    int mode;
+    // the merge: the host path's ids (ctl == nullptr), or the LoopCtl's, which every kernel of the
+    // device loop reads itself (the ids are -1; the form is fixed for a batch)
+    int32_t a, b, c;
+    LoopCtl *ctl;
+    int64_t max_length;
+    bool delta;   // device loop, MODE_TABLE: the delta form's launches ride along (allow_delta)
+    // one rank of a sharded corpus: the exchange buffer the pass leaves this shard's table (or
+    // delta rows) and replacement count in; nullptr in a single context
+    unsigned long long *xchg;
+};
+
+// Either pass's second half: the stitch of the region boundaries and the reduce, one span.
+int enqueue_stitch_reduce(bpe_ctx *c, const Pass &p) {
+    hipStream_t s = c->stream;
+    unsigned long long *x = p.xchg, *rep = &c->d_res->replaced;
+    hipEvent_t e_red = span_begin(c);
+    if (p.mode == MODE_INCR) {
+        // the touched pairs into the maintained tables (a rank: into its delta rows)
+        k_runs<MODE_INCR><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
+                                                       c->cold, c->d_heavy, p.ctl, p.a, p.b, p.c,
+                                                       c->d_hot, x);
+        k_reduce_rows<<<REDUCE_ROWS_GRID, 256, 0, s>>>(c->d_partials, c->G, c->d_spill, c->d_hot,
+                                                       c->cold, p.a, p.b, p.c, p.ctl, x,
+                                                       x ? rep : nullptr);
+        // (the host path's best hot key; the device loop's selection takes it itself)
+        if (!p.ctl)
+            k_argmax_hot<<<HOT_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, p.max_length, c->d_res);
+    } else {
+        if (p.mode == MODE_FUSED)
+            k_runs<MODE_FUSED><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
+                                                            c->cold, c->d_heavy, p.ctl, p.a, p.b, p.c);
+        else if (!p.delta)
+            k_runs<MODE_TABLE><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
+                                                            c->cold, c->d_heavy, p.ctl);
+        else {
+            // either form's stitch in one launch; after the apply-only stream the sites' deltas
+            // into the table (after a full pass k_site_delta returns at once)
+            k_runs_loop<<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
+                                                     c->cold, c->d_heavy, p.ctl, c->d_site_n);
+            k_site_delta<<<c->R, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_sites,
+                                              c->d_site_n, c->d_hot, p.ctl);
+        }
+        // (after a delta iteration it sums nothing: the scan of the table alone.  A rank: this
+        // shard's table, replacement count and largest bin into the exchange buffer, no best key)
+        k_reduce_table<<<REDUCE_TABLE_GRID, REDUCE_THREADS, 0, s>>>(
+            c->d_partials, c->G, c->d_spill, x ? x + XCHG_HDR : c->d_hot, c->d_len16, p.max_length,
+            x ? nullptr : c->d_res, p.ctl, x, x ? rep : nullptr, x ? &c->d_res->bin_max : nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return span_end(c, e_red, 1);
+}
+
+// The host path's pass: the merge (p.a, p.b) -> p.c applied and every pair counted, or counting
+// only (!merge).  A MODE_FUSED pass has had its k_cold_invalidate (do_apply).  The Result is the
+// caller's to clear.
+int enqueue_pass(bpe_ctx *c, const Pass &p, bool merge) {
+    int rc;
+    hipStream_t s = c->stream;
+    const int mode = p.mode;
+    const int32_t a = p.a, b = p.b, cc = p.c;
+    unsigned long long *rep = &c->d_res->replaced;
+    if (merge) digest_stale(c, WRITER_LOOP);   // (a host-path merge)
+    hipEvent_t e_step = span_begin(c);
+    if (mode == MODE_INCR) k_incr_invalidate<<<COLD_GRID, 256, 0, s>>>(c->cold, c->d_hot, a, b);
+    if (mode != MODE_TABLE) {
+        const auto k = mode == MODE_INCR
+                           ? (a == b ? k_step<MERGE_XX, MODE_INCR> : k_step<MERGE_XY, MODE_INCR>)
+                           : (a == b ? k_step<MERGE_XX, MODE_FUSED> : k_step<MERGE_XY, MODE_FUSED>);
+        k<<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, a, b, cc,
+                              c->d_partials, c->d_spill, c->cold, c->d_heavy, c->d_sums, rep,
+                              mode == MODE_INCR ? c->d_hot : nullptr);
+    } else   // (built in the step unit, with the flags of the device loop's pass)
+        HIP_TRY(bpe_step::launch_step_table(!merge ? NO_MERGE : a == b ? MERGE_XX : MERGE_XY, c->G,
+                                            s, c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry,
+                                            merge ? a : -1, merge ? b : -1, merge ? cc : -1,
+                                            c->d_partials, c->d_spill, &c->cold, c->d_heavy,
+                                            c->d_sums, rep));
+    HIP_TRY(hipGetLastError());
+    if ((rc = span_end(c, e_step, 0))) return rc;
+    return enqueue_stitch_reduce(c, p);
+}
+
+// The exact pass: the cold pairs of the sketch buckets marked in d_heavy, counted into the cold
+// table (no span: exact_pass reads the table's flags back at once).
+int enqueue_exact(bpe_ctx *c) {
+    hipStream_t s = c->stream;
+    k_step<NO_MERGE, MODE_EXACT><<<c->G, WG, 0, s>>>(
+        c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, -1, -1, -1, c->d_partials, c->d_spill,
+        c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced);
+    k_runs<MODE_EXACT><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill, c->cold,
+                                                    c->d_heavy, nullptr);
+    HIP_TRY(hipGetLastError());
+    return BPE_OK;
+}
+
+// The apply-only pass: the merge m = (a, b, c) streamed in without counting a pair (its
+// replacement count added to *replaced), or with m == nullptr nothing rewritten, and the carries
+// (RegionCarry) rebuilt for the corpus it leaves.  No span.
+int enqueue_apply(bpe_ctx *c, const int32_t *m, unsigned long long *replaced) {
+    hipStream_t s = c->stream;
+    if (m) digest_stale(c, WRITER_OUTSIDE);   // (a replay: k_apply rewrites chunks without the plane)
+    const auto k = !m ? k_apply<NO_MERGE> : m[0] == m[1] ? k_apply<MERGE_XX> : k_apply<MERGE_XY>;
+    k<<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, m ? m[0] : -1,
+                          m ? m[1] : -1, m ? m[2] : -1, c->d_sums, replaced);
+    k_runs<MODE_NONE><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, nullptr, c->cold,
+                                                   nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    return BPE_OK;
+}
+
+// The maintained tables' entries touching the LoopCtl's merge, zeroed for the pass to recount.
+int enqueue_loop_invalidate(bpe_ctx *c, const Pass &p) {
+    if (p.mode == MODE_INCR)
+        k_incr_invalidate<<<COLD_GRID, 256, 0, c->stream>>>(c->cold, c->d_hot, -1, -1, c->d_ctl,
+                                                            c->d_len16, p.max_length);
+    else if (p.mode == MODE_FUSED)
+        k_cold_invalidate<<<COLD_GRID, 256, 0, c->stream>>>(c->cold, -1, -1, c->d_ctl);
+    HIP_TRY(hipGetLastError());
+    return BPE_OK;
+}
+
+// MODE_TABLE with p.delta: the launch list is fixed and holds both forms of the iteration, the
+// full pass and the delta form (k_apply_loop streams the merge in without counting and lists the
+// rewritten chunks, k_runs_loop stitches either form, k_site_delta adds the sites' deltas to the
+// table, and k_reduce_table then only scans it); the kernels of the form the decision did not
+// take return on LoopCtl::delta.
+int enqueue_loop_pass(bpe_ctx *c, const Pass &p) {
+    int rc;
+    hipStream_t s = c->stream;
+    unsigned long long *x = p.xchg, *rep = &c->d_res->replaced;
+    digest_stale(c, x ? WRITER_OUTSIDE : WRITER_LOOP);   // (fresh again: digest_end_batch)
+    hipEvent_t e_step = span_begin(c);
+    // (a rank's selection is another call, the all-reduce between: its invalidate is timed here;
+    // the single context's went with its selection, loop_enqueue)
+    if (x && (rc = enqueue_loop_invalidate(c, p))) return rc;
+    if (p.mode != MODE_TABLE) {
+        const auto k = p.mode == MODE_INCR ? k_step_loop<MODE_INCR> : k_step_loop<MODE_FUSED>;
+        k<<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, c->d_ctl,
+                              c->d_partials, c->d_spill, c->cold, c->d_sums, rep,
+                              p.mode == MODE_INCR ? c->d_hot : nullptr, x);
+    } else {
+        HIP_TRY(bpe_step::launch_step_loop_table(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
+                                                 c->d_carry, c->d_ctl, c->d_partials, c->d_spill,
+                                                 &c->cold, c->d_sums, rep));
+        if (p.delta)
+            HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
+                                                c->d_carry, c->d_ctl, c->d_sums, rep, c->d_sites,
+                                                c->d_site_n, c->d_digest));
+    }
+    HIP_TRY(hipGetLastError());
+    // (span kind 2, the incr_* statistics: the single context's maintained passes only)
+    if ((rc = span_end(c, e_step, p.mode == MODE_INCR && !x ? 2 : 0))) return rc;
+    return enqueue_stitch_reduce(c, p);
+}
+
+// The arguments of a tie pass (k_tie, k_tie_fused) over the current corpus: n_cand candidates at
+// `cand` for a host-driven pass, or with a LoopCtl the device loop's (it reads res->n_cand).
+TieArgs tie_args(const bpe_ctx *c, const int2 *cand, int n_cand, const LoopCtl *ctl) {
+    return {c->d_ids, c->n_chunks, c->cpr, c->R, n_cand, c->d_carry, cand, c->d_res, ctl};
+}
+
+// One streaming pass of the host path: (optionally apply the merge a,b -> cc, then) count every
+// pair.  fused: a merge pass that also refreshes the maintained cold table (the caller
+// invalidates the pairs with a side a or b before a MODE_FUSED one).
 int run_pass(bpe_ctx *c, bool merge, int32_t a, int32_t b, int32_t cc, int64_t *replaced,
              bool fused = false) {
     int rc;
     if (merge && c->pending)
         if ((rc = settle(c))) return rc;
-    if (merge) c->digest_valid = false;   // (a host-path merge; see compact)
     if ((rc = ensure_partials(c))) return rc;
     c->cold_list = false;   // (fused and incremental passes update the cold table)
     if ((rc = sync_len16(c, c->opt_max_length))) return rc;   // the reduce's max_length filter
-    hipStream_t s = c->stream;
     // the spill is zero here: zeroed once at create, then by every k_reduce_table
-    HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
-    hipEvent_t e_step = span_begin(c);
-    const bool incr = merge && fused && c->use_incr;
-    if (incr) {
-        k_incr_invalidate<<<COLD_GRID, 256, 0, s>>>(c->cold, c->d_hot, a, b);
-        if (a == b)
-            k_step<MERGE_XX, MODE_INCR><<<c->G, WG, 0, s>>>(
-                c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, a, b, cc, c->d_partials,
-                c->d_spill, c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced, c->d_hot);
-        else
-            k_step<MERGE_XY, MODE_INCR><<<c->G, WG, 0, s>>>(
-                c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, a, b, cc, c->d_partials,
-                c->d_spill, c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced, c->d_hot);
-    } else if (merge && fused && a == b)
-        k_step<MERGE_XX, MODE_FUSED><<<c->G, WG, 0, s>>>(
-            c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, a, b, cc, c->d_partials, c->d_spill,
-            c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced);
-    else if (merge && fused)
-        k_step<MERGE_XY, MODE_FUSED><<<c->G, WG, 0, s>>>(
-            c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, a, b, cc, c->d_partials, c->d_spill,
-            c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced);
-    else
-        HIP_TRY(bpe_step::launch_step_table(!merge ? NO_MERGE : a == b ? MERGE_XX : MERGE_XY, c->G,
-                                            s, c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry,
-                                            merge ? a : -1, merge ? b : -1, merge ? cc : -1,
-                                            c->d_partials, c->d_spill, &c->cold, c->d_heavy,
-                                            c->d_sums, &c->d_res->replaced));
-    HIP_TRY(hipGetLastError());
-    if ((rc = span_end(c, e_step, 0))) return rc;
-    hipEvent_t e_red = span_begin(c);
-    if (incr) {
-        // the touched pairs into the maintained tables, then the best hot key
-        k_runs<MODE_INCR><<<(c->R + 255) / 256, 256, 0, s>>>(
-            c->d_sums, c->R, c->d_carry, c->d_spill, c->cold, c->d_heavy, nullptr, a, b, cc,
-            c->d_hot);
-        k_reduce_rows<<<4 * INCR_RLIM / 2 / RR_COLS, 256, 0, s>>>(
-            c->d_partials, c->G, c->d_spill, c->d_hot, c->cold, a, b, cc);
-        k_argmax_hot<<<HOT_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, c->opt_max_length,
-                                                    c->d_res);
-    } else {
-        if (merge && fused)
-            k_runs<MODE_FUSED><<<(c->R + 255) / 256, 256, 0, s>>>(
-                c->d_sums, c->R, c->d_carry, c->d_spill, c->cold, c->d_heavy, nullptr, a, b, cc);
-        else
-            k_runs<MODE_TABLE><<<(c->R + 255) / 256, 256, 0, s>>>(
-                c->d_sums, c->R, c->d_carry, c->d_spill, c->cold, c->d_heavy, nullptr);
-        k_reduce_table<<<HIST_WORDS / REDUCE_WORDS_PER_BLOCK, REDUCE_THREADS, 0, s>>>(
-            c->d_partials, c->G, c->d_spill, c->d_hot, c->d_len16, c->opt_max_length, c->d_res,
-            nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    if ((rc = span_end(c, e_red, 1))) return rc;
+    HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), c->stream));
+    const int mode = !(merge && fused) ? MODE_TABLE : c->use_incr ? MODE_INCR : MODE_FUSED;
+    const Pass p = {mode, a, b, cc, nullptr, c->opt_max_length, false, nullptr};
+    if ((rc = enqueue_pass(c, p, merge))) return rc;
     c->best_ready = true;
     c->best_ml = c->opt_max_length;
     if (c->stats_on) {
@@ -661,18 +864,49 @@ int run_pass(bpe_ctx *c, bool merge, int32_t a, int32_t b, int32_t cc, int64_t *
 // d_hot holds this corpus's counts with a usable sketch (the hot bins and the sketch bound)
 bool table_ok(const bpe_ctx *c) { return c->counts_valid && c->sketch_valid; }
 
-// Host accounting of an applied merge once its replacement count R is known.
+// The host's accounting of an applied merge (a, b) -> cc that replaced R occurrences in this
+// corpus (a shard's own R, not the global W).  `what`: the statistics the site counts per merge.
+enum MergeAcct : unsigned {
+    ACCT_ITER = 1,    // a mergeUntil iteration decided on the device (iterations, live_tokens)
+    ACCT_PASS = 2,    // ... applied by a streaming pass of the device loop (step_*)
+    ACCT_INCR = 4,    // ... a MODE_INCR pass of the single context (incr_*)
+    ACCT_FUSED = 8,   // ... a pass that kept the maintained tables (fused_passes)
+    // ... on the position index (pix_merges).  `packed` is left alone: the slots are the index's,
+    ACCT_PIX = 16,    // merged in place, and pix_finish writes the corpus back packed anyway
+};
+
+void account_merge(bpe_ctx *c, int32_t a, int32_t b, int32_t cc, int64_t R, unsigned what) {
+    if (c->stats_on && (what & ACCT_ITER)) {
+        c->stats.iterations += 1;
+        c->stats.live_tokens += c->n_live;   // (the tokens the iteration selected over: before R)
+        if (what & ACCT_PIX) c->stats.pix_merges += 1;
+    }
+    c->n_live -= R;
+    c->live_slots -= R;
+    c->h_count[a] -= R;
+    c->h_count[b] -= R;
+    c->h_count[cc] += R;
+    if (R && !(what & ACCT_PIX)) c->packed = false;
+    if (c->stats_on && (what & ACCT_PASS)) {
+        c->stats.step_launches += 1;
+        c->stats.step_slots += c->n_chunks * CHUNK;
+        c->stats.step_live += c->n_live;
+        if (what & ACCT_INCR) {
+            c->stats.incr_launches += 1;
+            c->stats.incr_live += c->n_live;
+        }
+        if (what & ACCT_FUSED) c->stats.fused_passes += 1;
+    }
+}
+
+// A pending merge's accounting once its replacement count R is known.  (Its pass and its
+// iteration were counted when they were enqueued: run_pass, do_find.)
 int settle_with(bpe_ctx *c, unsigned long long Ru) {
     if (!c->pending) return BPE_OK;
     c->pending = false;
     const int64_t R = (int64_t)Ru;
-    c->last_replaced = R;
-    c->n_live -= R;
-    c->live_slots -= R;
-    c->h_count[c->pend_a] -= R;
-    c->h_count[c->pend_b] -= R;
-    c->h_count[c->pend_c] += R;
-    if (R) c->packed = false;
+    c->last_replaced = R;   // (what bpe_apply_merge reports)
+    account_merge(c, c->pend_a, c->pend_b, c->pend_c, R, 0);
     if (c->pend_expect >= 0 && R != c->pend_expect)
         return fail(BPE_ERR_STATE, "bpe native: replacement count != W");
     return BPE_OK;
@@ -698,7 +932,7 @@ int compact(bpe_ctx *c) {
         if ((rc = run_pass(c, false, 0, 0, 0, nullptr))) return rc;
     hipStream_t s = c->stream;
     k_scan_live<<<1, 1024, 0, s>>>(c->d_sums, c->R, c->d_outoff, c->d_total);
-    // (no fill of the target first: k_compact writes the live prefix and seal_packed the last
+    // (no fill of the target first: k_compact writes the live prefix and seal_tail the last
     // chunk's tail and the spare chunk, the only slots past the prefix that anything reads.  A
     // fill of the whole buffer cost ~0.7 ms per compaction, 58 of them on zipf C3)
     k_compact<<<(c->R + 3) / 4, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_outoff,
@@ -711,18 +945,10 @@ int compact(bpe_ctx *c) {
         return fail(BPE_ERR_STATE, "bpe native: compaction lost slots");
     std::swap(c->d_ids, c->d_tmp);
     // (the plane goes stale, but the merge loop goes on as before: whether the next batch
-    // rebuilds it is up to the last batch's delta share, as after a host-path merge)
-    const bool dchg = c->digest_changed;
-    const bool counts = c->counts_valid, cold_exact = c->cold_exact, sketch = c->sketch_valid;
-    const bool glob = c->rl_global, pend = c->rl_delta_pending, list = c->cold_list;
-    if ((rc = seal_packed(c))) return rc;
-    c->digest_changed = dchg;
-    c->counts_valid = counts;
-    c->sketch_valid = sketch;
-    c->cold_exact = cold_exact;
-    c->rl_global = glob;
-    c->rl_delta_pending = pend;
-    c->cold_list = list;
+    // rebuilds it is up to the last batch's delta share, as after a host-path merge.  The tokens
+    // are the same: every count and every table of the old layout still holds)
+    digest_stale(c, WRITER_LOOP);
+    if ((rc = seal_tail(c))) return rc;
     if (c->stats_on) c->stats.compactions += 1;
     return BPE_OK;
 }
@@ -764,13 +990,7 @@ int exact_pass(bpe_ctx *c) {
     uint32_t flags[2] = {0, 0};
     for (int attempt = 0;; ++attempt) {
         if ((rc = cold_clear(c))) return rc;
-        k_step<NO_MERGE, MODE_EXACT><<<c->G, WG, 0, s>>>(
-            c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, -1, -1, -1, c->d_partials,
-            c->d_spill, c->cold, c->d_heavy, c->d_sums, &c->d_res->replaced);
-        k_runs<MODE_EXACT><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                              c->d_spill, c->cold, c->d_heavy,
-                                                              nullptr);
-        HIP_TRY(hipGetLastError());
+        if ((rc = enqueue_exact(c))) return rc;
         HIP_TRY(hipMemcpyAsync(flags, c->d_cold_flags, sizeof flags, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (!flags[1]) break;
@@ -907,21 +1127,11 @@ int tie_positions(bpe_ctx *c, const int2 *cand, unsigned n_cand, unsigned long l
     hipStream_t s = c->stream;
     for (unsigned j0 = 0; j0 < n_cand; j0 += MAX_CAND) {
         const unsigned nb = std::min<unsigned>(MAX_CAND, n_cand - j0);
-        TieArgs A;
-        memset(&A, 0, sizeof A);
-        A.ids = c->d_ids;
-        A.n_chunks = c->n_chunks;
-        A.cpr = c->cpr;
-        A.R = c->R;
-        A.n_cand = (int)nb;
-        A.carry = c->d_carry;
-        A.cand = cand + j0;
-        A.res = c->d_res;
-        A.ctl = nullptr;
         HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
         c->best_ready = false;   // the Result is reused
         hipEvent_t e_tie = span_begin(c);
-        if (c->n_live > 0) k_tie<<<(c->R + 3) / 4, 256, 0, s>>>(A);
+        if (c->n_live > 0)
+            k_tie<<<regions_grid(c), 256, 0, s>>>(tie_args(c, cand + j0, (int)nb, nullptr));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(c->h_res, c->d_res, sizeof(Result), hipMemcpyDeviceToHost, s));
         if ((rc = span_end(c, e_tie, 2))) return rc;
@@ -1034,50 +1244,55 @@ int do_apply(bpe_ctx *c, int32_t a, int32_t b, int32_t cc, int64_t *replaced) {
     return BPE_OK;
 }
 
-// Up to n mergeUntil iterations with the decisions kept on the device (core.ts:367-384): per
-// iteration k_select_multi, k_decide, [k_tie, k_decide] and the pass (k_step_loop, k_runs,
-// k_reduce_table), every kernel reading the merge from the LoopCtl, and one host sync at the end.
-// In the table state an iteration may take the delta form instead (LoopCtl::delta, decided on the
-// device): k_apply_loop streams the merge in without counting and lists the rewritten chunks,
-// k_site_delta adds the sites' deltas to the table, and k_reduce_table only scans it.  The launch
-// list is fixed; the kernels of the form not taken return on the flag.
-// With a maintained cold table (skewed corpora) the selection is k_argmax_cold + k_collect over
-// that table and the pass is the fused one (k_cold_invalidate, k_step_loop<MODE_FUSED>,
-// k_runs<MODE_FUSED>), as in the host path.
-// The merges go to out_abw[3 * i ...]; *status is the LoopStatus the batch ended with (LOOP_RUN:
-// all n done; LOOP_HOST: the next iteration needs the host path).  The host tables are brought up
-// to date from the log.
-int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, int64_t *out_abw,
-               int64_t *n_done, int *status) {
+// ---- the device loop: up to n mergeUntil iterations decided on the device (core.ts:367-384) ----
+// Per iteration the selection (k_select_multi; with a maintained cold table, skewed corpora,
+// k_select_maint), the decision with the R3 tie pass when tied (k_tie_fused) and the pass
+// (enqueue_loop_pass), every kernel reading the merge from the LoopCtl; one host sync per batch.
+
+// Before a batch of up to n merges decided on the device: room for their ids in the device length
+// table, which must be exact below the first of them (k_decide extends it from there).
+int len16_for_batch(bpe_ctx *c, int64_t n) {
     int rc;
-    *n_done = 0;
-    *status = LOOP_DONE;
+    if ((rc = ensure_len16_cap(c, (int64_t)c->h_len16.size() + n))) return rc;
+    return sync_len16(c, 1);
+}
+
+// A batch's control block in its pinned mirror: the fields every form of the device loop sets
+// (min_weight: after the core.ts:256 default).  The caller adds its own and uploads it.
+LoopCtl *ctl_begin(bpe_ctx *c, int64_t min_weight, bool maintained) {
+    LoopCtl *h = c->h_ctl;
+    memset(h, 0, sizeof *h);
+    h->status = LOOP_RUN;
+    h->next_id = (int32_t)c->h_len16.size();
+    h->w = -1;
+    h->min_weight = min_weight;
+    h->max_id = BPE_MAX_VOCAB;
+    h->maintained = maintained ? 1 : 0;
+    h->cold_cap = c->cold_cap;
+    return h;
+}
+
+// A batch's first part: the tables and carries a batch starts from, its buffers, the digest plane,
+// the Result and the control block.  *p: the form of the batch's passes.
+int loop_prepare(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, Pass *p) {
+    int rc;
     LEAVE_GLOBAL(c);
     if ((rc = settle(c))) return rc;
     c->cold_list = false;
     c->opt_max_length = max_length;
     const bool maint = c->cold_exact && c->counts_valid && c->carry_valid &&
                        !getenv("BPE_DEBUG_NO_FUSED");
-    // (A/B and checking knob: every maintained selection a full scan of the cold table)
-    static const bool sel_full = getenv("BPE_SEL_FULL") != nullptr;
     if (!maint) c->cold_exact = false;
     if (!maint && (!table_ok(c) || !c->carry_valid))
         if ((rc = run_pass(c, false, 0, 0, 0, nullptr))) return rc;
-    const int64_t base = (int64_t)c->h_len16.size();
-    if ((rc = ensure_len16_cap(c, base + n))) return rc;
-    // the device table must be exact below `base`: k_decide extends it
-    if (c->len16_lo < base) {
-        HIP_TRY(hipMemcpyAsync(c->d_len16 + c->len16_lo, c->h_len16.data() + c->len16_lo,
-                               (base - c->len16_lo) * sizeof(int32_t), hipMemcpyHostToDevice,
-                               c->stream));
-        c->len16_lo = base;
-    }
+    if ((rc = len16_for_batch(c, n))) return rc;
     geometry(c);
     // The table state may take the delta form (LoopCtl::delta; BPE_DELTA=0 turns it off, for A/B
     // and checking; read per batch): the site list holds a segment of cpr entries per region.
     const char *dknob = getenv("BPE_DELTA");
-    const bool delta_ok = !maint && !(dknob && atoi(dknob) == 0);
-    if (delta_ok && c->sites_cap < (int64_t)c->R * c->cpr) {
+    *p = {!maint ? MODE_TABLE : c->use_incr ? MODE_INCR : MODE_FUSED, -1, -1, -1, c->d_ctl, max_length,
+          !maint && !(dknob && atoi(dknob) == 0), nullptr};
+    if (p->delta && c->sites_cap < (int64_t)c->R * c->cpr) {
         dfree(c->d_sites);
         c->d_sites = nullptr;
         c->sites_cap = 0;
@@ -1085,43 +1300,9 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         if ((rc = dev_alloc(&c->d_sites, (size_t)cap))) return rc;
         c->sites_cap = cap;
     }
+    bool digest = false;   // the delta form's stream reads the digest plane
+    if (p->delta && (rc = digest_begin_batch(c, &digest))) return rc;
     hipStream_t s = c->stream;
-    // The delta form's stream reads the digest plane when it is fresh (BPE_DIGEST=0 keeps the int32
-    // stream everywhere, for A/B and checking; read per batch).  A stale plane is rebuilt here when
-    // the corpus was replaced or written from outside the merge loop since the last batch (ingest,
-    // a replay, the position index: the first batch after such a change always builds), and
-    // otherwise (the plane went stale by a full-form merge inside a batch, by a host-path merge
-    // or by a compaction) only if the last batch took the delta form in at least
-    // DIGEST_REBUILD_MIN and at least half of its iterations: a build costs about 1.3 int32
-    // streams, and a batch of heavy merges would clear the plane again at once.  If the plane
-    // cannot be allocated the batch runs on the int32 stream.
-    const char *gknob = getenv("BPE_DIGEST");
-    bool digest = delta_ok && !(gknob && atoi(gknob) == 0) && c->n_chunks > 0;
-    if (digest && c->digest_cap < c->n_chunks * CHUNK) {
-        dfree(c->d_digest);
-        c->d_digest = nullptr;
-        c->digest_cap = 0;
-        c->digest_valid = false;
-        const int64_t cap = (c->cap_slots > 0 ? c->cap_slots : c->n_chunks * CHUNK);
-        void *p = nullptr;
-        if (hipMalloc(&p, (size_t)cap) == hipSuccess) {
-            c->d_digest = static_cast<uint32_t *>(p);
-            c->digest_cap = cap;
-        } else {
-            (void)hipGetLastError();
-            digest = false;
-        }
-    }
-    if (digest && !c->digest_valid) {
-        if (c->digest_changed ||
-            (c->last_delta >= DIGEST_REBUILD_MIN && 2 * c->last_delta >= c->last_done)) {
-            HIP_TRY(bpe_step::launch_digest_build(s, c->d_ids, c->n_chunks, c->d_digest));
-            c->digest_valid = true;
-            if (c->stats_on) c->stats.digest_builds += 1;
-        }
-        c->digest_changed = false;
-    }
-    digest = digest && c->digest_valid;
     if (maint) {
         // (k_select_maint takes the best over the hot bins itself)
         HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
@@ -1132,128 +1313,88 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
         k_argmax_hot<<<HOT_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, max_length, c->d_res);
     }
-    LoopCtl *h = c->h_ctl;
-    memset(h, 0, sizeof *h);
-    h->status = LOOP_RUN;
-    h->next_id = (int32_t)base;
-    h->w = -1;
-    h->min_weight = min_weight;
-    h->max_id = BPE_MAX_VOCAB;
-    h->maintained = maint ? 1 : 0;
-    h->cold_cap = c->cold_cap;
-    h->allow_delta = delta_ok ? 1 : 0;
+    LoopCtl *h = ctl_begin(c, min_weight, maint);
+    h->allow_delta = p->delta ? 1 : 0;
     h->digest_ok = digest ? 1 : 0;
     HIP_TRY(hipMemcpyAsync(c->d_ctl, h, sizeof *h, hipMemcpyHostToDevice, s));
-    TieArgs A;
-    memset(&A, 0, sizeof A);
-    A.ids = c->d_ids;
-    A.n_chunks = c->n_chunks;
-    A.cpr = c->cpr;
-    A.R = c->R;
-    A.carry = c->d_carry;
-    A.cand = c->d_cand;
-    A.res = c->d_res;
-    A.ctl = c->d_ctl;
+    return BPE_OK;
+}
+
+// A batch's second part: n iterations enqueued, nothing waited for.
+int loop_enqueue(bpe_ctx *c, const Pass &p, int64_t n) {
+    int rc;
+    hipStream_t s = c->stream;
+    // (A/B and checking knob: every maintained selection a full scan of the cold table)
+    static const bool sel_full = getenv("BPE_SEL_FULL") != nullptr;
+    const TieArgs tie = tie_args(c, c->d_cand, 0, c->d_ctl);
     for (int64_t i = 0; i < n; ++i) {
         // the spans of every SPAN_EVERY-th iteration only: each event record costs the stream
         // a few microseconds, about 3% of an iteration with all six
         c->span_mute = (c->span_tick++ % SPAN_EVERY) != 0;
         hipEvent_t e_sel = span_begin(c);
-        if (maint) {
+        if (p.mode != MODE_TABLE) {
             // best key over the hot bins and the cold table, its pairs, the table's flags
             // a full scan of the cold table on the first selection of the batch and every
             // SEL_FULL_EVERY-th (its dead claims), else the block maxima on a grid of one
             // workgroup per 256 hot bins
-            const bool full = !c->use_incr || sel_full || i % SEL_FULL_EVERY == 0;
+            const bool full = p.mode == MODE_FUSED || sel_full || i % SEL_FULL_EVERY == 0;
             k_select_maint<<<full ? COLD_GRID : HOT_BINS / 256, 256, 0, s>>>(
-                c->d_hot, c->cold, c->d_len16, max_length, c->d_res, c->d_cand, c->d_brec,
+                c->d_hot, c->cold, c->d_len16, p.max_length, c->d_res, c->d_cand, c->d_brec,
                 c->d_ticket, c->d_ctl, full ? 1 : 0);
         } else {
-            k_select_multi<<<TABLE_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, max_length,
+            k_select_multi<<<TABLE_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, p.max_length,
                                                             c->d_res, c->d_cand, c->d_heavy,
                                                             c->d_ctl);
         }
         // the decision, the R3 tie pass when tied, and its commit: one launch
-        k_tie_fused<<<(c->R + 3) / 4, 256, 0, s>>>(A, c->d_len16, c->d_log, c->d_ticket);
-        // (the maintained tables' entries touching the merge, zeroed for the pass to recount:
-        // timed with the selection, so that the pass's span is the pass kernel alone)
-        if (maint && c->use_incr)
-            k_incr_invalidate<<<COLD_GRID, 256, 0, s>>>(c->cold, c->d_hot, -1, -1, c->d_ctl,
-                                                        c->d_len16, max_length);
-        else if (maint)
-            k_cold_invalidate<<<COLD_GRID, 256, 0, s>>>(c->cold, -1, -1, c->d_ctl);
+        k_tie_fused<<<regions_grid(c), 256, 0, s>>>(tie, c->d_len16, c->d_log, c->d_ticket);
         HIP_TRY(hipGetLastError());
+        // (timed with the selection, so that the pass's span is the pass kernel alone)
+        if ((rc = enqueue_loop_invalidate(c, p))) return rc;
         if ((rc = span_end(c, e_sel, 1))) return rc;
-        hipEvent_t e_step = span_begin(c);
-        if (maint && c->use_incr) {
-            k_step_loop<MODE_INCR><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                       c->d_carry, c->d_ctl, c->d_partials,
-                                                       c->d_spill, c->cold, c->d_sums,
-                                                       &c->d_res->replaced, c->d_hot);
-        } else if (maint) {
-            k_step_loop<MODE_FUSED><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                        c->d_carry, c->d_ctl, c->d_partials,
-                                                        c->d_spill, c->cold, c->d_sums,
-                                                        &c->d_res->replaced);
-        } else {
-            // (the full pass, or the delta form's apply-only stream: the one whose form the
-            // decision did not take returns at once)
-            HIP_TRY(bpe_step::launch_step_loop_table(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                     c->d_carry, c->d_ctl, c->d_partials,
-                                                     c->d_spill, &c->cold, c->d_sums,
-                                                     &c->d_res->replaced));
-            if (delta_ok)
-                HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                    c->d_carry, c->d_ctl, c->d_sums,
-                                                    &c->d_res->replaced, c->d_sites, c->d_site_n,
-                                                    c->d_digest));
-        }
-        HIP_TRY(hipGetLastError());
-        if ((rc = span_end(c, e_step, maint && c->use_incr ? 2 : 0))) return rc;
-        hipEvent_t e_red = span_begin(c);
-        if (maint && c->use_incr) {
-            k_runs<MODE_INCR><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                                 c->d_spill, c->cold, c->d_heavy,
-                                                                 c->d_ctl, -1, -1, -1, c->d_hot);
-            k_reduce_rows<<<4 * INCR_RLIM / 2 / RR_COLS, 256, 0, s>>>(
-                c->d_partials, c->G, c->d_spill, c->d_hot, c->cold, -1, -1, -1, c->d_ctl);
-        } else {
-            if (maint)
-                k_runs<MODE_FUSED><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                                      c->d_spill, c->cold,
-                                                                      c->d_heavy, c->d_ctl);
-            else if (!delta_ok)
-                k_runs<MODE_TABLE><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                                      c->d_spill, c->cold,
-                                                                      c->d_heavy, c->d_ctl);
-            if (delta_ok) {
-                // either form's stitch in one launch; after the apply-only stream the sites'
-                // deltas into the table (after a full pass k_site_delta returns at once)
-                k_runs_loop<<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                               c->d_spill, c->cold, c->d_heavy,
-                                                               c->d_ctl, c->d_site_n);
-                k_site_delta<<<c->R, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_sites,
-                                                  c->d_site_n, c->d_hot, c->d_ctl);
-            }
-            // (after a delta iteration it sums nothing: the scan of the table alone)
-            k_reduce_table<<<HIST_WORDS / REDUCE_WORDS_PER_BLOCK, REDUCE_THREADS, 0, s>>>(
-                c->d_partials, c->G, c->d_spill, c->d_hot, c->d_len16, max_length, c->d_res,
-                c->d_ctl);
-        }
-        HIP_TRY(hipGetLastError());
-        if ((rc = span_end(c, e_red, 1))) return rc;
+        if ((rc = enqueue_loop_pass(c, p))) return rc;
     }
     c->span_mute = false;
-    HIP_TRY(hipMemcpyAsync(h, c->d_ctl, sizeof *h, hipMemcpyDeviceToHost, s));
+    return BPE_OK;
+}
+
+// The one host sync of a batch (single context or rank): its control block, the Result and the
+// log of n merges into their pinned mirrors.
+int loop_read_back(bpe_ctx *c, int64_t n) {
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(c->h_ctl, c->d_ctl, sizeof(LoopCtl), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(c->h_res, c->d_res, sizeof(Result), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(c->h_log, c->d_log, LOG_WORDS * n * sizeof(long long),
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    // (a batch without the plane's stream may have rewritten chunks: whatever plane there is is
-    // stale; so is one a full-form merge of this batch passed by)
-    if (!h->digest_ok) c->digest_valid = false;
-    c->last_delta = h->n_delta;
-    c->last_done = h->n_done;
+    return BPE_OK;
+}
+
+// A finished batch's counters (a rank's batch takes no delta form: those counters are zero).
+void loop_stats(bpe_ctx *c, const LoopCtl *h) {
+    if (!c->stats_on) return;
+    c->stats.tie_passes += h->n_tie;
+    c->stats.unscreened_passes += h->n_unscreened;
+    c->stats.tie_tail += h->n_tail;
+    c->stats.tie_lone += h->n_lone;
+    c->stats.loop_host += h->n_host;
+    c->stats.delta_passes += h->n_delta;
+    c->stats.delta_chunks += (int64_t)h->delta_chunks;
+    c->stats.digest_passes += h->n_digest;
+    c->stats.digest_hits += (int64_t)h->digest_hits;
+}
+
+// A batch's third part: the one host sync, then the host tables brought up to date from the log.
+// The merges go to out_abw[3 * i ...]; *status is the LoopStatus the batch ended with (LOOP_RUN:
+// all n done; LOOP_HOST: the next iteration needs the host path).
+int loop_finish(bpe_ctx *c, const Pass &p, int64_t n, int64_t *out_abw, int64_t *n_done,
+                int *status) {
+    int rc;
+    LoopCtl *h = c->h_ctl;
+    const bool maint = p.mode != MODE_TABLE;
+    const int64_t base = (int64_t)c->h_len16.size();   // (the batch's first new id)
+    if ((rc = loop_read_back(c, n))) return rc;
+    digest_end_batch(c, h);
     const int64_t nd = h->n_done;
     if (h->status == LOOP_ERROR)
         return fail(BPE_ERR_STATE,
@@ -1266,30 +1407,15 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
         return fail(BPE_ERR_STATE, "bpe native: replacement count != W");
     c->h_len16.resize(base + nd, 1);
     c->h_count.resize(base + nd, 0);
+    const unsigned acct = ACCT_ITER | ACCT_PASS | (p.mode == MODE_INCR ? ACCT_INCR : 0) |
+                          (maint ? ACCT_FUSED : 0);
     for (int64_t i = 0; i < nd; ++i) {
         const int32_t a = (int32_t)c->h_log[LOG_WORDS * i], b = (int32_t)c->h_log[LOG_WORDS * i + 1];
         const int64_t W = c->h_log[LOG_WORDS * i + 2];
         const int64_t cc = base + i;
         c->h_len16[cc] = c->h_len16[a] + c->h_len16[b];                // core.ts:318
-        if (c->stats_on) {
-            c->stats.iterations += 1;
-            c->stats.live_tokens += c->n_live;
-        }
-        c->n_live -= W;
-        c->live_slots -= W;
-        c->h_count[a] -= W;
-        c->h_count[b] -= W;
-        c->h_count[cc] += W;
-        if (W) c->packed = false;
-        if (c->stats_on) {
-            c->stats.step_launches += 1;
-            c->stats.step_slots += c->n_chunks * CHUNK;
-            c->stats.step_live += c->n_live;
-            if (maint && c->use_incr) {
-                c->stats.incr_launches += 1;
-                c->stats.incr_live += c->n_live;
-            }
-        }
+        account_merge(c, a, b, (int32_t)cc, W, acct);   // (one corpus: W is its replacement count)
+        c->last_replaced = W;
         out_abw[3 * i] = a;
         out_abw[3 * i + 1] = b;
         out_abw[3 * i + 2] = W;
@@ -1304,29 +1430,28 @@ int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, in
             c->stats.sel_blocks = nr;   // (cumulative since the context was made)
         }
         if (nd) c->sketch_valid = false;                     // (fused passes)
-        if (c->stats_on) c->stats.fused_passes += nd;
     }
-    if (c->stats_on) {
-        c->stats.tie_passes += h->n_tie;
-        c->stats.unscreened_passes += h->n_unscreened;
-        c->stats.tie_tail += h->n_tail;
-        c->stats.tie_lone += h->n_lone;
-        c->stats.loop_host += h->n_host;
-        c->stats.delta_passes += h->n_delta;
-        c->stats.delta_chunks += (int64_t)h->delta_chunks;
-        c->stats.digest_passes += h->n_digest;
-        c->stats.digest_hits += (int64_t)h->digest_hits;
-    }
-    c->last_replaced = nd ? c->h_log[LOG_WORDS * (nd - 1) + 2] : c->last_replaced;
+    loop_stats(c, h);
     // every early-ended batch of the table state leaves the last reduce's best key in the Result
     // (the maintained state selects with k_select_maint: nothing is left ready)
     c->best_ready = !maint;
-    c->best_ml = max_length;
+    c->best_ml = p.max_length;
     c->counts_valid = c->carry_valid = true;
     if (!maint) c->sketch_valid = true;
     *n_done = nd;
     *status = h->status;
     return BPE_OK;
+}
+
+int loop_batch(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, int64_t *out_abw,
+               int64_t *n_done, int *status) {
+    int rc;
+    *n_done = 0;
+    *status = LOOP_DONE;
+    Pass p;
+    if ((rc = loop_prepare(c, max_length, min_weight, n, &p))) return rc;
+    if ((rc = loop_enqueue(c, p, n))) return rc;
+    return loop_finish(c, p, n, out_abw, n_done, status);
 }
 
 // ---- the device loop on one rank of a sharded corpus ------------------------
@@ -1389,26 +1514,12 @@ int rank_loop_begin(bpe_ctx *c, int64_t max_length, int64_t min_weight, unsigned
     }
     if ((rc = ensure_partials(c))) return rc;
     const int64_t base = (int64_t)c->h_len16.size();
-    if ((rc = ensure_len16_cap(c, base + LOOP_BATCH))) return rc;
-    if (c->len16_lo < base) {
-        HIP_TRY(hipMemcpyAsync(c->d_len16 + c->len16_lo, c->h_len16.data() + c->len16_lo,
-                               (base - c->len16_lo) * sizeof(int32_t), hipMemcpyHostToDevice,
-                               c->stream));
-        c->len16_lo = base;
-    }
+    if ((rc = len16_for_batch(c, LOOP_BATCH))) return rc;
     hipStream_t s = c->stream;
     HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
-    LoopCtl *h = c->h_ctl;
-    memset(h, 0, sizeof *h);
-    h->status = LOOP_RUN;
-    h->next_id = (int32_t)base;
-    h->w = -1;
-    h->min_weight = min_weight == 0 ? 2 : min_weight;                   // core.ts:256
+    LoopCtl *h = ctl_begin(c, min_weight == 0 ? 2 : min_weight, glob);   // core.ts:256
     h->sharded = 1;
-    h->max_id = BPE_MAX_VOCAB;
     h->last_rank = rank == world - 1;
-    h->maintained = glob ? 1 : 0;
-    h->cold_cap = c->cold_cap;
     int64_t nw;
     if (glob) {
         // the delta rows of every token id a merge of this batch can see (<= base + LOOP_BATCH)
@@ -1478,17 +1589,7 @@ int rank_loop_select(bpe_ctx *c) {
     }
     k_decide<<<1, 64, 0, s>>>(c->d_ctl, c->d_res, c->d_cand, c->d_len16, c->d_log, 0, nullptr,
                               c->rl_table);
-    TieArgs A;
-    memset(&A, 0, sizeof A);
-    A.ids = c->d_ids;
-    A.n_chunks = c->n_chunks;
-    A.cpr = c->cpr;
-    A.R = c->R;
-    A.carry = c->d_carry;
-    A.cand = c->d_cand;
-    A.res = c->d_res;
-    A.ctl = c->d_ctl;
-    k_tie<<<(c->R + 3) / 4, 256, 0, s>>>(A);
+    k_tie<<<regions_grid(c), 256, 0, s>>>(tie_args(c, c->d_cand, 0, c->d_ctl));
     k_tie_export<<<1, 64, 0, s>>>(c->d_ctl, c->d_res, c->rl_tie, c->rl_rank);
     HIP_TRY(hipGetLastError());
     return span_end(c, e_sel, 1);
@@ -1509,43 +1610,13 @@ int rank_loop_decide(bpe_ctx *c) {
 int rank_loop_count(bpe_ctx *c) {
     if (!c->rl_open) return fail(BPE_ERR_STATE, "bpe native: rank loop not begun");
     if (c->rl_pix) return pix_rank_count(c);
-    digest_stale(c);   // (the rank loop's passes keep no plane)
-    hipStream_t s = c->stream;
-    unsigned long long *x = c->rl_table;
-    hipEvent_t e_step = span_begin(c);
-    if (c->rl_global) {
-        k_incr_invalidate<<<COLD_GRID, 256, 0, s>>>(c->cold, c->d_hot, -1, -1, c->d_ctl, c->d_len16,
-                                                    c->rl_max_length);
-        k_step_loop<MODE_INCR><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry,
-                                                   c->d_ctl, c->d_partials, c->d_spill, c->cold,
-                                                   c->d_sums, &c->d_res->replaced, c->d_hot, x);
-    } else {
-        HIP_TRY(bpe_step::launch_step_loop_table(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                 c->d_carry, c->d_ctl, c->d_partials, c->d_spill,
-                                                 &c->cold, c->d_sums, &c->d_res->replaced));
-    }
-    HIP_TRY(hipGetLastError());
-    int rc;
-    if ((rc = span_end(c, e_step, 0))) return rc;
-    hipEvent_t e_red = span_begin(c);
-    if (c->rl_global) {
-        k_runs<MODE_INCR><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
-                                                             c->cold, c->d_heavy, c->d_ctl, -1, -1,
-                                                             -1, c->d_hot, x);
-        k_reduce_rows<<<4 * INCR_RLIM / 2 / RR_COLS, 256, 0, s>>>(
-            c->d_partials, c->G, c->d_spill, c->d_hot, c->cold, -1, -1, -1, c->d_ctl, x,
-            &c->d_res->replaced);
-    } else {
-        k_runs<MODE_TABLE><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                              c->d_spill, c->cold, c->d_heavy,
-                                                              c->d_ctl);
-        k_reduce_table<<<HIST_WORDS / REDUCE_WORDS_PER_BLOCK, REDUCE_THREADS, 0, s>>>(
-            c->d_partials, c->G, c->d_spill, x + XCHG_HDR, c->d_len16, c->rl_max_length, nullptr,
-            c->d_ctl, x, &c->d_res->replaced, &c->d_res->bin_max);
-    }
-    HIP_TRY(hipGetLastError());
+    // (the global state's pass is MODE_INCR; the table state's the full pass, never the delta form)
+    const Pass p = {c->rl_global ? MODE_INCR : MODE_TABLE, -1, -1, -1, c->d_ctl, c->rl_max_length,
+                    false, c->rl_table};
+    const int rc = enqueue_loop_pass(c, p);
+    if (rc) return rc;
     c->rl_enqueued += 1;
-    return span_end(c, e_red, 1);
+    return BPE_OK;
 }
 
 // Syncs, reads the batch's merges back (out_abwr: (a, b, W, this shard's replacement count)
@@ -1558,11 +1629,8 @@ int rank_loop_end(bpe_ctx *c, int64_t *out, int64_t cap, int64_t *n_done, int *s
     c->rl_open = false;
     hipStream_t s = c->stream;
     LoopCtl *h = c->h_ctl;
-    HIP_TRY(hipMemcpyAsync(h, c->d_ctl, sizeof *h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(c->h_res, c->d_res, sizeof(Result), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(c->h_log, c->d_log, LOG_WORDS * LOOP_BATCH * sizeof(long long),
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    const int rc = loop_read_back(c, LOOP_BATCH);
+    if (rc) return rc;
     const bool glob = c->rl_global;
     if (h->status == LOOP_ERROR) {
         const bool was_global = glob;
@@ -1602,22 +1670,8 @@ int rank_loop_end(bpe_ctx *c, int64_t *out, int64_t cap, int64_t *n_done, int *s
         const int64_t R = m[3] >= 0 ? m[3] : (int64_t)c->h_res->replaced;
         const int64_t cc = base + i;
         c->h_len16[cc] = c->h_len16[a] + c->h_len16[b];                // core.ts:318
-        if (c->stats_on) {
-            c->stats.iterations += 1;
-            c->stats.live_tokens += c->n_live;
-        }
-        c->n_live -= R;
-        c->live_slots -= R;
-        c->h_count[a] -= R;
-        c->h_count[b] -= R;
-        c->h_count[cc] += R;
-        if (R) c->packed = false;
-        if (c->stats_on) {
-            c->stats.step_launches += 1;
-            c->stats.step_slots += c->n_chunks * CHUNK;
-            c->stats.step_live += c->n_live;
-            if (glob) c->stats.fused_passes += 1;
-        }
+        // (the global state's passes count as fused ones, not in the incr_* statistics)
+        account_merge(c, a, b, (int32_t)cc, R, ACCT_ITER | ACCT_PASS | (glob ? ACCT_FUSED : 0));
         if (i < cap) {
             out[4 * i] = a;
             out[4 * i + 1] = b;
@@ -1626,13 +1680,7 @@ int rank_loop_end(bpe_ctx *c, int64_t *out, int64_t cap, int64_t *n_done, int *s
         }
     }
     c->len16_lo = base + nd;
-    if (c->stats_on) {
-        c->stats.tie_passes += h->n_tie;
-        c->stats.unscreened_passes += h->n_unscreened;
-        c->stats.tie_tail += h->n_tail;
-        c->stats.tie_lone += h->n_lone;
-        c->stats.loop_host += h->n_host;
-    }
+    loop_stats(c, h);
     c->carry_valid = true;   // (the last pass's carries)
     c->best_ready = false;
     const bool all = h->status == LOOP_RUN && nd == c->rl_enqueued;
@@ -1733,12 +1781,8 @@ int set_global_counts(bpe_ctx *c, const unsigned long long *table, const uint32_
 // Carries (RegionCarry) for the current corpus and geometry without counting pairs.
 int carry_pass(bpe_ctx *c) {
     geometry(c);
-    hipStream_t s = c->stream;
-    k_apply<NO_MERGE><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_carry, -1, -1,
-                                          -1, c->d_sums, nullptr);
-    k_runs<MODE_NONE><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry, nullptr,
-                                                         c->cold, nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
+    const int rc = enqueue_apply(c, nullptr, nullptr);
+    if (rc) return rc;
     c->carry_valid = true;
     return BPE_OK;
 }
@@ -1777,35 +1821,17 @@ int replay(bpe_ctx *c, const int32_t *abc, int64_t n, int64_t *replaced, bool co
             if ((rc = register_merge(c, m[0], m[1], m[2]))) return rc;
         }
         geometry(c);
-        digest_stale(c);   // (k_apply rewrites chunks without the plane)
         hipStream_t s = c->stream;
         HIP_TRY(hipMemsetAsync(c->d_repl, 0, nb * sizeof(unsigned long long), s));
-        for (int64_t j = 0; j < nb; ++j) {
-            const int32_t *m = abc + 3 * (i0 + j);
-            if (m[0] == m[1])
-                k_apply<MERGE_XX><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                      c->d_carry, m[0], m[1], m[2], c->d_sums,
-                                                      c->d_repl + j);
-            else
-                k_apply<MERGE_XY><<<c->G, WG, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R,
-                                                      c->d_carry, m[0], m[1], m[2], c->d_sums,
-                                                      c->d_repl + j);
-            k_runs<MODE_NONE><<<(c->R + 255) / 256, 256, 0, s>>>(c->d_sums, c->R, c->d_carry,
-                                                                 nullptr, c->cold, nullptr, nullptr);
-        }
-        HIP_TRY(hipGetLastError());
+        for (int64_t j = 0; j < nb; ++j)
+            if ((rc = enqueue_apply(c, abc + 3 * (i0 + j), c->d_repl + j))) return rc;
         HIP_TRY(hipMemcpyAsync(c->h_repl, c->d_repl, nb * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         for (int64_t j = 0; j < nb; ++j) {
             const int32_t *m = abc + 3 * (i0 + j);
             const int64_t R = (int64_t)c->h_repl[j];
-            c->n_live -= R;
-            c->live_slots -= R;
-            c->h_count[m[0]] -= R;
-            c->h_count[m[1]] -= R;
-            c->h_count[m[2]] += R;
-            if (R) c->packed = false;
+            account_merge(c, m[0], m[1], m[2], R, 0);   // (a replay is no iteration and no pass)
             if (replaced) replaced[i0 + j] = R;
         }
         c->counts_valid = false;
@@ -2009,7 +2035,7 @@ int pix_build_timed(bpe_ctx *c, int64_t max_length) {
     const uint32_t N = (uint32_t)n;
     PixCorpus &C = P->C;
     C.tok = c->d_ids;
-    digest_stale(c);   // (the index merges in place in d_ids)
+    digest_stale(c, WRITER_OUTSIDE);   // (the index merges in place in d_ids)
     C.n = N;
     if ((rc = pix_alloc(P, &C.nxt, N)) || (rc = pix_alloc(P, &C.prv, N))) return rc;
     const uint64_t pool_cap = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)N + std::max<uint64_t>(N / 2, 1u << 22));
@@ -2155,12 +2181,19 @@ int pix_finish(bpe_ctx *c) {
             return fail(BPE_ERR_STATE, "bpe native: position index: live slots lost");
     }
     std::swap(c->d_ids, c->d_tmp);
-    digest_stale(c);
     pix_free(c);
-    return seal_packed(c);
+    return seal_packed(c);   // (a corpus written from outside the merge loop)
 }
 
 int pix_reserve(bpe_ctx *c);
+
+// The n-th merge of a mergeUntil call into the caller's list, while it has room.
+static void put_merge(int64_t *out_abw, int64_t cap, int64_t n, int64_t a, int64_t b, int64_t w) {
+    if (n >= cap) return;
+    out_abw[3 * n] = a;
+    out_abw[3 * n + 1] = b;
+    out_abw[3 * n + 2] = w;
+}
 
 // mergeUntil on the index: batches of PIX_BATCH merges, one host round trip each.  An iteration
 // the index cannot take (PIX_HOST) runs on the streaming path, and the index is rebuilt after it.
@@ -2200,11 +2233,7 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
         if ((rc = do_apply(c, a, b, cc, nullptr))) return rc;
         if (c->pending) c->pend_expect = w;
         if ((rc = settle(c))) return rc;
-        if (n < cap) {
-            out_abw[3 * n] = a;
-            out_abw[3 * n + 1] = b;
-            out_abw[3 * n + 2] = w;
-        }
+        put_merge(out_abw, cap, n, a, b, w);
         ++n;
     }
     while (!max_iterations || n < max_iterations) {                      // core.ts:374-378
@@ -2238,8 +2267,7 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
         const int64_t base = (int64_t)c->h_len16.size();
         int64_t want = std::min<int64_t>(PIX_BATCH, BPE_MAX_VOCAB - base);
         if (max_iterations) want = std::min<int64_t>(want, max_iterations - n);
-        if ((rc = ensure_len16_cap(c, base + std::max<int64_t>(want, 1)))) return rc;
-        if ((rc = sync_len16(c, 1))) return rc;
+        if ((rc = len16_for_batch(c, std::max<int64_t>(want, 1)))) return rc;
         int status = PIX_HOST;
         int64_t nd = 0;
         if (want > 0) {
@@ -2272,21 +2300,8 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
                 const int64_t W = P->h_log[PIX_LOG * i + 2];
                 const int64_t cc = base + i;
                 c->h_len16[cc] = c->h_len16[a] + c->h_len16[b];            // core.ts:318
-                if (c->stats_on) {
-                    c->stats.iterations += 1;
-                    c->stats.live_tokens += c->n_live;
-                    c->stats.pix_merges += 1;
-                }
-                c->n_live -= W;
-                c->live_slots -= W;
-                c->h_count[a] -= W;
-                c->h_count[b] -= W;
-                c->h_count[cc] += W;
-                if (n < cap) {
-                    out_abw[3 * n] = a;
-                    out_abw[3 * n + 1] = b;
-                    out_abw[3 * n + 2] = W;
-                }
+                account_merge(c, a, b, (int32_t)cc, W, ACCT_ITER | ACCT_PIX);
+                put_merge(out_abw, cap, n, a, b, W);
             }
             c->len16_lo = base + nd;   // pix_commit wrote the new lengths on the device
             if (status == PIX_DONE) break;
@@ -2309,11 +2324,7 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
         if ((rc = do_apply(c, a, b, cc, nullptr))) return rc;
         if (c->pending) c->pend_expect = w;
         if ((rc = settle(c))) return rc;
-        if (n < cap) {
-            out_abw[3 * n] = a;
-            out_abw[3 * n + 1] = b;
-            out_abw[3 * n + 2] = w;
-        }
+        put_merge(out_abw, cap, n, a, b, w);
         ++n;
     }
     if ((rc = pix_finish(c))) return rc;
@@ -2463,8 +2474,7 @@ int pix_rank_begin(bpe_ctx *c, int64_t max_length, int64_t min_weight, unsigned 
     hipStream_t s = c->stream;
     if ((rc = pix_reserve(c))) return rc;
     const int64_t base = (int64_t)c->h_len16.size();
-    if ((rc = ensure_len16_cap(c, base + LOOP_BATCH))) return rc;
-    if ((rc = sync_len16(c, 1))) return rc;
+    if ((rc = len16_for_batch(c, LOOP_BATCH))) return rc;
     P->T.len16 = c->d_len16;
     if (P->max_length != max_length) {
         // (the selection keys filter on max_length: every block max again)
@@ -2595,16 +2605,7 @@ int pix_rank_end(bpe_ctx *c, int64_t *out, int64_t cap, int64_t *n_done, int *st
         const int64_t W = m[2], R = m[3];
         const int64_t cc = base + i;
         c->h_len16[cc] = c->h_len16[a] + c->h_len16[b];                // core.ts:318
-        if (c->stats_on) {
-            c->stats.iterations += 1;
-            c->stats.live_tokens += c->n_live;
-            c->stats.pix_merges += 1;
-        }
-        c->n_live -= R;
-        c->live_slots -= R;
-        c->h_count[a] -= R;
-        c->h_count[b] -= R;
-        c->h_count[cc] += R;
+        account_merge(c, a, b, (int32_t)cc, R, ACCT_ITER | ACCT_PIX);
         if (i < cap) {
             out[4 * i] = a;
             out[4 * i + 1] = b;
@@ -3153,11 +3154,7 @@ static int merge_until_stream(bpe_ctx *c, int64_t max_length, int64_t min_weight
         const int32_t cc = (int32_t)c->h_len16.size();
         if ((rc = do_apply(c, a, b, cc, nullptr))) return rc;
         if (c->pending) c->pend_expect = w;    // checked when the count comes back
-        if (n < cap) {
-            out_abw[3 * n] = a;
-            out_abw[3 * n + 1] = b;
-            out_abw[3 * n + 2] = w;
-        }
+        put_merge(out_abw, cap, n, a, b, w);
         ++n;
     }
     *n_merges = n;

@@ -6,17 +6,18 @@
 // made the maintained-state pass (MODE_INCR) 2 % slower on zipf C3, so only this instantiation
 // takes it, with its own scheduling flags and ring depth (Makefile STEP_FLAGS).
 //
-// The kernel header is included with internal linkage (an anonymous namespace), so its other
-// kernels are not defined twice in libbpe.so; the launcher therefore takes the engine's
-// structures as untyped pointers (same layout: the same header).
+// The pass's header (bpe_pass.hip.h, the part of the kernels this unit launches from) is included
+// with internal linkage (an anonymous namespace), so its kernels are not defined twice in
+// libbpe.so; the launcher therefore takes the engine's structures as untyped pointers (same
+// layout: the same header).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
 
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"   // (the header's other kernels, unused here)
+#pragma clang diagnostic ignored "-Wunused-function"   // (the header's other instantiations)
 namespace {
-#include "bpe_kernels.hip.h"
+#include "bpe_pass.hip.h"
 }
 #pragma clang diagnostic pop
 

@@ -397,6 +397,48 @@ def test_host_path_merge_between_batches_makes_the_plane_stale():
     assert b1['digest_builds'] == 2 and b1['digest_passes'] > 8, b1
 
 
+def stale_between(between):
+    """A batch of eight light merges on a fresh plane, one merge by `between` (a writer of the
+    corpus outside the device loop), a second batch: it rebuilds the plane and reads it again."""
+    samples, len16 = light_pairs_corpus(10)
+    wanted = {(2 * i, 2 * i + 1) for i in range(7)}
+    stats, merges, per_batch = drive(samples, len16, 0, 2, wanted, between=between)
+    print(per_batch)
+    assert merges[8][:2] == (16, 17), merges[8]
+    b0, b1 = per_batch[0], per_batch[1]
+    assert b0['digest_passes'] == 8 and b0['digest_builds'] == 1, b0
+    assert b1['digest_builds'] == 2 and b1['digest_passes'] > 8, b1
+
+
+@gpu
+@pytest.mark.parametrize('count_after', [False, True], ids=['apply_only', 'counting'])
+def test_replay_between_batches_makes_the_plane_stale(count_after):
+    """apply_merges of one merge: the apply-only pass (k_apply), or with count_after the counting
+    pass of the host path."""
+    def one_replayed_merge(e, st, want):
+        w = st.merge_until(0, 2, 1)
+        (a, b, W), = w
+        got = e.apply_merges([(a, b, HOT_BASE + len(want))], count_after=count_after)
+        assert [int(r) for r in got] == [W]
+        want += w
+
+    stale_between(one_replayed_merge)
+
+
+@gpu
+def test_position_index_merge_between_batches_makes_the_plane_stale():
+    """One merge in the incremental mode: the index merges in place in the corpus buffer, and the
+    corpus is written back to the chunk layout."""
+    def one_index_merge(e, st, want):
+        w = st.merge_until(0, 2, 1)
+        e.set_mode('incremental')
+        assert e.merge_until(0, 2, 1) == w
+        e.set_mode('stream')
+        want += w
+
+    stale_between(one_index_merge)
+
+
 @gpu
 def test_compaction_between_batches_makes_the_plane_stale():
     """A heavy merge first (the full form: 1 % of the slots die, so the next call compacts), seven
