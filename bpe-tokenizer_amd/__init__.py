@@ -40,6 +40,9 @@ C_API = [
     'bpe_encoder_create', 'bpe_encoder_destroy', 'bpe_encoder_add_merges', 'bpe_encoder_clear',
     'bpe_encoder_num_merges', 'bpe_encode_batch', 'bpe_encoder_get_stats', 'bpe_encoder_reset_stats',
     'bpe_rccl_unique_id', 'bpe_rank_rccl_init', 'bpe_rank_loop_rccl', 'bpe_rank_rccl_destroy',
+    'bpe_decoder_create', 'bpe_decoder_destroy', 'bpe_decoder_clear', 'bpe_decoder_add_tokens',
+    'bpe_decoder_add_merges', 'bpe_decoder_num_tokens', 'bpe_decoder_set_vector_index',
+    'bpe_decode_batch', 'bpe_decode_batch_device', 'bpe_decoder_get_stats', 'bpe_decoder_reset_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -57,6 +60,10 @@ DELTA_ROWS = 6      # BPE_DELTA_ROWS
 XCHG_WORDS = XCHG_HDR + DELTA_ROWS * MAX_VOCAB   # BPE_XCHG_WORDS
 TIE_WORDS = 32      # BPE_TIE_WORDS
 ENCODE_LDS_TOKENS = 16384   # BPE_ENCODE_LDS_TOKENS: longer texts are replayed by apply passes
+DECODE_TILE = 1024  # BPE_DECODE_TILE: values per workgroup of the decode kernels
+DECODE_SCAN_ROUND = 8192   # BPE_DECODE_SCAN_ROUND: tile sums per round of the decode kernels' scan
+DECODE_IDS = 0      # BPE_DECODE_IDS: decodeTokens, values are token ids
+DECODE_VECTORS = 1  # BPE_DECODE_VECTORS: decodeVector, values are vector indices
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -110,6 +117,16 @@ class EncoderStats(ctypes.Structure):
                 ('texts_rank', ctypes.c_int64), ('texts_replay', ctypes.c_int64),
                 ('tokens_in', ctypes.c_int64), ('tokens_out', ctypes.c_int64),
                 ('steps', ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DecoderStats(ctypes.Structure):
+    """bpe_decoder_stats (include/bpe.h)."""
+    _fields_ = [('kernel_ms', ctypes.c_double), ('calls', ctypes.c_int64),
+                ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
+                ('units_out', ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -194,6 +211,19 @@ def lib():
         'bpe_encode_batch': ([vp, i32p, i64p, ctypes.c_int64, i32p, i64p], ctypes.c_int),
         'bpe_encoder_get_stats': ([vp, ctypes.POINTER(EncoderStats)], ctypes.c_int),
         'bpe_encoder_reset_stats': ([vp], ctypes.c_int),
+        'bpe_decoder_create': ([ctypes.POINTER(vp), ctypes.c_int], ctypes.c_int),
+        'bpe_decoder_destroy': ([vp], ctypes.c_int),
+        'bpe_decoder_clear': ([vp], ctypes.c_int),
+        'bpe_decoder_add_tokens': ([vp, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_decoder_add_merges': ([vp, i32p, ctypes.c_int64], ctypes.c_int),
+        'bpe_decoder_num_tokens': ([vp, i32p, i64p], ctypes.c_int),
+        'bpe_decoder_set_vector_index': ([vp, i32p, ctypes.c_int32], ctypes.c_int),
+        'bpe_decode_batch': ([vp, ctypes.c_int, i32p, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p],
+                             ctypes.c_int),
+        'bpe_decode_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                     i64p], ctypes.c_int),
+        'bpe_decoder_get_stats': ([vp, ctypes.POINTER(DecoderStats)], ctypes.c_int),
+        'bpe_decoder_reset_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -593,6 +623,155 @@ class Encoder:
 
     def reset_stats(self):
         _check(lib().bpe_encoder_reset_stats(self._enc), 'bpe_encoder_reset_stats')
+
+
+def _units(x):
+    """A token's chars as UTF-16 code units: a str (lone surrogates kept) or an array of units."""
+    if isinstance(x, str):
+        return np.frombuffer(x.encode('utf-16-le', 'surrogatepass'), dtype='<u2')
+    return np.ascontiguousarray(x, dtype=np.uint16).ravel()
+
+
+def units_to_str(units):
+    """UTF-16 code units -> str, lone surrogates kept (as a JS string holds them)."""
+    return np.ascontiguousarray(units, dtype='<u2').tobytes().decode('utf-16-le', 'surrogatepass')
+
+
+class Decoder:
+    """decodeVector / decodeTokens (core.ts:447-471) for batches of texts (bpe_decoder_*,
+    include/bpe.h): the vocabulary lives on the device as a blob of UTF-16 units and one record per
+    token id; a call expands vector indices or token ids into units there (csrc/bpe_decode.hip).
+    No CPU fallback."""
+
+    _KINDS = {'ids': DECODE_IDS, 'tokens': DECODE_IDS, 'vectors': DECODE_VECTORS,
+              DECODE_IDS: DECODE_IDS, DECODE_VECTORS: DECODE_VECTORS}
+
+    def __init__(self, device=0):
+        p = ctypes.c_void_p()
+        _check(lib().bpe_decoder_create(ctypes.byref(p), int(device)), 'bpe_decoder_create')
+        self._dec = p
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, '_dec', None):
+            lib().bpe_decoder_destroy(self._dec)
+            self._dec = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        _check(lib().bpe_decoder_clear(self._dec), 'bpe_decoder_clear')
+
+    def add_tokens(self, tokens):
+        """Appends char tokens: each a str (encoded with surrogatepass, so lone surrogates
+        survive) or an array of UTF-16 units."""
+        parts = [_units(t) for t in tokens]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        units = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint16) if off[-1] \
+            else np.zeros(1, np.uint16)
+        _check(lib().bpe_decoder_add_tokens(self._dec, units.ctypes.data,
+                                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                            len(parts)), 'bpe_decoder_add_tokens')
+
+    def add_merges(self, merges):
+        """Appends merged tokens from (a, b, c) triples: chars[c] = chars[a] + chars[b]."""
+        abc = _i32(np.asarray(merges, dtype=np.int32).reshape(-1))
+        _check(lib().bpe_decoder_add_merges(self._dec, abc.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                            len(abc) // 3), 'bpe_decoder_add_merges')
+
+    def num_tokens(self):
+        """(token count, UTF-16 units of all tokens' chars)."""
+        n, u = ctypes.c_int32(), ctypes.c_int64()
+        _check(lib().bpe_decoder_num_tokens(self._dec, ctypes.byref(n), ctypes.byref(u)),
+               'bpe_decoder_num_tokens')
+        return n.value, u.value
+
+    def set_vector_index(self, from_vector_index):
+        """from_vector_index of compactVectorIndex (core.ts:222-241); None drops the index."""
+        if from_vector_index is None:
+            _check(lib().bpe_decoder_set_vector_index(self._dec, None, 0), 'bpe_decoder_set_vector_index')
+            return
+        a = _i32(from_vector_index).ravel()
+        buf = a if a.size else np.zeros(1, np.int32)
+        _check(lib().bpe_decoder_set_vector_index(self._dec, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  a.size), 'bpe_decoder_set_vector_index')
+
+    def decode_flat(self, vals, off, kind='vectors'):
+        """Flat form: texts vals[off[k]:off[k+1]] -> (units uint16, out_off int64).  The sizing
+        call, then the real one."""
+        kind = self._KINDS[kind]
+        vals = _i32(vals).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        src = vals if vals.size else np.zeros(1, np.int32)
+        i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        rc = lib().bpe_decode_batch(self._dec, kind, src.ctypes.data_as(i32p), off.ctypes.data_as(i64p), n,
+                                    None, 0, out_off.ctypes.data_as(i64p))
+        if rc == BPE_OK:   # (nothing to write)
+            return np.zeros(0, np.uint16), out_off
+        if rc != ERR_ARG or out_off[n] <= 0:
+            _check(rc, 'bpe_decode_batch')
+        units = np.empty(int(out_off[n]), dtype=np.uint16)
+        _check(lib().bpe_decode_batch(self._dec, kind, src.ctypes.data_as(i32p), off.ctypes.data_as(i64p), n,
+                                      units.ctypes.data, units.size, out_off.ctypes.data_as(i64p)),
+               'bpe_decode_batch')
+        return units, out_off
+
+    def decode(self, texts, kind='vectors'):
+        """texts: a list of vectors (or id sequences, kind='ids') -> list of str."""
+        lens = [len(t) for t in texts]
+        off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        vals = np.concatenate([np.asarray(t, dtype=np.int32) for t in texts]) if texts and off[-1] \
+            else np.zeros(0, np.int32)
+        units, oo = self.decode_flat(vals, off, kind)
+        raw = units.astype('<u2', copy=False).tobytes()
+        return [raw[2 * oo[k]:2 * oo[k + 1]].decode('utf-16-le', 'surrogatepass')
+                for k in range(len(texts))]
+
+    def decode_tensors(self, vals, off, kind='vectors'):
+        """Device form (bpe_decode_batch_device): vals a torch int32 tensor and off a torch int64
+        tensor on the decoder's device -> (int16 tensor of the units, int64 offsets tensor), both on
+        that device."""
+        import torch
+        kind = self._KINDS[kind]
+        if vals.dtype != torch.int32 or off.dtype != torch.int64:
+            raise BpeError('decode_tensors takes int32 values and int64 offsets', ERR_ARG)
+        if not (vals.is_cuda and off.is_cuda and vals.device.index == self.device
+                and off.device.index == self.device):
+            raise BpeError('decode_tensors takes tensors on the decoder\'s device', ERR_ARG)
+        vals, off = vals.contiguous(), off.contiguous()
+        n = off.numel() - 1
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=vals.device)
+        torch.cuda.synchronize(vals.device)   # (the decoder runs on a stream of its own)
+        need = ctypes.c_int64()
+        vp = vals.data_ptr() if vals.numel() else None
+        rc = lib().bpe_decode_batch_device(self._dec, kind, vp, off.data_ptr(), n, None, 0,
+                                           out_off.data_ptr(), ctypes.byref(need))
+        if rc == BPE_OK:
+            return torch.zeros(0, dtype=torch.int16, device=vals.device), out_off
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, 'bpe_decode_batch_device')
+        units = torch.empty(need.value, dtype=torch.int16, device=vals.device)
+        torch.cuda.synchronize(vals.device)
+        _check(lib().bpe_decode_batch_device(self._dec, kind, vp, off.data_ptr(), n, units.data_ptr(),
+                                             units.numel(), out_off.data_ptr(), ctypes.byref(need)),
+               'bpe_decode_batch_device')
+        return units, out_off
+
+    def stats(self):
+        s = DecoderStats()
+        _check(lib().bpe_decoder_get_stats(self._dec, ctypes.byref(s)), 'bpe_decoder_get_stats')
+        return s.as_dict()
+
+    def reset_stats(self):
+        _check(lib().bpe_decoder_reset_stats(self._dec), 'bpe_decoder_reset_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

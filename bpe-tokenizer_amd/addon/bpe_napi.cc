@@ -11,27 +11,9 @@
 #include <vector>
 
 #include "bpe.h"
+#include "napi_util.h"
 
 namespace {
-
-napi_value throw_native(napi_env env, const char *what) {
-    char buf[1024];
-    bpe_last_error(buf, sizeof buf);
-    std::string msg = buf[0] ? std::string(buf) : std::string("bpe native: ") + what + " failed";
-    napi_throw_error(env, nullptr, msg.c_str());
-    return nullptr;
-}
-
-napi_value throw_arg(napi_env env, const char *msg) {
-    napi_throw_type_error(env, nullptr, msg);
-    return nullptr;
-}
-
-bool get_args(napi_env env, napi_callback_info info, size_t want, napi_value *argv) {
-    size_t argc = want;
-    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok) return false;
-    return argc >= want;
-}
 
 // An engine handle: the context behind a JS external.  destroyEngine() frees the context (its
 // device memory) at once; the holder itself goes with the external's finalizer.
@@ -50,12 +32,6 @@ bpe_ctx *get_ctx(napi_env env, napi_value v) {
     void *p = nullptr;
     if (napi_get_value_external(env, v, &p) != napi_ok || !p) return nullptr;
     return static_cast<Holder *>(p)->c;   // (null after destroyEngine: every call then fails)
-}
-
-int64_t get_i64(napi_env env, napi_value v) {
-    int64_t x = 0;
-    napi_get_value_int64(env, v, &x);
-    return x;
 }
 
 napi_value num(napi_env env, double x) {

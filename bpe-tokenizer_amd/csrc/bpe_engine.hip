@@ -2651,7 +2651,7 @@ int pix_rank_end(bpe_ctx *c, int64_t *out, int64_t cap, int64_t *n_done, int *st
 // ================================================================================================
 extern "C" {
 
-int bpe_version(void) { return 200; }
+int bpe_version(void) { return 201; }
 
 int bpe_digest(const int32_t *ids, int64_t n, uint8_t *out) {
     if (n < 0 || (n > 0 && (!ids || !out))) return fail(BPE_ERR_ARG, "bpe native: bad digest arguments");

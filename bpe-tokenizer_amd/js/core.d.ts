@@ -54,6 +54,11 @@ export declare class BPETokenizer {
   encodeToVector(content: string): number[]
   decodeTokens(tokens: Token[]): string
   decodeVector(vector: number[]): string
+  /**
+   * decodeVector for many vectors at once on the GPU: equals `vectors.map(v => this.decodeVector(v))`,
+   * the `unknown vector index: V` error included.  Needs a HIP device.
+   */
+  decodeVectorBatch(vectors: number[][]): string[]
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

@@ -12,7 +12,8 @@
  *
  * There is no CPU fallback: the first corpus operation creates the HIP engine and throws
  * `bpe native: ...` when no device is available.  Methods that never touch the corpus
- * (fromJSON, toJSON, encode*, decode*, compactVectorIndex) work without a GPU.
+ * (fromJSON, toJSON, encode*, decode*, compactVectorIndex) work without a GPU; decodeVectorBatch,
+ * an addition to the reference's surface, decodes on the device and needs one.
  *
  * Node 12 compatible (no `?.`, `??`, `String.prototype.replaceAll`).
  */
@@ -21,6 +22,7 @@ const {
   maxLengthArg,
   minWeightArg,
   encodeIdsMaybeOnDevice,
+  decodeVectorsOnDevice,
   idsToCode,
 } = require('./native')
 
@@ -481,6 +483,36 @@ class BPETokenizer {
       }
     }
     return content
+  }
+
+  /**
+   * @description decodeVector for many vectors at once on the GPU (bpe_decode_batch): equals
+   * `vectors.map(v => this.decodeVector(v))`, the same error included (`unknown vector index: V`
+   * for the first offending entry in order).  The decoder holds the token table's chars on the
+   * device and follows it (native.js syncDecoder).  A batch with an entry that is no int32 takes
+   * the JS loop, as only that can tell what the reference does with it.  Needs a HIP device
+   * (`bpe native: ...` otherwise); decodeVector itself stays on the host.
+   */
+  decodeVectorBatch(vectors) {
+    if (vectors.length === 0) return []
+    if (!this.from_vector_index) this.compactVectorIndex()
+    let off = new Float64Array(vectors.length + 1)
+    for (let k = 0; k < vectors.length; k++) off[k + 1] = off[k] + vectors[k].length
+    let vals = new Int32Array(off[vectors.length])
+    let p = 0
+    for (let vector of vectors) {
+      for (let x of vector) {
+        if (typeof x !== 'number' || (x | 0) !== x) return vectors.map(v => this.decodeVector(v))
+        vals[p++] = x
+      }
+    }
+    try {
+      return decodeVectorsOnDevice(this, vals, off)
+    } catch (e) {
+      let m = /^unknown vector index: (-?\d+) \(text \d+, position \d+\)$/.exec(String(e && e.message))
+      if (m) throw new Error(`unknown vector index: ${m[1]}`)
+      throw e
+    }
   }
 
   /**

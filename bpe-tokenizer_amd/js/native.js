@@ -11,6 +11,13 @@ function loadNative() {
   return native
 }
 
+// the decoder's addon (addon/bpe_decode_napi.node: createDecoder ... decodeBatch)
+let nativeDecode = null
+function loadNativeDecode() {
+  if (!nativeDecode) nativeDecode = require(path.join(__dirname, '..', 'addon', 'bpe_decode_napi.node'))
+  return nativeDecode
+}
+
 /**
  * encodeToCode (core.ts:392-409) runs on the GPU (bpe_encode_batch: the merge-rank encoder for
  * texts up to ENCODE_LDS_TOKENS tokens, apply-only replay passes above) when a per-call cost model
@@ -123,6 +130,59 @@ function encodeIdsMaybeOnDevice(owner, list, tripleOf, ids) {
   }
 }
 
+/**
+ * The owner's device decoder (bpe_decoder_*), holding the chars of `owner.token_table` in id order
+ * and `owner.from_vector_index`; the tokens added to the table since the last call are appended to
+ * it (addToCorpus, applyMerge, restoreMerge, mergeUntil), a replaced or shortened table (fromJSON)
+ * rebuilds it, and a new from_vector_index array (compactVectorIndex makes one each time) is sent
+ * again.  The owner keeps the handle in non-enumerable fields.
+ */
+function syncDecoder(owner) {
+  let n = loadNativeDecode()
+  let table = owner.token_table
+  if (!owner._decoder) {
+    for (let k of ['_decoder', '_dec_table', '_dec_n', '_dec_last', '_dec_index'])
+      if (!Object.prototype.hasOwnProperty.call(owner, k))
+        Object.defineProperty(owner, k, { value: null, writable: true, enumerable: false })
+    owner._decoder = n.createDecoder(0)
+    owner._dec_table = null
+  }
+  let have = owner._dec_n || 0
+  if (owner._dec_table !== table || have > table.length || (have && table[have - 1] !== owner._dec_last)) {
+    n.decoderClear(owner._decoder)
+    owner._dec_table = table
+    owner._dec_index = null
+    owner._dec_n = have = 0
+  }
+  if (have < table.length) {
+    let k = table.length - have
+    let off = new Float64Array(k + 1)
+    for (let i = 0; i < k; i++) off[i + 1] = off[i] + table[have + i].chars.length
+    let units = new Uint16Array(off[k])
+    for (let i = 0; i < k; i++) {
+      let chars = table[have + i].chars
+      for (let j = 0, p = off[i]; j < chars.length; j++) units[p + j] = chars.charCodeAt(j)
+    }
+    owner._dec_n = 0 // (a failed append leaves the decoder to be rebuilt)
+    owner._dec_table = null
+    n.decoderAddTokens(owner._decoder, units, off)
+    owner._dec_table = table
+    owner._dec_index = null // (new tokens drop the decoder's index, core.ts:348)
+  }
+  owner._dec_n = table.length
+  owner._dec_last = table.length ? table[table.length - 1] : null
+  if (owner._dec_index !== owner.from_vector_index) {
+    n.decoderSetVectorIndex(owner._decoder, owner.from_vector_index ? Int32Array.from(owner.from_vector_index) : null)
+    owner._dec_index = owner.from_vector_index
+  }
+  return owner._decoder
+}
+
+/** a batch of vectors (Int32Array values, Float64Array offsets) through the owner's decoder -> strings */
+function decodeVectorsOnDevice(owner, vals, off) {
+  return loadNativeDecode().decodeBatch(syncDecoder(owner), vals, off, 1)
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -156,10 +216,13 @@ function minWeightArg(options) {
 
 module.exports = {
   loadNative,
+  loadNativeDecode,
   maxLengthArg,
   minWeightArg,
   encodeOnDevice,
   encodeIdsOnDevice,
   encodeIdsMaybeOnDevice,
+  syncDecoder,
+  decodeVectorsOnDevice,
   idsToCode,
 }

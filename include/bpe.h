@@ -394,6 +394,75 @@ int bpe_encode_batch(bpe_encoder *enc, const int32_t *ids, const int64_t *off, i
 int bpe_encoder_get_stats(bpe_encoder *enc, bpe_encoder_stats *out);
 int bpe_encoder_reset_stats(bpe_encoder *enc);
 
+/* ---- decoding ----------------------------------------------------------------------------------
+ * decodeVector / decodeTokens (core.ts:447-471) for a batch of texts: `content += token.chars` for
+ * every value of a text (core.ts:462-468), the values being vector indices (mapped through
+ * from_vector_index first) or token ids.  A decoder holds the vocabulary on one device: a blob of
+ * UTF-16 code units (`token.chars` is a JS string: a unit is a uint16_t, lone surrogates included)
+ * and one (offset, length) record per token id, with 32-bit offsets: a vocabulary whose chars would
+ * pass 2^32 units is refused with BPE_ERR_VOCAB.  Ids stay below BPE_MAX_VOCAB.
+ *
+ * Token order: ids are given in the order the tokens are added; char tokens (bpe_decoder_add_tokens)
+ * and merged tokens (bpe_decoder_add_merges) interleave freely, as they do in the reference when
+ * addToCorpus runs after merges.
+ * bpe_decoder_add_tokens appends n char tokens with ids count, count + 1, ...: token k's chars are
+ * units[off[k] .. off[k+1]) (any length >= 0; the reference makes 1 or 2).
+ * bpe_decoder_add_merges appends n merged tokens, chars[c] = chars[a] + chars[b] (core.ts:318,487),
+ * from the (a, b, c) triples the encoder takes.  Each c must equal the token count at its turn
+ * (core.ts:315,484), else BPE_ERR_ARG; a and b must be below that count (they may name tokens added
+ * earlier in the same call), else BPE_ERR_VOCAB.  A failed call adds nothing.
+ * bpe_decoder_set_vector_index takes from_vector_index of compactVectorIndex (core.ts:222-241): n
+ * token ids, each below the token count, else BPE_ERR_VOCAB; n == 0 with NULL drops the index.
+ * add_tokens, add_merges and clear drop the index too (invalidateVectorIndex, core.ts:348), and
+ * BPE_DECODE_VECTORS without an index returns BPE_ERR_STATE.
+ *
+ * bpe_decode_batch: text k is vals[off[k] .. off[k+1]); off[0] need not be 0, offsets must not
+ * decrease, n_texts == 0 is fine (out_off[0] = 0).  It writes n_texts + 1 offsets with
+ * out_off[0] = 0, so out_off[n_texts] is the number of units needed; if that exceeds units_cap no
+ * unit is written and BPE_ERR_ARG comes back (units_out == NULL with units_cap 0 is the sizing
+ * call); otherwise the texts' units are written back to back.
+ * A value outside [0, n_live) for vectors, or [0, n_tokens) for ids, fails the whole call with
+ * BPE_ERR_VOCAB; nothing is written to units_out or out_off, and the message is
+ *   unknown vector index: V (text K, position I)      /      unknown token index: V (text K, position I)
+ * for the first offending value in flat order, the one the reference's loop throws on
+ * (core.ts:462-468).  The decoder stays usable.
+ * bpe_decode_batch_device is the same pipeline on buffers already on the decoder's device (e.g.
+ * torch tensors holding a model's output); it runs on the decoder's stream and synchronises before
+ * returning; *needed is a host int64.  The host form is this function plus the copies.
+ * Offsets must not be negative (BPE_ERR_ARG).
+ * The kernels work on tiles of BPE_DECODE_TILE values, and the scan of the tiles' sums takes
+ * BPE_DECODE_SCAN_ROUND of them per round (csrc/bpe_decode.hip; exported for the tests, which
+ * place texts around the first and size a batch past the second). */
+#define BPE_DECODE_TILE 1024
+#define BPE_DECODE_SCAN_ROUND 8192
+#define BPE_DECODE_IDS 0       /* decodeTokens: values are token ids */
+#define BPE_DECODE_VECTORS 1   /* decodeVector: values are vector indices */
+typedef struct bpe_decoder bpe_decoder;
+typedef struct {
+    double kernel_ms;         /* HIP-event time of the decode kernels (per call: first launch to last) */
+    int64_t calls;            /* decode calls (the sizing call counts) */
+    int64_t texts;            /* texts of the calls whose values were all known */
+    int64_t values_in;        /* ... their values */
+    int64_t units_out;        /* UTF-16 units written */
+} bpe_decoder_stats;
+
+/* A decoder with no tokens on HIP device `device` (fails with BPE_ERR_HIP without one). */
+int bpe_decoder_create(bpe_decoder **out, int device);
+int bpe_decoder_destroy(bpe_decoder *dec);
+/* Drops every token (fromJSON of another tokenizer, core.ts:140-145). */
+int bpe_decoder_clear(bpe_decoder *dec);
+int bpe_decoder_add_tokens(bpe_decoder *dec, const uint16_t *units, const int64_t *off, int64_t n);
+int bpe_decoder_add_merges(bpe_decoder *dec, const int32_t *abc, int64_t n);
+int bpe_decoder_num_tokens(bpe_decoder *dec, int32_t *n_tokens, int64_t *n_units);
+int bpe_decoder_set_vector_index(bpe_decoder *dec, const int32_t *from_vector_index, int32_t n);
+int bpe_decode_batch(bpe_decoder *dec, int kind, const int32_t *vals, const int64_t *off,
+                     int64_t n_texts, uint16_t *units_out, int64_t units_cap, int64_t *out_off);
+int bpe_decode_batch_device(bpe_decoder *dec, int kind, const int32_t *d_vals, const int64_t *d_off,
+                            int64_t n_texts, uint16_t *d_units_out, int64_t units_cap,
+                            int64_t *d_out_off, int64_t *needed);
+int bpe_decoder_get_stats(bpe_decoder *dec, bpe_decoder_stats *out);
+int bpe_decoder_reset_stats(bpe_decoder *dec);
+
 #ifdef __cplusplus
 }
 #endif
