@@ -33,6 +33,7 @@ C_API = [
     'bpe_read_samples', 'bpe_find_next_merge',
     'bpe_apply_merge', 'bpe_apply_merges', 'bpe_merge_until', 'bpe_stats_enable', 'bpe_get_stats', 'bpe_reset_stats',
     'bpe_get_stream', 'bpe_synth_latin1', 'bpe_synth_zipf', 'bpe_recount', 'bpe_export_counts',
+    'bpe_debug_tables', 'bpe_table_state',
     'bpe_digest',
     'bpe_heavy_counts', 'bpe_select_counts', 'bpe_tie_positions', 'bpe_rank_loop_begin',
     'bpe_rank_loop_select', 'bpe_rank_loop_decide', 'bpe_rank_loop_count', 'bpe_rank_loop_end',
@@ -184,6 +185,8 @@ def lib():
         'bpe_reset_stats': ([vp], ctypes.c_int),
         'bpe_get_stream': ([vp, ctypes.POINTER(vp)], ctypes.c_int),
         'bpe_recount': ([vp], ctypes.c_int),
+        'bpe_debug_tables': ([vp, vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_table_state': ([vp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         'bpe_export_counts': ([vp, vp], ctypes.c_int),
         'bpe_heavy_counts': ([vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
         'bpe_select_counts': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -551,6 +554,31 @@ class Engine:
 
     def reset_stats(self):
         _check(lib().bpe_reset_stats(self._ctx), 'bpe_reset_stats')
+
+    # the maintained tables, for checking (include/bpe_tools.h) -------------------------------------
+    def is_maintained(self):
+        """Whether the context holds the single-context maintained state (bpe_table_state)."""
+        m = ctypes.c_int()
+        _check(lib().bpe_table_state(self._ctx, ctypes.byref(m)), 'bpe_table_state')
+        return bool(m.value)
+
+    def maintained_tables(self):
+        """(hot, keys, counts): the HOT_BINS u64 hot bins (pair (a, b) at b * 256 + a) and the
+        cold table's dense entries (key a << 16 | b as uint32, count as uint64; bpe_debug_tables:
+        the sizing call, then the real one)."""
+        hot = np.zeros(HOT_BINS, np.uint64)
+        n = ctypes.c_int64()
+        _check(lib().bpe_debug_tables(self._ctx, hot.ctypes.data, None, None, 0, ctypes.byref(n)),
+               'bpe_debug_tables')
+        keys = np.zeros(max(n.value, 1), np.uint32)
+        counts = np.zeros(max(n.value, 1), np.uint64)
+        cap = n.value
+        if cap:
+            _check(lib().bpe_debug_tables(self._ctx, hot.ctypes.data, keys.ctypes.data,
+                                          counts.ctypes.data, cap, ctypes.byref(n)),
+                   'bpe_debug_tables')
+        k = min(n.value, cap)
+        return hot, keys[:k], counts[:k]
 
 
 class Encoder:

@@ -3376,14 +3376,19 @@ int bpe_leave_global(bpe_ctx *c) {
     return BPE_OK;
 }
 
-// (debug: BPE_DEBUG_GLOBAL, bpe_multi.cpp) this context's maintained tables: the hot bins
-// (HOT_BINS u64 into hot) and the cold table's dense entries (up to cap; *n = n_used)
+// (bpe_tools.h; BPE_DEBUG_GLOBAL in bpe_multi.cpp, and the tests) this context's maintained
+// tables: the hot bins (HOT_BINS u64 into hot) and the cold table's dense entries (up to cap;
+// *n = n_used)
 int bpe_debug_tables(bpe_ctx *c, uint64_t *hot, uint32_t *keys, uint64_t *counts, int64_t cap,
                      int64_t *n) {
+    if (!c || c->multi || !hot || !n || cap < 0 || (cap > 0 && (!keys || !counts)))
+        return fail(BPE_ERR_ARG, "bpe native: bad debug_tables arguments");
     int rc = set_device(c);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(hot, c->d_hot, HOT_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    *n = 0;
+    if (!c->cold_cap) return BPE_OK;   // (no cold table yet)
     uint32_t nu = 0;
     HIP_TRY(hipMemcpy(&nu, c->cold.n_used, sizeof nu, hipMemcpyDeviceToHost));
     uint32_t of = 0;
@@ -3396,6 +3401,15 @@ int bpe_debug_tables(bpe_ctx *c, uint64_t *hot, uint32_t *keys, uint64_t *counts
         HIP_TRY(hipMemcpy(keys, c->cold.dkeys, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(counts, c->cold.dcounts, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    return BPE_OK;
+}
+
+int bpe_table_state(bpe_ctx *c, int *maintained) {
+    if (!c || c->multi || !maintained) return fail(BPE_ERR_ARG, "bpe native: bad table_state arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = settle(c))) return rc;
+    *maintained = c->cold_exact && c->counts_valid ? 1 : 0;
     return BPE_OK;
 }
 

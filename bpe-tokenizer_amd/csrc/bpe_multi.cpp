@@ -19,6 +19,7 @@
 // rank loop cannot finish (heavy sketch buckets, many tied pairs) takes the host protocol: global
 // table, exact counts of the heavy cold pairs on every shard, global selection, tie positions.
 #include "bpe_multi.h"
+#include "bpe_tools.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -810,9 +811,6 @@ int enter_maintained(bpe_multi *m) {
     if (dbg && !m->pix) MTRY(debug_compare_global(m, -1));
     return BPE_OK;
 }
-
-extern "C" int bpe_debug_tables(bpe_ctx *c, uint64_t *hot, uint32_t *keys, uint64_t *counts,
-                                int64_t cap, int64_t *n);
 
 // (debug: BPE_DEBUG_GLOBAL=1) every shard's copy of the global tables must be the same: the hot
 // bins, and the cold pairs with a count (holes and dead claims aside)

@@ -28,6 +28,21 @@ int bpe_synth_zipf(uint32_t seed, double s, uint32_t n_words, uint64_t first_sam
 struct bpe_ctx;
 int bpe_recount(struct bpe_ctx *ctx);
 
+/* The maintained tables of a single-device context, copied out for checking: the HOT_BINS (65536)
+ * u64 hot bins into `hot` (pair (a, b) with both ids below 256 at b * 256 + a) and the cold
+ * table's dense entries into keys / counts (key a << 16 | b, 0xFFFFFFFF = a hole; a count of 0 =
+ * a claim whose pair is gone), up to `cap` of them; *n = the entries in use.  Two calls: cap 0
+ * (keys and counts may be null) for *n, then with room.  BPE_ERR_ARG for a multi-device context
+ * and for null arguments.  What the tables mean is bpe_table_state's matter. */
+int bpe_debug_tables(struct bpe_ctx *ctx, uint64_t *hot, uint32_t *keys, uint64_t *counts,
+                     int64_t cap, int64_t *n);
+
+/* *maintained = 1 while the context holds the single-context maintained state (the hot bins and
+ * the cold table hold the exact count of every pair of the corpus and are kept so merge by
+ * merge), else 0.  A pending merge's replacement count is settled first; nothing else changes.
+ * BPE_ERR_ARG for a multi-device context and for null arguments. */
+int bpe_table_state(struct bpe_ctx *ctx, int *maintained);
+
 #ifdef __cplusplus
 }
 #endif
