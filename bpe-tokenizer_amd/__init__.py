@@ -44,6 +44,8 @@ C_API = [
     'bpe_decoder_create', 'bpe_decoder_destroy', 'bpe_decoder_clear', 'bpe_decoder_add_tokens',
     'bpe_decoder_add_merges', 'bpe_decoder_num_tokens', 'bpe_decoder_set_vector_index',
     'bpe_decode_batch', 'bpe_decode_batch_device', 'bpe_decoder_get_stats', 'bpe_decoder_reset_stats',
+    'bpe_encoder_set_chars', 'bpe_encoder_set_vector_index', 'bpe_encode_text_batch',
+    'bpe_encode_text_batch_device', 'bpe_encoder_get_text_stats', 'bpe_encoder_reset_text_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -65,6 +67,10 @@ DECODE_TILE = 1024  # BPE_DECODE_TILE: values per workgroup of the decode kernel
 DECODE_SCAN_ROUND = 8192   # BPE_DECODE_SCAN_ROUND: tile sums per round of the decode kernels' scan
 DECODE_IDS = 0      # BPE_DECODE_IDS: decodeTokens, values are token ids
 DECODE_VECTORS = 1  # BPE_DECODE_VECTORS: decodeVector, values are vector indices
+TEXT_TILE = 2048    # BPE_TEXT_TILE: UTF-16 units per workgroup of the text front end
+TEXT_SCAN_ROUND = 2048   # BPE_TEXT_SCAN_ROUND: tile counts per round of the front end's scan
+ENCODE_IDS = 0      # BPE_ENCODE_IDS: text -> token ids
+ENCODE_VECTORS = 1  # BPE_ENCODE_VECTORS: text -> vector indices (encodeToVector)
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -128,6 +134,16 @@ class DecoderStats(ctypes.Structure):
     _fields_ = [('kernel_ms', ctypes.c_double), ('calls', ctypes.c_int64),
                 ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
                 ('units_out', ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TextStats(ctypes.Structure):
+    """bpe_text_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units_in', ctypes.c_int64),
+                ('chars', ctypes.c_int64), ('values_out', ctypes.c_int64),
+                ('front_ms', ctypes.c_double), ('back_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -227,6 +243,14 @@ def lib():
                                      i64p], ctypes.c_int),
         'bpe_decoder_get_stats': ([vp, ctypes.POINTER(DecoderStats)], ctypes.c_int),
         'bpe_decoder_reset_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_set_chars': ([vp, vp, i32p, ctypes.c_int64], ctypes.c_int),
+        'bpe_encoder_set_vector_index': ([vp, i32p, ctypes.c_int32], ctypes.c_int),
+        'bpe_encode_text_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p],
+                                  ctypes.c_int),
+        'bpe_encode_text_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                          i64p], ctypes.c_int),
+        'bpe_encoder_get_text_stats': ([vp, ctypes.POINTER(TextStats)], ctypes.c_int),
+        'bpe_encoder_reset_text_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -591,6 +615,7 @@ class Encoder:
         p = ctypes.c_void_p()
         _check(lib().bpe_encoder_create(ctypes.byref(p), int(device)), 'bpe_encoder_create')
         self._enc = p
+        self.device = int(device)
         if merges is not None and len(merges):
             self.add_merges(merges)
 
@@ -651,6 +676,90 @@ class Encoder:
 
     def reset_stats(self):
         _check(lib().bpe_encoder_reset_stats(self._enc), 'bpe_encoder_reset_stats')
+
+    # the text form: encodeToVector (core.ts:392-445) from UTF-16 units ---------------------------
+    _KINDS = {'ids': ENCODE_IDS, 'tokens': ENCODE_IDS, 'vectors': ENCODE_VECTORS,
+              ENCODE_IDS: ENCODE_IDS, ENCODE_VECTORS: ENCODE_VECTORS}
+
+    def set_chars(self, mapping):
+        """Replaces the char table (char_to_token): a dict of a str of one code point (a lone
+        surrogate included), or an int code point, to a token id.  An empty dict drops it."""
+        cps = np.asarray([ord(k) if isinstance(k, str) else int(k) for k in mapping], dtype=np.uint32)
+        ids = _i32(list(mapping.values()))
+        cbuf = cps if cps.size else np.zeros(1, np.uint32)
+        ibuf = ids if ids.size else np.zeros(1, np.int32)
+        _check(lib().bpe_encoder_set_chars(self._enc, cbuf.ctypes.data,
+                                           ibuf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), cps.size),
+               'bpe_encoder_set_chars')
+
+    def set_vector_index(self, to_vector_index):
+        """to_vector_index of compactVectorIndex (core.ts:222-241): one entry per token id, -1
+        for a hole; None drops the index."""
+        if to_vector_index is None:
+            _check(lib().bpe_encoder_set_vector_index(self._enc, None, 0), 'bpe_encoder_set_vector_index')
+            return
+        a = _i32(to_vector_index).ravel()
+        buf = a if a.size else np.zeros(1, np.int32)
+        _check(lib().bpe_encoder_set_vector_index(self._enc, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                  a.size), 'bpe_encoder_set_vector_index')
+
+    def encode_text_flat(self, units, off, kind='vectors'):
+        """Flat form: texts units[off[k]:off[k+1]] (UTF-16 units) -> (values int32, out_off int64)."""
+        kind = self._KINDS[kind]
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        total = max(int(off[-1] - off[0]), 0) if n > 0 else 0
+        out = np.zeros(max(total, 1), dtype=np.int32)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        _check(lib().bpe_encode_text_batch(self._enc, kind, src.ctypes.data,
+                                           off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                                           out.ctypes.data, out.size,
+                                           out_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               'bpe_encode_text_batch')
+        return out[:out_off[n]], out_off
+
+    def encode_text(self, texts, kind='vectors'):
+        """texts: a list of str (encoded with surrogatepass: lone surrogates survive) -> list of
+        int32 arrays of vector indices (or token ids, kind='ids')."""
+        parts = [_units(t) for t in texts]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        units = np.concatenate(parts).astype(np.uint16) if parts and off[-1] else np.zeros(0, np.uint16)
+        out, oo = self.encode_text_flat(units, off, kind)
+        return [out[oo[k]:oo[k + 1]].copy() for k in range(len(parts))]
+
+    def encode_text_tensors(self, units, off, kind='vectors'):
+        """Device form (bpe_encode_text_batch_device): units a torch int16 or uint16 tensor and off
+        a torch int64 tensor on the encoder's device -> (int32 tensor of the values, int64 offsets
+        tensor), both on that device."""
+        import torch
+        kind = self._KINDS[kind]
+        if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+            raise BpeError('encode_text_tensors takes int16 or uint16 units and int64 offsets', ERR_ARG)
+        if not (units.is_cuda and off.is_cuda and units.device.index == self.device
+                and off.device.index == self.device):
+            raise BpeError('encode_text_tensors takes tensors on the encoder\'s device', ERR_ARG)
+        units, off = units.contiguous(), off.contiguous()
+        n = off.numel() - 1
+        vals = torch.empty(max(units.numel(), 1), dtype=torch.int32, device=units.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=units.device)
+        torch.cuda.synchronize(units.device)   # (the encoder runs on a stream of its own)
+        need = ctypes.c_int64()
+        up = units.data_ptr() if units.numel() else None
+        _check(lib().bpe_encode_text_batch_device(self._enc, kind, up, off.data_ptr(), n, vals.data_ptr(),
+                                                  units.numel(), out_off.data_ptr(), ctypes.byref(need)),
+               'bpe_encode_text_batch_device')
+        return vals[:need.value], out_off
+
+    def text_stats(self):
+        s = TextStats()
+        _check(lib().bpe_encoder_get_text_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_text_stats')
+        return s.as_dict()
+
+    def reset_text_stats(self):
+        _check(lib().bpe_encoder_reset_text_stats(self._enc), 'bpe_encoder_reset_text_stats')
 
 
 def _units(x):

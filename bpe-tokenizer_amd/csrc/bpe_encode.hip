@@ -28,6 +28,11 @@
 // Two workgroup barriers per step.  Texts longer than an LDS buffer, and merge lists for which the
 // greedy would differ, go through the apply-only streaming passes of a scratch engine
 // (bpe_apply_merges: the same M replaceAll rewrites, one pass each, all long texts together).
+//
+// The text form (bpe_encode_text_batch, at the end of this file) puts bpe_text.hip.h's kernels
+// around k_encode: a front end from UTF-16 units to the compact ids and id offsets k_encode reads,
+// and a back end that packs its output as vector indices; encodeToVector (core.ts:392-445) of a
+// batch then never maps a char or an id on the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -420,6 +425,8 @@ constexpr int LDS_TAB_MIN_TOKENS = 128;
 
 }  // namespace
 
+#include "bpe_text.hip.h"   // the text front end and the vector back end (bpe_encode_text_batch)
+
 struct bpe_encoder {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -450,6 +457,7 @@ struct bpe_encoder {
     bpe_ctx *scratch = nullptr;               // the apply-pass route
     int32_t scratch_known = 0;
     bpe_encoder_stats st{};
+    bpe_text_state txt;                       // the text form (bpe_encode_text_batch)
 };
 
 namespace {
@@ -778,6 +786,354 @@ int encode_groups(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_
     return rc;
 }
 
+// ---- the text form (bpe_encode_text_batch): bpe_text.hip.h's kernels around k_encode -------------
+
+void text_free(bpe_encoder *E) {
+    bpe_text_state &T = E->txt;
+    if (T.d_bmp) (void)hipFree(T.d_bmp);
+    if (T.d_pairs) (void)hipFree(T.d_pairs);
+    if (T.d_tvi) (void)hipFree(T.d_tvi);
+    if (T.d_st) (void)hipFree(T.d_st);
+    if (T.h_st) (void)hipHostFree(T.h_st);
+    for (hipEvent_t &ev : T.ev)
+        if (ev) (void)hipEventDestroy(ev);
+    T = bpe_text_state{};
+}
+
+void text_drop_index(bpe_encoder *E) {
+    E->txt.tvi.clear();
+    E->txt.has_tvi = false;
+    E->txt.tvi_dirty = false;
+}
+
+// status words and events (made by the first text call), then the tables that changed
+int text_upload(bpe_encoder *E) {
+    bpe_text_state &T = E->txt;
+    if (!T.d_st) ENC_TRY(hipMalloc((void **)&T.d_st, TS_WORDS * 8));
+    if (!T.h_st) ENC_TRY(hipHostMalloc((void **)&T.h_st, TS_WORDS * 8, hipHostMallocDefault));
+    for (hipEvent_t &ev : T.ev)
+        if (!ev) ENC_TRY(hipEventCreate(&ev));
+    int rc;
+    if (T.has_chars && T.chars_dirty) {
+        if (!T.d_bmp) ENC_TRY(hipMalloc((void **)&T.d_bmp, 65536 * 2));
+        if ((rc = grow_dev(&T.d_pairs, &T.d_pairs_n, T.pairs.size()))) return rc;
+        ENC_TRY(hipMemcpyAsync(T.d_bmp, T.bmp.data(), 65536 * 2, hipMemcpyHostToDevice, E->stream));
+        ENC_TRY(hipMemcpyAsync(T.d_pairs, T.pairs.data(), T.pairs.size() * sizeof(uint2),
+                               hipMemcpyHostToDevice, E->stream));
+        T.chars_dirty = false;
+    }
+    if (T.has_tvi && T.tvi_dirty) {
+        if ((rc = grow_dev(&T.d_tvi, &T.d_tvi_n, T.tvi.size()))) return rc;
+        if (!T.tvi.empty())
+            ENC_TRY(hipMemcpyAsync(T.d_tvi, T.tvi.data(), T.tvi.size() * 4, hipMemcpyHostToDevice, E->stream));
+        T.tvi_dirty = false;
+    }
+    // (the host vectors may be replaced right after the call returns: the copies must be done)
+    ENC_TRY(hipStreamSynchronize(E->stream));
+    return BPE_OK;
+}
+
+int text_char_error(int64_t k, int64_t unit, uint32_t u0, uint32_t u1, bool has_next) {
+    uint32_t cp = u0;
+    if ((u0 & 0xFC00u) == 0xD800u && has_next && (u1 & 0xFC00u) == 0xDC00u)
+        cp = 0x10000u + ((u0 - 0xD800u) << 10) + (u1 - 0xDC00u);
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "unknown token, char: U+%04X (text %lld, unit %lld)", cp, (long long)k,
+                  (long long)unit);
+    return bpe_fail(BPE_ERR_VOCAB, msg);
+}
+
+int text_index_error(int32_t id, int64_t k, int64_t pos) {
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "unknown token index: %d (text %lld, position %lld)", id, (long long)k,
+                  (long long)pos);
+    return bpe_fail(BPE_ERR_VOCAB, msg);
+}
+
+// The pipeline.  dev: units, off, vals_out and out_off are device buffers (the device form);
+// otherwise host buffers, staged through the encoder's device buffer.
+int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off, int64_t n_texts,
+             int32_t *vals_out, int64_t cap, int64_t *out_off, bool dev, int64_t *needed) {
+    bpe_text_state &T = E->txt;
+    *needed = 0;
+    if (kind != BPE_ENCODE_IDS && kind != BPE_ENCODE_VECTORS)
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode kind");
+    if (n_texts < 0 || n_texts >= 0x7FFFFFFF || cap < 0 || !out_off || (n_texts && !off) || (cap && !vals_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_text_batch arguments");
+    if (kind == BPE_ENCODE_VECTORS && !T.has_tvi)
+        return bpe_fail(BPE_ERR_STATE, "bpe native: encode to vectors without a vector index "
+                                       "(bpe_encoder_set_vector_index)");
+    ENC_TRY(hipSetDevice(E->device));
+    hipStream_t s = E->stream;
+    T.st.calls++;
+    // the offsets on the host: checked here, and the launch lists are made from them
+    std::vector<int64_t> off_copy;
+    const int64_t *h_off = off;
+    if (dev && n_texts) {
+        off_copy.resize((size_t)n_texts + 1);
+        ENC_TRY(hipMemcpyAsync(off_copy.data(), off, off_copy.size() * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipStreamSynchronize(s));
+        h_off = off_copy.data();
+    }
+    if (n_texts && h_off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+    for (int64_t k = 0; k < n_texts; ++k)
+        if (h_off[k + 1] < h_off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+    const int64_t base = n_texts ? h_off[0] : 0, total = n_texts ? h_off[n_texts] - base : 0;
+    if (total && !units) return bpe_fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+    if (total && !T.has_chars)
+        return bpe_fail(BPE_ERR_STATE, "bpe native: encode of text without a char table (bpe_encoder_set_chars)");
+    if (total == 0) {   // (no text, or every text empty)
+        if (dev) {
+            ENC_TRY(hipMemsetAsync(out_off, 0, (size_t)(n_texts + 1) * 8, s));
+            ENC_TRY(hipStreamSynchronize(s));
+        } else {
+            std::memset(out_off, 0, (size_t)(n_texts + 1) * 8);
+        }
+        T.st.texts += n_texts;
+        return BPE_OK;
+    }
+    int rc;
+    if ((rc = text_upload(E)) || (rc = upload_table(E))) return rc;
+    // launch shape of every text by its unit count (its chars are at most that many), or the
+    // apply-pass route for the whole call
+    std::vector<int32_t> lists[N_SHAPES];
+    bool replay = !E->greedy_ok;
+    for (int64_t k = 0; k < n_texts && !replay; ++k) {
+        const int64_t l = h_off[k + 1] - h_off[k];
+        if (l > CAP_MAX) {
+            replay = true;
+        } else {
+            int i = 0;
+            while (shape_cap(i) < l) ++i;
+            lists[i].push_back((int32_t)k);
+        }
+    }
+    const int mis = dev ? (int)(((uintptr_t)(units + base) >> 1) & (TXT_RUN - 1)) : 0;
+    const int64_t n_tiles = (total + mis + TXT_TILE - 1) / TXT_TILE;
+    if (n_tiles > 0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: text batch too large");
+    // device: [ooff (n+2) | ids, then the packed output | id_off (n+2) | which | out | len |
+    //          tile counts, then bases | first text of each tile | tile marks | units | off]
+    // (the last two: the host form's staging); pinned: [which | ooff]
+    const size_t b_ids = align16((size_t)total * 4);
+    const size_t b_off = align16((size_t)(n_texts + 2) * 8);
+    const size_t b_which = align16((size_t)n_texts * 4);
+    const size_t b_tiles = align16((size_t)n_tiles * 8), b_edge = align16((size_t)n_tiles * 4);
+    const size_t b_units = dev ? 0 : align16((size_t)total * 2);
+    const size_t bytes = b_off + b_ids + b_off + b_which + b_ids + b_which + 2 * b_tiles + b_edge + b_units +
+                         (dev ? 0 : b_off);
+    if ((rc = grow_stage(E, b_which + b_off, bytes))) return rc;
+    struct Release {
+        bpe_encoder *e;
+        ~Release() { release_stage(e); }
+    } release{E};
+    char *d = E->d_buf;
+    int64_t *d_ooff = reinterpret_cast<int64_t *>(d);
+    int32_t *d_ids = reinterpret_cast<int32_t *>(d += b_off);
+    int64_t *d_idoff = reinterpret_cast<int64_t *>(d += b_ids);
+    int32_t *d_which = reinterpret_cast<int32_t *>(d += b_off);
+    int32_t *d_out = reinterpret_cast<int32_t *>(d += b_which);
+    int32_t *d_len = reinterpret_cast<int32_t *>(d += b_ids);
+    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(d += b_which);
+    long long *d_first = reinterpret_cast<long long *>(d += b_tiles);
+    uint32_t *d_edge = reinterpret_cast<uint32_t *>(d += b_tiles);
+    uint16_t *d_units = reinterpret_cast<uint16_t *>(d += b_edge);
+    int64_t *d_uoff = reinterpret_cast<int64_t *>(d += b_units);
+    unsigned long long *d_err = reinterpret_cast<unsigned long long *>(d_idoff + n_texts + 1);
+    int32_t *h_which = reinterpret_cast<int32_t *>(E->h_buf);
+    int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf + b_which);
+    const uint16_t *units_al;
+    const int64_t *k_off;
+    if (dev) {
+        units_al = units + base - mis;
+        k_off = off;
+    } else {
+        ENC_TRY(hipMemcpyAsync(d_units, units + base, (size_t)total * 2, hipMemcpyHostToDevice, s));
+        ENC_TRY(hipMemcpyAsync(d_uoff, off, (size_t)(n_texts + 1) * 8, hipMemcpyHostToDevice, s));
+        units_al = d_units;
+        k_off = d_uoff;
+    }
+    ENC_TRY(hipMemsetAsync(T.d_st, 0xFF, 16, s));
+    ENC_TRY(hipMemsetAsync(T.d_st + 2, 0, (TS_WORDS - 2) * 8, s));
+    ENC_TRY(hipMemsetAsync(d_err, 0, 8, s));
+    ENC_TRY(hipMemsetAsync(d_first, 0xFF, (size_t)n_tiles * 8, s));
+    ENC_TRY(hipMemsetAsync(d_edge, 0, (size_t)n_tiles * 4, s));
+    const CharTab ct{T.d_bmp, T.d_pairs, (1u << T.pair_bits) - 1, 32 - T.pair_bits};
+    ENC_TRY(hipEventRecord(T.ev[0], s));
+    k_txt_count<<<(unsigned)((n_tiles + TXT_CNT_TILES - 1) / TXT_CNT_TILES), TXT_WG, 0, s>>>(units_al, mis, total,
+                                                                                          n_tiles, d_tiles);
+    k_txt_texts<<<(unsigned)std::min<int64_t>((n_texts + 256) / 256, 2048), 256, 0, s>>>(
+        units_al, mis, total, k_off, n_texts, base, n_tiles, d_first, d_edge, d_tiles);
+    k_txt_scan<<<1, 1024, 0, s>>>(d_tiles, n_tiles, T.d_st);
+    k_txt_map<<<(unsigned)n_tiles, TXT_WG, 0, s>>>(units_al, mis, total, ct, d_tiles, d_first, d_edge, k_off,
+                                                  n_texts, base, d_ids, d_idoff, T.d_st);
+    ENC_TRY(hipGetLastError());
+    ENC_TRY(hipEventRecord(T.ev[1], s));
+
+    // the unknown char at flat unit `pc`: its text, and the message (two units come back)
+    auto text_of_unit = [&](int64_t pc) {
+        return (int64_t)(std::upper_bound(h_off, h_off + n_texts + 1, base + pc) - h_off) - 1;
+    };
+    auto char_error = [&](int64_t pc) -> int {
+        const int64_t k = text_of_unit(pc);
+        const bool has_next = base + pc + 1 < h_off[k + 1];
+        uint16_t u[2] = {0, 0};
+        if (dev) {
+            ENC_TRY(hipMemcpyAsync(u, units + base + pc, has_next ? 4 : 2, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipStreamSynchronize(s));
+        } else {
+            u[0] = units[base + pc];
+            if (has_next) u[1] = units[base + pc + 1];
+        }
+        return text_char_error(k, base + pc - h_off[k], u[0], u[1], has_next);
+    };
+    int64_t n_out = 0;
+    float ms = 0;
+
+    if (replay) {
+        // host assembly, as bpe_encode_batch does for these texts: the front end's ids come back,
+        // bpe_encode_batch replays them, and the vector index is applied here
+        ENC_TRY(hipMemcpyAsync(T.h_st, T.d_st, TS_WORDS * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipStreamSynchronize(s));
+        const int64_t n_ids = (int64_t)T.h_st[TS_CHARS];
+        if (n_ids < 0 || n_ids > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad char count");
+        std::vector<int32_t> ids((size_t)std::max<int64_t>(n_ids, 1)), vals((size_t)std::max<int64_t>(n_ids, 1));
+        std::vector<int64_t> idoff((size_t)n_texts + 1), ooff((size_t)n_texts + 1, 0);
+        ENC_TRY(hipMemcpyAsync(ids.data(), d_ids, (size_t)n_ids * 4, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipMemcpyAsync(idoff.data(), d_idoff, idoff.size() * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipStreamSynchronize(s));
+        ENC_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+        T.st.front_ms += ms;
+        const bool bad_char = T.h_st[TS_BADCHAR] != TXT_NONE;
+        const int64_t pc = (int64_t)T.h_st[TS_BADCHAR];
+        // (an unknown char: the texts before its text may still hold a hole, which comes first)
+        const int64_t n_use = bad_char ? text_of_unit(pc) : n_texts;
+        if (bad_char && kind == BPE_ENCODE_IDS) return char_error(pc);
+        if ((rc = bpe_encode_batch(E, ids.data(), idoff.data(), n_use, vals.data(), ooff.data()))) return rc;
+        if (kind == BPE_ENCODE_VECTORS) {
+            const int64_t n_tvi = (int64_t)T.tvi.size();
+            for (int64_t k = 0; k < n_use; ++k)
+                for (int64_t i = ooff[k]; i < ooff[k + 1]; ++i) {
+                    const int32_t id = vals[(size_t)i];
+                    const int32_t v = id < n_tvi ? T.tvi[(size_t)id] : -1;
+                    if (v < 0) return text_index_error(id, k, i - ooff[k]);
+                    vals[(size_t)i] = v;
+                }
+        }
+        if (bad_char) return char_error(pc);
+        n_out = ooff[n_texts];
+        *needed = n_out;
+        if (n_out > cap) {
+            char msg[128];
+            std::snprintf(msg, sizeof msg, "bpe native: encode needs %lld values, the buffer holds %lld",
+                          (long long)n_out, (long long)cap);
+            return bpe_fail(BPE_ERR_ARG, msg);
+        }
+        if (dev) {
+            if (n_out) ENC_TRY(hipMemcpyAsync(vals_out, vals.data(), (size_t)n_out * 4, hipMemcpyHostToDevice, s));
+            ENC_TRY(hipMemcpyAsync(out_off, ooff.data(), ooff.size() * 8, hipMemcpyHostToDevice, s));
+            ENC_TRY(hipStreamSynchronize(s));
+        } else {
+            if (n_out) std::memcpy(vals_out, vals.data(), (size_t)n_out * 4);
+            std::memcpy(out_off, ooff.data(), ooff.size() * 8);
+        }
+        T.st.chars += n_ids;
+    } else {
+        size_t at = 0;
+        for (auto &L : lists) {
+            std::memcpy(h_which + at, L.data(), L.size() * 4);
+            at += L.size();
+        }
+        ENC_TRY(hipMemcpyAsync(d_which, h_which, (size_t)n_texts * 4, hipMemcpyHostToDevice, s));
+        const size_t tab = (size_t)E->lt.words * 4;
+        const bool few = (size_t)n_texts <= LATENCY_TEXTS;
+        ENC_TRY(hipEventRecord(E->ev0, s));
+        at = 0;
+        for (int i = 0; i < N_SHAPES; ++i) {
+            if (lists[i].empty()) continue;
+            const bool tab_lds = few && shape_cap(i) > LDS_TAB_MIN_TOKENS && shape_lds(i) + tab <= LDS_BYTES;
+            launch_shape(i, E, (unsigned)lists[i].size(), tab_lds, d_ids, d_idoff, d_which + at, d_out, d_len,
+                         d_err);
+            at += lists[i].size();
+        }
+        ENC_TRY(hipGetLastError());
+        ENC_TRY(hipEventRecord(E->ev1, s));
+        // packed on the device, into the ids buffer (read by the kernels above, free now)
+        const bool vec = kind == BPE_ENCODE_VECTORS;
+        const uint32_t n_tvi = (uint32_t)T.tvi.size();
+        ENC_TRY(hipEventRecord(T.ev[2], s));
+        if (n_texts <= 1024 && total <= (1 << 18)) {
+            if (vec)
+                k_txt_pack_small_vec<<<1, 1024, 0, s>>>(d_out, d_idoff, d_len, (int)n_texts, d_ooff, d_err, T.d_tvi,
+                                                        n_tvi, d_ids, T.d_st);
+            else
+                k_pack_small<<<1, 1024, 0, s>>>(d_out, d_idoff, d_len, (int)n_texts, d_ooff, d_err, d_ids);
+        } else {
+            k_scan_lens<<<1, 1024, 0, s>>>(d_len, n_texts, d_ooff, d_err);
+            if (vec)
+                k_txt_gather_vec<<<(unsigned)((n_texts + 3) / 4), 256, 0, s>>>(d_out, d_idoff, d_len, d_ooff, n_texts,
+                                                                              T.d_tvi, n_tvi, d_ids, T.d_st);
+            else
+                k_gather<<<(unsigned)((n_texts + 3) / 4), 256, 0, s>>>(d_out, d_idoff, d_len, d_ooff, n_texts, d_ids);
+        }
+        ENC_TRY(hipGetLastError());
+        ENC_TRY(hipEventRecord(T.ev[3], s));
+        ENC_TRY(hipMemcpyAsync(T.h_st, T.d_st, TS_WORDS * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipMemcpyAsync(h_ooff, d_ooff, (size_t)(n_texts + 2) * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipStreamSynchronize(s));
+        ENC_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+        T.st.front_ms += ms;
+        ENC_TRY(hipEventElapsedTime(&ms, T.ev[2], T.ev[3]));
+        T.st.back_ms += ms;
+        ENC_TRY(hipEventElapsedTime(&ms, E->ev0, E->ev1));
+        E->st.kernel_ms += ms;
+        if (h_ooff[n_texts + 1]) return bpe_fail(BPE_ERR_STATE, "bpe native: char table id out of range");
+        // the reference's error order: the first failing text's error, and inside one text the char's
+        const bool bad_char = T.h_st[TS_BADCHAR] != TXT_NONE, bad_idx = vec && T.h_st[TS_BADIDX] != TXT_NONE;
+        if (bad_char || bad_idx) {
+            const int64_t pc = (int64_t)T.h_st[TS_BADCHAR], pi = (int64_t)T.h_st[TS_BADIDX];
+            const int64_t kc = bad_char ? text_of_unit(pc) : n_texts;
+            const int64_t ki = bad_idx ? (int64_t)(std::upper_bound(h_ooff, h_ooff + n_texts + 1, pi) - h_ooff) - 1
+                                       : n_texts;
+            if (ki >= kc) return char_error(pc);
+            int64_t at_in = 0;
+            int32_t id = 0;
+            ENC_TRY(hipMemcpyAsync(&at_in, d_idoff + ki, 8, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipStreamSynchronize(s));
+            ENC_TRY(hipMemcpyAsync(&id, d_out + at_in + (pi - h_ooff[ki]), 4, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipStreamSynchronize(s));
+            return text_index_error(id, ki, pi - h_ooff[ki]);
+        }
+        n_out = h_ooff[n_texts];
+        if (n_out < 0 || n_out > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad packed length");
+        *needed = n_out;
+        if (n_out > cap) {
+            char msg[128];
+            std::snprintf(msg, sizeof msg, "bpe native: encode needs %lld values, the buffer holds %lld",
+                          (long long)n_out, (long long)cap);
+            return bpe_fail(BPE_ERR_ARG, msg);
+        }
+        if (dev) {
+            if (n_out) ENC_TRY(hipMemcpyAsync(vals_out, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToDevice, s));
+            ENC_TRY(hipMemcpyAsync(out_off, d_ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToDevice, s));
+            ENC_TRY(hipStreamSynchronize(s));
+        } else {
+            if (n_out) {
+                ENC_TRY(hipMemcpyAsync(vals_out, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
+                ENC_TRY(hipStreamSynchronize(s));
+            }
+            std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
+        }
+        E->st.texts_rank += n_texts;
+        E->st.tokens_in += (int64_t)T.h_st[TS_CHARS];
+        E->st.tokens_out += n_out;
+        T.st.chars += (int64_t)T.h_st[TS_CHARS];
+    }
+    T.st.texts += n_texts;
+    T.st.units_in += total;
+    T.st.values_out += n_out;
+    return BPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -825,6 +1181,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     if (E->d_steps) (void)hipFree(E->d_steps);
     if (E->d_buf) (void)hipFree(E->d_buf);
     if (E->h_buf) (void)hipHostFree(E->h_buf);
+    text_free(E);
     if (E->ev0) (void)hipEventDestroy(E->ev0);
     if (E->ev1) (void)hipEventDestroy(E->ev1);
     for (int i = 0; i < 2; ++i)
@@ -845,6 +1202,7 @@ int bpe_encoder_clear(bpe_encoder *E) {
     E->vocab = 0;
     table_rebuild(E, 10);
     E->dirty = true;
+    text_drop_index(E);
     return BPE_OK;
 }
 
@@ -874,6 +1232,7 @@ int bpe_encoder_add_merges(bpe_encoder *E, const int32_t *abc, int64_t n) {
     }
     if (rehash) table_rebuild(E, bits);
     E->dirty = true;
+    text_drop_index(E);
     return BPE_OK;
 }
 
@@ -1066,6 +1425,91 @@ int bpe_encoder_reset_stats(bpe_encoder *E) {
     ENC_TRY(hipSetDevice(E->device));
     ENC_TRY(hipMemset(E->d_steps, 0, 64));
     E->st = bpe_encoder_stats{};
+    return BPE_OK;
+}
+
+int bpe_encoder_set_chars(bpe_encoder *E, const uint32_t *code_points, const int32_t *ids, int64_t n) {
+    if (!E || n < 0 || (n && (!code_points || !ids)))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad set_chars arguments");
+    bpe_text_state &T = E->txt;
+    if (n == 0) {
+        T.bmp.clear();
+        T.pairs.clear();
+        T.has_chars = false;
+        T.chars_dirty = false;
+        return BPE_OK;
+    }
+    // built aside: a failed call changes nothing
+    std::vector<uint16_t> bmp(65536, CHAR_UNKNOWN);
+    int64_t n_pairs = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (code_points[i] > 0x10FFFFu) return bpe_fail(BPE_ERR_ARG, "bpe native: code point above U+10FFFF");
+        if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB)
+            return bpe_fail(BPE_ERR_VOCAB, "bpe native: char token id out of range");
+        n_pairs += code_points[i] > 0xFFFFu;
+    }
+    uint32_t bits = 4;
+    while (((int64_t)1 << bits) < 2 * n_pairs) ++bits;
+    std::vector<uint2> pairs((size_t)1 << bits, make_uint2(PAIR_EMPTY, 0u));
+    const uint32_t mask = (1u << bits) - 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t cp = code_points[i];
+        if (cp <= 0xFFFFu) {
+            if (bmp[cp] != CHAR_UNKNOWN) return bpe_fail(BPE_ERR_ARG, "bpe native: duplicate code point");
+            bmp[cp] = (uint16_t)ids[i];
+        } else {
+            uint32_t h = pair_home(cp, 32 - bits);
+            while (pairs[h].x != PAIR_EMPTY) {
+                if (pairs[h].x == cp) return bpe_fail(BPE_ERR_ARG, "bpe native: duplicate code point");
+                h = (h + 1) & mask;
+            }
+            pairs[h] = make_uint2(cp, (uint32_t)ids[i]);
+        }
+    }
+    T.bmp.swap(bmp);
+    T.pairs.swap(pairs);
+    T.pair_bits = bits;
+    T.has_chars = true;
+    T.chars_dirty = true;
+    return BPE_OK;
+}
+
+int bpe_encoder_set_vector_index(bpe_encoder *E, const int32_t *to_vector_index, int32_t n) {
+    if (!E || n < 0 || (n && !to_vector_index))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad set_vector_index arguments");
+    if (n == 0 && !to_vector_index) {
+        text_drop_index(E);
+        return BPE_OK;
+    }
+    E->txt.tvi.assign(to_vector_index, to_vector_index + n);
+    E->txt.has_tvi = true;
+    E->txt.tvi_dirty = true;
+    return BPE_OK;
+}
+
+int bpe_encode_text_batch(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                          int32_t *vals_out, int64_t vals_cap, int64_t *out_off) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int64_t needed = 0;
+    return text_run(E, kind, units, off, n_texts, vals_out, vals_cap, out_off, false, &needed);
+}
+
+int bpe_encode_text_batch_device(bpe_encoder *E, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                 int64_t n_texts, int32_t *d_vals_out, int64_t vals_cap, int64_t *d_out_off,
+                                 int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    return text_run(E, kind, d_units, d_off, n_texts, d_vals_out, vals_cap, d_out_off, true, needed);
+}
+
+int bpe_encoder_get_text_stats(bpe_encoder *E, bpe_text_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->txt.st;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_text_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->txt.st = bpe_text_stats{};
     return BPE_OK;
 }
 

@@ -59,6 +59,12 @@ export declare class BPETokenizer {
    * the `unknown vector index: V` error included.  Needs a HIP device.
    */
   decodeVectorBatch(vectors: number[][]): string[]
+  /**
+   * encodeToVector for many texts at once on the GPU: equals `texts.map(t => this.encodeToVector(t))`,
+   * the `unknown token, char: ...` and `unknown token index: N` errors included.  Without a HIP
+   * device (or with BPE_ENCODE_DEVICE=0) that map runs in JS.
+   */
+  encodeToVectorBatch(texts: string[]): number[][]
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

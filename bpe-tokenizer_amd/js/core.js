@@ -13,7 +13,8 @@
  * There is no CPU fallback: the first corpus operation creates the HIP engine and throws
  * `bpe native: ...` when no device is available.  Methods that never touch the corpus
  * (fromJSON, toJSON, encode*, decode*, compactVectorIndex) work without a GPU; decodeVectorBatch,
- * an addition to the reference's surface, decodes on the device and needs one.
+ * an addition to the reference's surface, decodes on the device and needs one; encodeToVectorBatch,
+ * the addition opposite it, encodes on the device and maps encodeToVector in JS without one.
  *
  * Node 12 compatible (no `?.`, `??`, `String.prototype.replaceAll`).
  */
@@ -23,6 +24,7 @@ const {
   minWeightArg,
   encodeIdsMaybeOnDevice,
   decodeVectorsOnDevice,
+  encodeTextsMaybeOnDevice,
   idsToCode,
 } = require('./native')
 
@@ -455,6 +457,26 @@ class BPETokenizer {
     }
 
     return vector
+  }
+
+  /**
+   * @description encodeToVector for many texts at once on the GPU (bpe_encode_text_batch: chars to
+   * token ids, the merges, and the vector index, all on the device): equals
+   * `texts.map(t => this.encodeToVector(t))`, the same errors included (the first failing text's;
+   * inside a text `unknown token, char: ...` before `unknown token index: N`).  The encoder holds
+   * the merges, the char table and the index on the device and follows them (native.js
+   * syncTextEncoder).  It follows encodeToCode's routing: when the device cannot take the call (no
+   * addon, no HIP device, a token id at or above 55 296) the map runs in JS; BPE_ENCODE_DEVICE=1
+   * lets the device's errors through, =0 keeps every call in JS.
+   */
+  encodeToVectorBatch(texts) {
+    if (texts.length === 0) return []
+    if (!this.to_vector_index) this.compactVectorIndex()
+    if (texts.every(t => typeof t === 'string')) {
+      let out = encodeTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, texts)
+      if (out) return out
+    }
+    return texts.map(t => this.encodeToVector(t))
   }
 
   /** core.ts:447-453 */

@@ -18,6 +18,13 @@ function loadNativeDecode() {
   return nativeDecode
 }
 
+// the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
+let nativeText = null
+function loadNativeText() {
+  if (!nativeText) nativeText = require(path.join(__dirname, '..', 'addon', 'bpe_text_napi.node'))
+  return nativeText
+}
+
 /**
  * encodeToCode (core.ts:392-409) runs on the GPU (bpe_encode_batch: the merge-rank encoder for
  * texts up to ENCODE_LDS_TOKENS tokens, apply-only replay passes above) when a per-call cost model
@@ -183,6 +190,141 @@ function decodeVectorsOnDevice(owner, vals, off) {
   return loadNativeDecode().decodeBatch(syncDecoder(owner), vals, off, 1)
 }
 
+/**
+ * The owner's device text encoder (bpe_encode_text_batch: chars -> ids -> merges -> vector indices,
+ * all on the device), following the owner's tables: the merges appended to `list` since the last
+ * call are appended (a replaced or shortened list rebuilds them), the char table is sent again when
+ * `owner.char_to_token` has gained keys or been replaced (keys that are not exactly one code point
+ * are skipped: `for (let char of content)` never produces them), and the index when
+ * `owner.to_vector_index` is a new array (compactVectorIndex makes one each time; holes go as -1).
+ * The owner keeps the handle in non-enumerable fields.
+ */
+function syncTextEncoder(owner, list, tripleOf) {
+  let n = loadNativeText()
+  list = list || owner.merge_tokens
+  tripleOf = tripleOf || (m => [m[0].index, m[1].index, m[2].index])
+  if (!owner._tenc) {
+    for (let k of ['_tenc', '_tenc_list', '_tenc_n', '_tenc_last', '_tenc_chars', '_tenc_nchars', '_tenc_index'])
+      if (!Object.prototype.hasOwnProperty.call(owner, k))
+        Object.defineProperty(owner, k, { value: null, writable: true, enumerable: false })
+    owner._tenc = n.createTextEncoder(0)
+    owner._tenc_list = null
+  }
+  let have = owner._tenc_n || 0
+  if (owner._tenc_list !== list || have > list.length || (have && list[have - 1] !== owner._tenc_last)) {
+    n.textEncoderClear(owner._tenc)
+    owner._tenc_list = list
+    owner._tenc_index = null // (clear drops the encoder's index, core.ts:348)
+    owner._tenc_n = have = 0
+  }
+  if (have < list.length) {
+    let k = list.length - have
+    let abc = new Int32Array(3 * k)
+    for (let i = 0; i < k; i++) {
+      let t = tripleOf(list[have + i])
+      abc[3 * i] = t[0]
+      abc[3 * i + 1] = t[1]
+      abc[3 * i + 2] = t[2]
+    }
+    owner._tenc_n = 0 // (a failed append leaves the merges to be rebuilt)
+    owner._tenc_list = null
+    n.textEncoderAddMerges(owner._tenc, abc)
+    owner._tenc_list = list
+    owner._tenc_index = null // (new merges drop the encoder's index)
+  }
+  owner._tenc_n = list.length
+  owner._tenc_last = list.length ? list[list.length - 1] : null
+  let table = owner.char_to_token
+  let keys = Object.keys(table)
+  if (owner._tenc_chars !== table || owner._tenc_nchars !== keys.length) {
+    let cps = new Uint32Array(keys.length)
+    let ids = new Int32Array(keys.length)
+    let m = 0
+    for (let key of keys) {
+      let cp = key.codePointAt(0)
+      if (cp === undefined || key.length !== (cp > 0xffff ? 2 : 1)) continue
+      cps[m] = cp
+      ids[m++] = table[key].index
+    }
+    owner._tenc_chars = null
+    n.textEncoderSetChars(owner._tenc, cps.subarray(0, m), ids.subarray(0, m))
+    owner._tenc_chars = table
+    owner._tenc_nchars = keys.length
+  }
+  if (owner._tenc_index !== owner.to_vector_index) {
+    let index = null
+    if (owner.to_vector_index) {
+      index = new Int32Array(owner.to_vector_index.length).fill(-1)
+      owner.to_vector_index.forEach((v, i) => {
+        index[i] = v
+      })
+    }
+    n.textEncoderSetVectorIndex(owner._tenc, index)
+    owner._tenc_index = owner.to_vector_index
+  }
+  return owner._tenc
+}
+
+/** texts (strings) as one Uint16Array of UTF-16 units and a Float64Array of offsets */
+function textsToUnits(texts) {
+  let off = new Float64Array(texts.length + 1)
+  for (let k = 0; k < texts.length; k++) off[k + 1] = off[k] + texts[k].length
+  // (one conversion for the batch; 'utf16le' writes the code units as they are, lone surrogates too)
+  let buf = Buffer.from(texts.join(''), 'utf16le')
+  if (buf.byteOffset & 1) buf = Buffer.from(new Uint8Array(buf))
+  return [new Uint16Array(buf.buffer, buf.byteOffset, buf.length >> 1), off]
+}
+
+/**
+ * A batch of texts through the owner's device text encoder -> array of vectors, or null when the
+ * device cannot take the call (the caller then maps encodeToVector in JS): BPE_ENCODE_DEVICE=0, no
+ * addon or no HIP device (remembered for the owner's lifetime), or a token id the device does not
+ * hold (>= BPE_MAX_VOCAB: remembered while the owner keeps that merge list and char table).  With
+ * BPE_ENCODE_DEVICE=1 the device's errors go through.  The reference's own errors (an unknown char,
+ * an unknown token index) are thrown with its strings either way.
+ */
+const CAPABILITY_TEXT_TABLE = /merge token id out of range|more merges than token ids|char token id out of range/
+function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
+  if (ENCODE_DEVICE === '0') return null
+  if (
+    ENCODE_DEVICE !== '1' &&
+    (owner._tenc_failed === true || (owner._tenc_failed && owner._tenc_failed === list))
+  )
+    return null
+  let res
+  try {
+    let enc = syncTextEncoder(owner, list, tripleOf)
+    let [units, off] = textsToUnits(texts)
+    res = loadNativeText().encodeTextBatch(enc, units, off, 1)
+  } catch (e) {
+    let msg = String((e && e.message) || e)
+    let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
+    if (m) throw new Error('unknown token, char: ' + JSON.stringify(String.fromCodePoint(parseInt(m[1], 16))))
+    m = /^unknown token index: (-?\d+) \(text \d+, position \d+\)$/.exec(msg)
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    if (ENCODE_DEVICE === '1') throw e
+    if (!Object.prototype.hasOwnProperty.call(owner, '_tenc_failed'))
+      Object.defineProperty(owner, '_tenc_failed', { value: null, writable: true, enumerable: false })
+    if (!owner._tenc) {
+      owner._tenc_failed = true
+    } else {
+      // (the encoder may hold part of the tables: the next call loads them again from the start)
+      owner._tenc_list = null
+      owner._tenc_chars = null
+      if (CAPABILITY_TEXT_TABLE.test(msg)) owner._tenc_failed = list
+      else if (!warned) {
+        warned = true
+        process.emitWarning('bpe device text encoder failed, this call encodes in JS: ' + msg)
+      }
+    }
+    return null
+  }
+  let [vals, off] = res
+  let out = new Array(texts.length)
+  for (let k = 0; k < texts.length; k++) out[k] = Array.from(vals.subarray(off[k], off[k + 1]))
+  return out
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -217,6 +359,7 @@ function minWeightArg(options) {
 module.exports = {
   loadNative,
   loadNativeDecode,
+  loadNativeText,
   maxLengthArg,
   minWeightArg,
   encodeOnDevice,
@@ -224,5 +367,7 @@ module.exports = {
   encodeIdsMaybeOnDevice,
   syncDecoder,
   decodeVectorsOnDevice,
+  syncTextEncoder,
+  encodeTextsMaybeOnDevice,
   idsToCode,
 }

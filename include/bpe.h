@@ -394,6 +394,70 @@ int bpe_encode_batch(bpe_encoder *enc, const int32_t *ids, const int64_t *off, i
 int bpe_encoder_get_stats(bpe_encoder *enc, bpe_encoder_stats *out);
 int bpe_encoder_reset_stats(bpe_encoder *enc);
 
+/* ---- encoding from text ------------------------------------------------------------------------
+ * encodeToVector (core.ts:392-445) for a batch of UTF-16 texts, all three of its stages on the
+ * device: chars -> token ids (`for (let char of content)` + char_to_token, core.ts:396-402), the
+ * merges (bpe_encode_batch's kernels and routes), and ids -> vector indices (to_vector_index,
+ * core.ts:434-444).  A unit continues the char before it when it is a low surrogate (0xDC00-0xDFFF),
+ * not its text's first unit, and the unit before it is a high surrogate (0xD800-0xDBFF); every
+ * other unit starts a char.  A char's key is its code point; a lone surrogate's its unit value.
+ *
+ * bpe_encoder_set_chars replaces the whole char table (char_to_token): n (code point, id) entries;
+ * n == 0 drops it.  A code point above 0x10FFFF or a duplicate gives BPE_ERR_ARG, an id outside
+ * [0, BPE_MAX_VOCAB) BPE_ERR_VOCAB; a failed call changes nothing.  bpe_encoder_clear keeps the
+ * table (it drops merges).
+ * bpe_encoder_set_vector_index takes to_vector_index of compactVectorIndex (core.ts:222-241): one
+ * entry per token id, -1 for a hole (a token of weight 0); ids at or past n are holes.  NULL with
+ * n == 0 drops the index; bpe_encoder_add_merges and bpe_encoder_clear drop it too
+ * (invalidateVectorIndex, core.ts:348).
+ *
+ * bpe_encode_text_batch: text k is units[off[k] .. off[k+1]); off[0] need not be 0 and units before
+ * it are never read; offsets must not decrease or be negative (BPE_ERR_ARG); n_texts == 0 is fine.
+ * It writes the texts' values (token ids, or vector indices) back to back into vals_out and
+ * n_texts + 1 offsets into out_off (out_off[0] = 0).  A text never grows, so vals_cap >=
+ * off[n_texts] - off[0] always suffices; a smaller cap that the result does not fit gives
+ * BPE_ERR_ARG with nothing written.  BPE_ENCODE_VECTORS without an index, and a call with at least
+ * one unit without a char table, give BPE_ERR_STATE.
+ * A char that is not in the table, or (vectors) a resulting id that is a hole, fails the whole
+ * call with BPE_ERR_VOCAB; nothing is written to either output, the encoder stays usable, and the
+ * message is
+ *   unknown token, char: U+XXXX (text K, unit I)         (I: the char's first unit in its text)
+ *   unknown token index: N (text K, position I)          (I: the position in the encoded text)
+ * for the error the reference's `texts.map(t => encodeToVector(t))` throws: the first failing
+ * text's, and inside one text the char's (core.ts:398-401 runs before any merge).
+ * Launch shapes and the replay route are chosen by a text's unit count (its char count is at most
+ * that); texts longer than BPE_ENCODE_LDS_TOKENS units and lists the greedy cannot take make the
+ * call assemble on the host, as bpe_encode_batch does.  Output is identical either way.
+ * bpe_encode_text_batch_device is the same pipeline on buffers already on the encoder's device
+ * (any 2-byte aligned unit pointer); values and offsets stay there; it reads the offsets back
+ * (8 B per text) for the launch lists, runs on the encoder's stream and synchronises before
+ * returning.  *needed (a host int64) receives the number of values.
+ * The front end works on tiles of BPE_TEXT_TILE units and scans BPE_TEXT_SCAN_ROUND tile counts per
+ * round (csrc/bpe_text.hip.h; exported for the tests). */
+#define BPE_TEXT_TILE 2048
+#define BPE_TEXT_SCAN_ROUND 2048
+#define BPE_ENCODE_IDS 0       /* values out are token ids (encodeToCode's tokens) */
+#define BPE_ENCODE_VECTORS 1   /* values out are vector indices (encodeToVector) */
+typedef struct {
+    int64_t calls;            /* text calls */
+    int64_t texts;            /* texts of the calls that succeeded */
+    int64_t units_in;         /* ... their UTF-16 units */
+    int64_t chars;            /* ... their chars (token ids before the merges) */
+    int64_t values_out;       /* ... the values written */
+    double front_ms;          /* HIP-event time of the front-end kernels (units -> ids) */
+    double back_ms;           /* ... of the back-end kernels (pack, vector index); the merge-rank
+                                 kernels' time stays in bpe_encoder_stats.kernel_ms */
+} bpe_text_stats;
+int bpe_encoder_set_chars(bpe_encoder *enc, const uint32_t *code_points, const int32_t *ids, int64_t n);
+int bpe_encoder_set_vector_index(bpe_encoder *enc, const int32_t *to_vector_index, int32_t n);
+int bpe_encode_text_batch(bpe_encoder *enc, int kind, const uint16_t *units, const int64_t *off,
+                          int64_t n_texts, int32_t *vals_out, int64_t vals_cap, int64_t *out_off);
+int bpe_encode_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                 int64_t n_texts, int32_t *d_vals_out, int64_t vals_cap,
+                                 int64_t *d_out_off, int64_t *needed);
+int bpe_encoder_get_text_stats(bpe_encoder *enc, bpe_text_stats *out);
+int bpe_encoder_reset_text_stats(bpe_encoder *enc);
+
 /* ---- decoding ----------------------------------------------------------------------------------
  * decodeVector / decodeTokens (core.ts:447-471) for a batch of texts: `content += token.chars` for
  * every value of a text (core.ts:462-468), the values being vector indices (mapped through
