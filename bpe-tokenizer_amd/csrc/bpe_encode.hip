@@ -379,12 +379,19 @@ k_scan_lens(const int32_t *__restrict__ len, int64_t n, int64_t *__restrict__ oo
     }
 }
 
+// The pack kernels' per-value map: the id itself here, its vector index in bpe_text.hip.h (VecMap).
+// `pos` is the value's flat output position.
+struct MapId {
+    __device__ __forceinline__ int32_t operator()(int32_t id, unsigned long long) const { return id; }
+};
+
 // Both in one workgroup, for a call of at most 1024 texts (the one-text-per-call shape): the scan,
 // then one wave per text.
+template <class Map>
 __global__ void __launch_bounds__(1024)
 k_pack_small(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off,
              const int32_t *__restrict__ len, int n, int64_t *__restrict__ ooff,
-             const unsigned long long *__restrict__ err, int32_t *__restrict__ dst) {
+             const unsigned long long *__restrict__ err, int32_t *__restrict__ dst, Map map) {
     __shared__ int scn[16];
     __shared__ int start[1025];
     const int v = (int)threadIdx.x < n ? len[threadIdx.x] : 0;
@@ -401,22 +408,24 @@ k_pack_small(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off
     __syncthreads();
     for (int t = threadIdx.x >> 6; t < n; t += 16) {
         const int32_t *s = src + in_off[t];
-        int32_t *d = dst + start[t];
+        const int o = start[t];
+        int32_t *d = dst + o;
         const int l = len[t];
-        for (int i = threadIdx.x & 63; i < l; i += 64) d[i] = s[i];
+        for (int i = threadIdx.x & 63; i < l; i += 64) d[i] = map(s[i], (unsigned long long)(o + i));
     }
 }
 
+template <class Map>
 __global__ void __launch_bounds__(256)
 k_gather(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off,
          const int32_t *__restrict__ len, const int64_t *__restrict__ ooff, int64_t n,
-         int32_t *__restrict__ dst) {
+         int32_t *__restrict__ dst, Map map) {
     const int64_t text = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (text >= n) return;
     const int32_t *s = src + in_off[text];
-    int32_t *d = dst + ooff[text];
+    const int64_t o = ooff[text];
     const int l = len[text];
-    for (int i = threadIdx.x & 63; i < l; i += 64) d[i] = s[i];
+    for (int i = threadIdx.x & 63; i < l; i += 64) dst[o + i] = map(s[i], (unsigned long long)(o + i));
 }
 
 // shorter texts take the HBM table even in the few-texts form (the LDS copy costs more than its
@@ -597,12 +606,11 @@ int grow_stage(bpe_encoder *E, size_t h_bytes, size_t d_bytes) {
         ENC_TRY(hipHostMalloc((void **)&E->h_buf, n, hipHostMallocDefault));
         E->h_cap = n;
     }
-    const size_t bytes = d_bytes;
-    if (E->d_cap < bytes) {
+    if (E->d_cap < d_bytes) {
         if (E->d_buf) (void)hipFree(E->d_buf);
         E->d_buf = nullptr;
         E->d_cap = 0;
-        const size_t n = bytes * 3 / 2 + 4096;
+        const size_t n = d_bytes * 3 / 2 + 4096;
         ENC_TRY(hipMalloc((void **)&E->d_buf, n));
         E->d_cap = n;
     }
@@ -620,7 +628,158 @@ void release_stage(bpe_encoder *E) {
     }
 }
 
+struct Release {
+    bpe_encoder *e;
+    ~Release() { release_stage(e); }
+};
+
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// ---- the pieces every form of the encoder is made of ----------------------------
+
+// The device staging of one call, or of one slot of a grouped call, sized for n texts of `total`
+// ids together:
+//     [ooff (n+2) | ids, then the packed output | off (n+2) | which | out | len]
+// err, the bad-id counter of k_encode, is word n + 1 of `off`: the id forms zero it through the
+// upload of the offsets (rel_offsets), the text form through a memset, because there k_txt_map
+// writes the offsets.  The pack kernels copy it to ooff[n + 1], so one copy brings the packed
+// offsets and it back (fetch_ooff).  The order [ooff | ids | off | which] is what lets a small id
+// call move [ids | off | which] up and [ooff | packed ids] down in one copy each through a pinned
+// mirror of the same sizes.  place() returns the end: a form's own regions go there.
+struct Stage {
+    size_t b_off, b_ids, b_which;   // region sizes in bytes; len is sized like which
+    int64_t *ooff = nullptr, *off = nullptr;
+    int32_t *ids = nullptr, *which = nullptr, *out = nullptr, *len = nullptr;
+    unsigned long long *err = nullptr;
+    Stage(int64_t n, int64_t total)
+        : b_off(align16((size_t)(n + 2) * 8)), b_ids(align16((size_t)std::max<int64_t>(total, 1) * 4)),
+          b_which(align16((size_t)n * 4)) {}
+    size_t bytes() const { return 2 * (b_off + b_ids + b_which); }
+    // at `d`, for a call of n texts (at most the n it was sized for)
+    char *place(char *d, int64_t n) {
+        ooff = reinterpret_cast<int64_t *>(d);
+        ids = reinterpret_cast<int32_t *>(d += b_off);
+        off = reinterpret_cast<int64_t *>(d += b_ids);
+        which = reinterpret_cast<int32_t *>(d += b_off);
+        out = reinterpret_cast<int32_t *>(d += b_which);
+        len = reinterpret_cast<int32_t *>(d += b_ids);
+        err = reinterpret_cast<unsigned long long *>(off + n + 1);
+        return d + b_which;
+    }
+};
+
+// the host copy of Stage::off: offsets relative to the first text's, and the zeroed err word
+void rel_offsets(int64_t *h_off, const int64_t *off, int64_t n) {
+    for (int64_t k = 0; k <= n; ++k) h_off[k] = off[k] - off[0];
+    h_off[n + 1] = 0;
+}
+
+// The texts of a call by launch shape (the smallest that holds the text), in the order of `which`.
+struct ShapeLists {
+    std::vector<int32_t> of[N_SHAPES];
+    int64_t n = 0;   // texts listed
+};
+
+// Can k_encode take a text of l tokens?  Not one longer than an LDS buffer, and none under a merge
+// list the greedy would get wrong: those are replayed.
+bool kernel_takes(const bpe_encoder *E, int64_t l) { return E->greedy_ok && l <= CAP_MAX; }
+
+// Text k of [0, n) by its length off[k + 1] - off[k] (an upper bound will do): into its shape's
+// list, or into `replay`.  What a replayed text means for the call is the form's decision.
+void classify(const bpe_encoder *E, const int64_t *off, int64_t n, ShapeLists &lists,
+              std::vector<int64_t> &replay) {
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t l = off[k + 1] - off[k];
+        if (!kernel_takes(E, l)) {
+            replay.push_back(k);
+        } else {
+            int i = 0;
+            while (shape_cap(i) < l) ++i;
+            lists.of[i].push_back((int32_t)k);
+            ++lists.n;
+        }
+    }
+}
+
+void fill_which(const ShapeLists &lists, int32_t *h_which) {
+    for (auto &v : lists.of) {
+        std::memcpy(h_which, v.data(), v.size() * 4);
+        h_which += v.size();
+    }
+}
+
+// k_encode over every listed text (L.which uploaded from fill_which), one launch per shape in use,
+// between the events `before` and `after` (either may be null).  may_few: a call of few texts gives
+// each a CU to itself, and the table is read from LDS where it fits beside the text.
+int launch_lists(bpe_encoder *E, const ShapeLists &lists, bool may_few, const Stage &L, hipEvent_t before,
+                 hipEvent_t after) {
+    const size_t tab = (size_t)E->lt.words * 4;
+    const bool few = may_few && (size_t)lists.n <= LATENCY_TEXTS;
+    if (before) ENC_TRY(hipEventRecord(before, E->stream));
+    size_t at = 0;
+    for (int i = 0; i < N_SHAPES; ++i) {
+        if (lists.of[i].empty()) continue;
+        const bool tab_lds = few && shape_cap(i) > LDS_TAB_MIN_TOKENS && shape_lds(i) + tab <= LDS_BYTES;
+        launch_shape(i, E, (unsigned)lists.of[i].size(), tab_lds, L.ids, L.off, L.which + at, L.out, L.len, L.err);
+        at += lists.of[i].size();
+    }
+    ENC_TRY(hipGetLastError());
+    if (after) ENC_TRY(hipEventRecord(after, E->stream));
+    return BPE_OK;
+}
+
+// The call's output packed on the device, into the ids region (read by k_encode, free now), every
+// value through `map` (MapId, or the text form's VecMap): the scan of the lengths, then the gather.
+template <class Map>
+int pack_gather(hipStream_t s, const Stage &L, int64_t n, Map map) {
+    k_scan_lens<<<1, 1024, 0, s>>>(L.len, n, L.ooff, L.err);
+    k_gather<<<(unsigned)((n + 3) / 4), 256, 0, s>>>(L.out, L.off, L.len, L.ooff, n, L.ids, map);
+    ENC_TRY(hipGetLastError());
+    return BPE_OK;
+}
+
+// ... or, for a call one workgroup can copy, both in one launch
+template <class Map>
+int pack(hipStream_t s, const Stage &L, int64_t n, int64_t total, Map map) {
+    if (n > 1024 || total > (1 << 18)) return pack_gather(s, L, n, map);
+    k_pack_small<<<1, 1024, 0, s>>>(L.out, L.off, L.len, (int)n, L.ooff, L.err, L.ids, map);
+    ENC_TRY(hipGetLastError());
+    return BPE_OK;
+}
+
+// [ooff (n+1) | bad-id word] of a packed call into the pinned h_ooff, waited for; a count in the
+// bad-id word fails the call with the form's own error.  more: bytes of the region after ooff (the
+// packed ids) that come with it, for a mirror laid out like the stage and a stage sized for n.
+int fetch_ooff(hipStream_t s, const Stage &L, int64_t *h_ooff, int64_t n, size_t more, int bad_rc,
+               const char *bad_msg) {
+    ENC_TRY(hipMemcpyAsync(h_ooff, L.ooff, align16((size_t)(n + 2) * 8) + more, hipMemcpyDeviceToHost, s));
+    ENC_TRY(hipStreamSynchronize(s));
+    if (h_ooff[n + 1]) return bpe_fail(bad_rc, bad_msg);
+    return BPE_OK;
+}
+
+// the packed length of n texts of `total` ids in: checked, and against the caller's capacity
+// where there is one (cap >= 0)
+int packed_length(const int64_t *h_ooff, int64_t n, int64_t total, int64_t cap, int64_t *n_out) {
+    *n_out = h_ooff[n];
+    if (*n_out < 0 || *n_out > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad packed length");
+    if (cap >= 0 && *n_out > cap) {
+        char msg[128];
+        std::snprintf(msg, sizeof msg, "bpe native: encode needs %lld values, the buffer holds %lld",
+                      (long long)*n_out, (long long)cap);
+        return bpe_fail(BPE_ERR_ARG, msg);
+    }
+    return BPE_OK;
+}
+
+// the packed values to the caller's host or device buffer (and everything before it on s done)
+int copy_packed(hipStream_t s, int32_t *dst, const int32_t *src, int64_t n_out, hipMemcpyKind kind) {
+    if (n_out) ENC_TRY(hipMemcpyAsync(dst, src, (size_t)n_out * 4, kind, s));
+    ENC_TRY(hipStreamSynchronize(s));
+    return BPE_OK;
+}
+
+constexpr const char *BAD_ID = "bpe native: token id out of range in text";
 
 // the apply-pass route: every listed text as one sample of the scratch engine, all M merges
 // replayed over them (one streaming pass per merge), the results back into out at the texts'
@@ -670,7 +829,7 @@ int encode_replay(bpe_encoder *E, const int32_t *ids, const int64_t *off, const 
 constexpr int64_t GROUP_TOKENS = int64_t(1) << 23;
 
 int encode_groups_run(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n_texts,
-                      const std::vector<int32_t> &shape_of, int32_t *ids_out, int64_t *out_off) {
+                      int32_t *ids_out, int64_t *out_off) {
     // contiguous text ranges [g0, g1) of >= GROUP_TOKENS tokens (the last one whatever is left)
     // (few groups: each group's longest texts finish alone, so more groups cost kernel time)
     static const int64_t n_groups = [] {
@@ -689,12 +848,9 @@ int encode_groups_run(bpe_encoder *E, const int32_t *ids, const int64_t *off, in
         max_t = std::max(max_t, off[cut[g + 1]] - off[cut[g]]);
         max_n = std::max(max_n, cut[g + 1] - cut[g]);
     }
-    // per slot, device: [ooff (n+2) | ids | off (n+2) | which | out | len]; pinned: [ooff | off | which]
-    const size_t b_ids = align16((size_t)std::max<int64_t>(max_t, 1) * 4);
-    const size_t b_off = align16((size_t)(max_n + 2) * 8);
-    const size_t b_which = align16((size_t)max_n * 4);
-    const size_t slot_d = b_off + b_ids + b_off + b_which + b_ids + b_which;
-    const size_t slot_h = b_off + b_off + b_which;
+    // per slot, device: a Stage for the largest group; pinned: [ooff | off | which] of its sizes
+    Stage slot[2] = {Stage(max_n, max_t), Stage(max_n, max_t)};
+    const size_t slot_d = slot[0].bytes(), b_off = slot[0].b_off, slot_h = 2 * b_off + slot[0].b_which;
     int rc;
     if ((rc = grow_stage(E, 2 * slot_h, 2 * slot_d))) return rc;
     hipStream_t ks = E->stream, cs = E->cstream;
@@ -706,18 +862,13 @@ int encode_groups_run(bpe_encoder *E, const int32_t *ids, const int64_t *off, in
         const int sl = g & 1;
         const int64_t k0 = cut[g], n = cut[g + 1] - k0;
         int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf + sl * slot_h);
-        char *d = E->d_buf + sl * slot_d;
+        int64_t n_out = 0;
+        int rc;
         ENC_TRY(hipStreamWaitEvent(cs, E->g_k1[sl], 0));
-        ENC_TRY(hipMemcpyAsync(h_ooff, d, (size_t)(n + 2) * 8, hipMemcpyDeviceToHost, cs));
-        ENC_TRY(hipStreamSynchronize(cs));
-        if (h_ooff[n + 1]) return bpe_fail(BPE_ERR_VOCAB, "bpe native: token id out of range in text");
-        const int64_t n_out = h_ooff[n];
-        if (n_out < 0 || n_out > off[cut[g + 1]] - off[k0])
-            return bpe_fail(BPE_ERR_STATE, "bpe native: bad packed length");
-        if (n_out) {
-            ENC_TRY(hipMemcpyAsync(ids_out + base, d + b_off, (size_t)n_out * 4, hipMemcpyDeviceToHost, cs));
-            ENC_TRY(hipStreamSynchronize(cs));
-        }
+        if ((rc = fetch_ooff(cs, slot[sl], h_ooff, n, 0, BPE_ERR_VOCAB, BAD_ID)) ||
+            (rc = packed_length(h_ooff, n, off[cut[g + 1]] - off[k0], -1, &n_out)) ||
+            (rc = copy_packed(cs, ids_out + base, slot[sl].ids, n_out, hipMemcpyDeviceToHost)))
+            return rc;
         for (int64_t k = 1; k <= n; ++k) out_off[k0 + k] = base + h_ooff[k];
         base += n_out;
         float ms = 0;
@@ -729,40 +880,24 @@ int encode_groups_run(bpe_encoder *E, const int32_t *ids, const int64_t *off, in
     for (int g = 0; g < ng; ++g) {
         const int sl = g & 1;
         const int64_t k0 = cut[g], n = cut[g + 1] - k0, t0 = off[k0], tn = off[cut[g + 1]] - t0;
-        char *d = E->d_buf + sl * slot_d;
-        char *h = E->h_buf + sl * slot_h;
-        int64_t *d_ooff = reinterpret_cast<int64_t *>(d);
-        int32_t *d_ids = reinterpret_cast<int32_t *>(d + b_off);
-        int64_t *d_off = reinterpret_cast<int64_t *>(d + b_off + b_ids);
-        int32_t *d_which = reinterpret_cast<int32_t *>(d + b_off + b_ids + b_off);
-        int32_t *d_out = reinterpret_cast<int32_t *>(d + b_off + b_ids + b_off + b_which);
-        int32_t *d_len = reinterpret_cast<int32_t *>(d + b_off + 2 * b_ids + b_off + b_which);
-        unsigned long long *d_err = reinterpret_cast<unsigned long long *>(d_off + n + 1);
-        int64_t *h_off = reinterpret_cast<int64_t *>(h + b_off);
-        int32_t *h_which = reinterpret_cast<int32_t *>(h + b_off + b_off);
+        Stage &L = slot[sl];
+        L.place(E->d_buf + sl * slot_d, n);
+        int64_t *h_off = reinterpret_cast<int64_t *>(E->h_buf + sl * slot_h + b_off);
+        int32_t *h_which = reinterpret_cast<int32_t *>(E->h_buf + sl * slot_h + 2 * b_off);
         // (slot sl's pinned staging was last read by group g - 2's upload, complete by now: its
         // kernels, which waited for it, were waited for by finish(g - 2))
-        for (int64_t k = 0; k <= n; ++k) h_off[k] = off[k0 + k] - t0;
-        h_off[n + 1] = 0;
-        int64_t cnt[N_SHAPES] = {};
-        for (int64_t k = 0; k < n; ++k) ++cnt[shape_of[k0 + k]];
-        int64_t at[N_SHAPES];
-        for (int i = 0, a = 0; i < N_SHAPES; a += (int)cnt[i], ++i) at[i] = a;
-        int64_t fill[N_SHAPES];
-        std::memcpy(fill, at, sizeof fill);
-        for (int64_t k = 0; k < n; ++k) h_which[fill[shape_of[k0 + k]]++] = (int32_t)k;
-        ENC_TRY(hipMemcpyAsync(d_ids, ids + t0, (size_t)tn * 4, hipMemcpyHostToDevice, cs));
-        ENC_TRY(hipMemcpyAsync(d_off, h_off, b_off + (size_t)n * 4, hipMemcpyHostToDevice, cs));
+        rel_offsets(h_off, off + k0, n);
+        ShapeLists lists;
+        std::vector<int64_t> none;   // (the caller has seen that no text is replayed)
+        classify(E, off + k0, n, lists, none);
+        fill_which(lists, h_which);
+        ENC_TRY(hipMemcpyAsync(L.ids, ids + t0, (size_t)tn * 4, hipMemcpyHostToDevice, cs));
+        ENC_TRY(hipMemcpyAsync(L.off, h_off, b_off + (size_t)n * 4, hipMemcpyHostToDevice, cs));
         ENC_TRY(hipEventRecord(E->g_in[sl], cs));
         ENC_TRY(hipStreamWaitEvent(ks, E->g_in[sl], 0));
-        ENC_TRY(hipEventRecord(E->g_k0[sl], ks));
-        for (int i = 0; i < N_SHAPES; ++i)
-            if (cnt[i])
-                launch_shape(i, E, (unsigned)cnt[i], false, d_ids, d_off, d_which + at[i], d_out,
-                             d_len, d_err);
-        k_scan_lens<<<1, 1024, 0, ks>>>(d_len, n, d_ooff, d_err);
-        k_gather<<<(unsigned)((n + 3) / 4), 256, 0, ks>>>(d_out, d_off, d_len, d_ooff, n, d_ids);
-        ENC_TRY(hipGetLastError());
+        // (not few: a group of GROUP_TOKENS / 2 tokens or more is hundreds of texts)
+        if ((rc = launch_lists(E, lists, false, L, E->g_k0[sl], nullptr)) || (rc = pack_gather(ks, L, n, MapId{})))
+            return rc;
         ENC_TRY(hipEventRecord(E->g_k1[sl], ks));
         if (g > 0 && (rc = finish(g - 1))) return rc;
     }
@@ -774,16 +909,124 @@ int encode_groups_run(bpe_encoder *E, const int32_t *ids, const int64_t *off, in
 }
 
 int encode_groups(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n_texts,
-                  const std::vector<int32_t> &shape_of, int32_t *ids_out, int64_t *out_off) {
+                  int32_t *ids_out, int64_t *out_off) {
     // (nothing of an earlier call may still read the staging buffers; a refused call leaves
     // nothing in flight either)
     ENC_TRY(hipStreamSynchronize(E->stream));
-    const int rc = encode_groups_run(E, ids, off, n_texts, shape_of, ids_out, out_off);
+    const int rc = encode_groups_run(E, ids, off, n_texts, ids_out, out_off);
     // (every copy of the call is complete on success; a failed call drains both streams)
     (void)hipStreamSynchronize(E->cstream);
     (void)hipStreamSynchronize(E->stream);
     release_stage(E);
     return rc;
+}
+
+// The id form (bpe_encode_batch; the text form's replay route enters here too).  It may reallocate
+// d_buf and h_buf, and release a large h_buf on return: a caller with staging of its own there has
+// brought what it needs to the host first.
+int encode_ids(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n_texts, int32_t *ids_out,
+               int64_t *out_off) {
+    if (n_texts < 0 || (n_texts && (!off || !out_off)))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_batch arguments");
+    if (n_texts == 0) {
+        if (out_off) out_off[0] = 0;
+        return BPE_OK;
+    }
+    int64_t longest = 0;
+    for (int64_t k = 0; k < n_texts; ++k) {
+        if (off[k + 1] < off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+        longest = std::max(longest, off[k + 1] - off[k]);
+    }
+    const int64_t base = off[0], total = off[n_texts] - base;
+    if (total && (!ids || !ids_out)) return bpe_fail(BPE_ERR_ARG, "bpe native: null id buffer");
+    ENC_TRY(hipSetDevice(E->device));
+    E->st.calls++;
+    E->st.tokens_in += total;
+    int rc;
+    // a very large call with no text to replay: in groups, each classifying its own texts
+    if (total >= 2 * GROUP_TOKENS && kernel_takes(E, longest) && !getenv("BPE_ENCODE_ONE_GROUP")) {
+        if ((rc = upload_table(E))) return rc;
+        return encode_groups(E, ids, off, n_texts, ids_out, out_off);
+    }
+    // per text: the kernels, or the apply-pass route
+    ShapeLists lists;
+    std::vector<int64_t> replay;
+    classify(E, off, n_texts, lists, replay);
+    // (only the replay's host route checks ids on the host; the kernels count bad ids)
+    for (int64_t k : replay)
+        for (int64_t i = off[k]; i < off[k + 1]; ++i)
+            if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB) return bpe_fail(BPE_ERR_VOCAB, BAD_ID);
+    if ((rc = upload_table(E))) return rc;
+    // A small call's pinned buffer mirrors the stage's [ooff | ids | off | which]; a large call
+    // copies its ids straight from and to the caller's buffers (no host staging pass; a pageable
+    // copy costs tens of microseconds of fixed overhead, which a small call cannot hide) and pins
+    // only [ooff | off | which].
+    Stage L(n_texts, total);
+    const bool small = (size_t)total * 4 <= SMALL_CALL_BYTES;
+    const size_t h_ids_bytes = small ? L.b_ids : 0;
+    if ((rc = grow_stage(E, 2 * L.b_off + h_ids_bytes + L.b_which, L.bytes()))) return rc;
+    Release release{E};
+    L.place(E->d_buf, n_texts);
+    char *h = E->h_buf;
+    int64_t *h_ooff = reinterpret_cast<int64_t *>(h);
+    int32_t *h_ids = reinterpret_cast<int32_t *>(h + L.b_off);   // (small calls only)
+    int64_t *h_off = reinterpret_cast<int64_t *>(h + L.b_off + h_ids_bytes);
+    int32_t *h_which = reinterpret_cast<int32_t *>(h + L.b_off + h_ids_bytes + L.b_off);
+    rel_offsets(h_off, off, n_texts);
+    fill_which(lists, h_which);
+    if (small) {
+        if (total) std::memcpy(h_ids, ids + base, (size_t)total * 4);
+        ENC_TRY(hipMemcpyAsync(L.ids, h_ids, L.b_ids + L.b_off + (size_t)lists.n * 4, hipMemcpyHostToDevice,
+                               E->stream));
+    } else {
+        ENC_TRY(hipMemcpyAsync(L.ids, ids + base, (size_t)total * 4, hipMemcpyHostToDevice, E->stream));
+        ENC_TRY(hipMemcpyAsync(L.off, h_off, L.b_off + (size_t)lists.n * 4, hipMemcpyHostToDevice, E->stream));
+    }
+    // replay texts keep length 0 on the device; they are written on the host below
+    if (!replay.empty()) ENC_TRY(hipMemsetAsync(L.len, 0, (size_t)n_texts * 4, E->stream));
+    if ((rc = launch_lists(E, lists, true, L, E->ev0, E->ev1))) return rc;
+    if (replay.empty()) {
+        // [ooff | packed ids] in one copy through the mirror, or the offsets first and then only
+        // the packed ids (merges shrink a batch: 5x on zipf words)
+        int64_t n_out = 0;
+        if ((rc = pack(E->stream, L, n_texts, total, MapId{})) ||
+            (rc = fetch_ooff(E->stream, L, h_ooff, n_texts, small ? (size_t)total * 4 : 0, BPE_ERR_VOCAB, BAD_ID)) ||
+            (rc = packed_length(h_ooff, n_texts, total, -1, &n_out)))
+            return rc;
+        if (small) {
+            if (n_out) std::memcpy(ids_out, h_ids, (size_t)n_out * 4);
+        } else if ((rc = copy_packed(E->stream, ids_out, L.ids, n_out, hipMemcpyDeviceToHost)))
+            return rc;
+        std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
+    } else {
+        // host assembly: the kernels' texts come back at their input offsets, the replayed ones
+        // from the scratch engine (into the same host buffer: after the copies have landed)
+        std::vector<int64_t> len((size_t)n_texts, 0);
+        std::vector<int32_t> out((size_t)std::max<int64_t>(total, 1));
+        std::vector<int32_t> lens((size_t)n_texts);
+        unsigned long long err = 0;
+        ENC_TRY(hipMemcpyAsync(out.data(), L.out, (size_t)total * 4, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipMemcpyAsync(lens.data(), L.len, (size_t)n_texts * 4, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipMemcpyAsync(&err, L.err, 8, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipStreamSynchronize(E->stream));
+        if (err) return bpe_fail(BPE_ERR_VOCAB, BAD_ID);
+        if ((rc = encode_replay(E, ids, off, replay, out.data(), len.data()))) return rc;
+        for (auto &v : lists.of)
+            for (int32_t k : v) len[k] = lens[k];
+        int64_t o = 0;
+        out_off[0] = 0;
+        for (int64_t k = 0; k < n_texts; ++k) {
+            if (len[k]) std::memcpy(ids_out + o, out.data() + (off[k] - base), (size_t)len[k] * 4);
+            o += len[k];
+            out_off[k + 1] = o;
+        }
+    }
+    float ms = 0;
+    ENC_TRY(hipEventElapsedTime(&ms, E->ev0, E->ev1));
+    E->st.kernel_ms += ms;
+    E->st.texts_rank += lists.n;
+    E->st.tokens_out += out_off[n_texts];
+    return BPE_OK;
 }
 
 // ---- the text form (bpe_encode_text_batch): bpe_text.hip.h's kernels around k_encode -------------
@@ -896,51 +1139,30 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     if ((rc = text_upload(E)) || (rc = upload_table(E))) return rc;
     // launch shape of every text by its unit count (its chars are at most that many), or the
     // apply-pass route for the whole call
-    std::vector<int32_t> lists[N_SHAPES];
-    bool replay = !E->greedy_ok;
-    for (int64_t k = 0; k < n_texts && !replay; ++k) {
-        const int64_t l = h_off[k + 1] - h_off[k];
-        if (l > CAP_MAX) {
-            replay = true;
-        } else {
-            int i = 0;
-            while (shape_cap(i) < l) ++i;
-            lists[i].push_back((int32_t)k);
-        }
-    }
+    ShapeLists lists;
+    std::vector<int64_t> no_kernel;
+    classify(E, h_off, n_texts, lists, no_kernel);
+    const bool replay = !no_kernel.empty();
     const int mis = dev ? (int)(((uintptr_t)(units + base) >> 1) & (TXT_RUN - 1)) : 0;
     const int64_t n_tiles = (total + mis + TXT_TILE - 1) / TXT_TILE;
     if (n_tiles > 0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: text batch too large");
-    // device: [ooff (n+2) | ids, then the packed output | id_off (n+2) | which | out | len |
-    //          tile counts, then bases | first text of each tile | tile marks | units | off]
+    // device: the stage (its ids and off written by k_txt_map: the chars are at most the units), then
+    //   [tile counts, then bases | first text of each tile | tile marks | units | off]
     // (the last two: the host form's staging); pinned: [which | ooff]
-    const size_t b_ids = align16((size_t)total * 4);
-    const size_t b_off = align16((size_t)(n_texts + 2) * 8);
-    const size_t b_which = align16((size_t)n_texts * 4);
+    Stage L(n_texts, total);
     const size_t b_tiles = align16((size_t)n_tiles * 8), b_edge = align16((size_t)n_tiles * 4);
     const size_t b_units = dev ? 0 : align16((size_t)total * 2);
-    const size_t bytes = b_off + b_ids + b_off + b_which + b_ids + b_which + 2 * b_tiles + b_edge + b_units +
-                         (dev ? 0 : b_off);
-    if ((rc = grow_stage(E, b_which + b_off, bytes))) return rc;
-    struct Release {
-        bpe_encoder *e;
-        ~Release() { release_stage(e); }
-    } release{E};
-    char *d = E->d_buf;
-    int64_t *d_ooff = reinterpret_cast<int64_t *>(d);
-    int32_t *d_ids = reinterpret_cast<int32_t *>(d += b_off);
-    int64_t *d_idoff = reinterpret_cast<int64_t *>(d += b_ids);
-    int32_t *d_which = reinterpret_cast<int32_t *>(d += b_off);
-    int32_t *d_out = reinterpret_cast<int32_t *>(d += b_which);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d += b_ids);
-    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(d += b_which);
+    const size_t bytes = L.bytes() + 2 * b_tiles + b_edge + b_units + (dev ? 0 : L.b_off);
+    if ((rc = grow_stage(E, L.b_which + L.b_off, bytes))) return rc;
+    Release release{E};
+    char *d = L.place(E->d_buf, n_texts);
+    unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(d);
     long long *d_first = reinterpret_cast<long long *>(d += b_tiles);
     uint32_t *d_edge = reinterpret_cast<uint32_t *>(d += b_tiles);
     uint16_t *d_units = reinterpret_cast<uint16_t *>(d += b_edge);
     int64_t *d_uoff = reinterpret_cast<int64_t *>(d += b_units);
-    unsigned long long *d_err = reinterpret_cast<unsigned long long *>(d_idoff + n_texts + 1);
     int32_t *h_which = reinterpret_cast<int32_t *>(E->h_buf);
-    int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf + b_which);
+    int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf + L.b_which);
     const uint16_t *units_al;
     const int64_t *k_off;
     if (dev) {
@@ -954,7 +1176,7 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     }
     ENC_TRY(hipMemsetAsync(T.d_st, 0xFF, 16, s));
     ENC_TRY(hipMemsetAsync(T.d_st + 2, 0, (TS_WORDS - 2) * 8, s));
-    ENC_TRY(hipMemsetAsync(d_err, 0, 8, s));
+    ENC_TRY(hipMemsetAsync(L.err, 0, 8, s));
     ENC_TRY(hipMemsetAsync(d_first, 0xFF, (size_t)n_tiles * 8, s));
     ENC_TRY(hipMemsetAsync(d_edge, 0, (size_t)n_tiles * 4, s));
     const CharTab ct{T.d_bmp, T.d_pairs, (1u << T.pair_bits) - 1, 32 - T.pair_bits};
@@ -965,7 +1187,7 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
         units_al, mis, total, k_off, n_texts, base, n_tiles, d_first, d_edge, d_tiles);
     k_txt_scan<<<1, 1024, 0, s>>>(d_tiles, n_tiles, T.d_st);
     k_txt_map<<<(unsigned)n_tiles, TXT_WG, 0, s>>>(units_al, mis, total, ct, d_tiles, d_first, d_edge, k_off,
-                                                  n_texts, base, d_ids, d_idoff, T.d_st);
+                                                  n_texts, base, L.ids, L.off, T.d_st);
     ENC_TRY(hipGetLastError());
     ENC_TRY(hipEventRecord(T.ev[1], s));
 
@@ -990,16 +1212,17 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     float ms = 0;
 
     if (replay) {
-        // host assembly, as bpe_encode_batch does for these texts: the front end's ids come back,
-        // bpe_encode_batch replays them, and the vector index is applied here
+        // host assembly, as the id form does for these texts: the front end's ids come back (they
+        // must: encode_ids lays its own stage over this one), encode_ids replays them, counting
+        // its call and tokens as any id call, and the vector index is applied here
         ENC_TRY(hipMemcpyAsync(T.h_st, T.d_st, TS_WORDS * 8, hipMemcpyDeviceToHost, s));
         ENC_TRY(hipStreamSynchronize(s));
         const int64_t n_ids = (int64_t)T.h_st[TS_CHARS];
         if (n_ids < 0 || n_ids > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad char count");
         std::vector<int32_t> ids((size_t)std::max<int64_t>(n_ids, 1)), vals((size_t)std::max<int64_t>(n_ids, 1));
         std::vector<int64_t> idoff((size_t)n_texts + 1), ooff((size_t)n_texts + 1, 0);
-        ENC_TRY(hipMemcpyAsync(ids.data(), d_ids, (size_t)n_ids * 4, hipMemcpyDeviceToHost, s));
-        ENC_TRY(hipMemcpyAsync(idoff.data(), d_idoff, idoff.size() * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipMemcpyAsync(ids.data(), L.ids, (size_t)n_ids * 4, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipMemcpyAsync(idoff.data(), L.off, idoff.size() * 8, hipMemcpyDeviceToHost, s));
         ENC_TRY(hipStreamSynchronize(s));
         ENC_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
         T.st.front_ms += ms;
@@ -1008,7 +1231,7 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
         // (an unknown char: the texts before its text may still hold a hole, which comes first)
         const int64_t n_use = bad_char ? text_of_unit(pc) : n_texts;
         if (bad_char && kind == BPE_ENCODE_IDS) return char_error(pc);
-        if ((rc = bpe_encode_batch(E, ids.data(), idoff.data(), n_use, vals.data(), ooff.data()))) return rc;
+        if ((rc = encode_ids(E, ids.data(), idoff.data(), n_use, vals.data(), ooff.data()))) return rc;
         if (kind == BPE_ENCODE_VECTORS) {
             const int64_t n_tvi = (int64_t)T.tvi.size();
             for (int64_t k = 0; k < n_use; ++k)
@@ -1020,73 +1243,36 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
                 }
         }
         if (bad_char) return char_error(pc);
-        n_out = ooff[n_texts];
-        *needed = n_out;
-        if (n_out > cap) {
-            char msg[128];
-            std::snprintf(msg, sizeof msg, "bpe native: encode needs %lld values, the buffer holds %lld",
-                          (long long)n_out, (long long)cap);
-            return bpe_fail(BPE_ERR_ARG, msg);
-        }
+        if ((rc = packed_length(ooff.data(), n_texts, total, cap, needed))) return rc;
+        n_out = *needed;
         if (dev) {
-            if (n_out) ENC_TRY(hipMemcpyAsync(vals_out, vals.data(), (size_t)n_out * 4, hipMemcpyHostToDevice, s));
             ENC_TRY(hipMemcpyAsync(out_off, ooff.data(), ooff.size() * 8, hipMemcpyHostToDevice, s));
-            ENC_TRY(hipStreamSynchronize(s));
+            if ((rc = copy_packed(s, vals_out, vals.data(), n_out, hipMemcpyHostToDevice))) return rc;
         } else {
             if (n_out) std::memcpy(vals_out, vals.data(), (size_t)n_out * 4);
             std::memcpy(out_off, ooff.data(), ooff.size() * 8);
         }
         T.st.chars += n_ids;
     } else {
-        size_t at = 0;
-        for (auto &L : lists) {
-            std::memcpy(h_which + at, L.data(), L.size() * 4);
-            at += L.size();
-        }
-        ENC_TRY(hipMemcpyAsync(d_which, h_which, (size_t)n_texts * 4, hipMemcpyHostToDevice, s));
-        const size_t tab = (size_t)E->lt.words * 4;
-        const bool few = (size_t)n_texts <= LATENCY_TEXTS;
-        ENC_TRY(hipEventRecord(E->ev0, s));
-        at = 0;
-        for (int i = 0; i < N_SHAPES; ++i) {
-            if (lists[i].empty()) continue;
-            const bool tab_lds = few && shape_cap(i) > LDS_TAB_MIN_TOKENS && shape_lds(i) + tab <= LDS_BYTES;
-            launch_shape(i, E, (unsigned)lists[i].size(), tab_lds, d_ids, d_idoff, d_which + at, d_out, d_len,
-                         d_err);
-            at += lists[i].size();
-        }
-        ENC_TRY(hipGetLastError());
-        ENC_TRY(hipEventRecord(E->ev1, s));
-        // packed on the device, into the ids buffer (read by the kernels above, free now)
+        fill_which(lists, h_which);
+        ENC_TRY(hipMemcpyAsync(L.which, h_which, (size_t)n_texts * 4, hipMemcpyHostToDevice, s));
+        if ((rc = launch_lists(E, lists, true, L, E->ev0, E->ev1))) return rc;
         const bool vec = kind == BPE_ENCODE_VECTORS;
-        const uint32_t n_tvi = (uint32_t)T.tvi.size();
         ENC_TRY(hipEventRecord(T.ev[2], s));
-        if (n_texts <= 1024 && total <= (1 << 18)) {
-            if (vec)
-                k_txt_pack_small_vec<<<1, 1024, 0, s>>>(d_out, d_idoff, d_len, (int)n_texts, d_ooff, d_err, T.d_tvi,
-                                                        n_tvi, d_ids, T.d_st);
-            else
-                k_pack_small<<<1, 1024, 0, s>>>(d_out, d_idoff, d_len, (int)n_texts, d_ooff, d_err, d_ids);
-        } else {
-            k_scan_lens<<<1, 1024, 0, s>>>(d_len, n_texts, d_ooff, d_err);
-            if (vec)
-                k_txt_gather_vec<<<(unsigned)((n_texts + 3) / 4), 256, 0, s>>>(d_out, d_idoff, d_len, d_ooff, n_texts,
-                                                                              T.d_tvi, n_tvi, d_ids, T.d_st);
-            else
-                k_gather<<<(unsigned)((n_texts + 3) / 4), 256, 0, s>>>(d_out, d_idoff, d_len, d_ooff, n_texts, d_ids);
-        }
-        ENC_TRY(hipGetLastError());
+        if ((rc = vec ? pack(s, L, n_texts, total, VecMap{T.d_tvi, (uint32_t)T.tvi.size(), T.d_st})
+                      : pack(s, L, n_texts, total, MapId{})))
+            return rc;
         ENC_TRY(hipEventRecord(T.ev[3], s));
         ENC_TRY(hipMemcpyAsync(T.h_st, T.d_st, TS_WORDS * 8, hipMemcpyDeviceToHost, s));
-        ENC_TRY(hipMemcpyAsync(h_ooff, d_ooff, (size_t)(n_texts + 2) * 8, hipMemcpyDeviceToHost, s));
-        ENC_TRY(hipStreamSynchronize(s));
+        // (here the bad-id word counts ids of the char table; the call's times are counted first)
+        const int bad_id = fetch_ooff(s, L, h_ooff, n_texts, 0, BPE_ERR_STATE, "bpe native: char table id out of range");
         ENC_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
         T.st.front_ms += ms;
         ENC_TRY(hipEventElapsedTime(&ms, T.ev[2], T.ev[3]));
         T.st.back_ms += ms;
         ENC_TRY(hipEventElapsedTime(&ms, E->ev0, E->ev1));
         E->st.kernel_ms += ms;
-        if (h_ooff[n_texts + 1]) return bpe_fail(BPE_ERR_STATE, "bpe native: char table id out of range");
+        if (bad_id) return bad_id;
         // the reference's error order: the first failing text's error, and inside one text the char's
         const bool bad_char = T.h_st[TS_BADCHAR] != TXT_NONE, bad_idx = vec && T.h_st[TS_BADIDX] != TXT_NONE;
         if (bad_char || bad_idx) {
@@ -1097,32 +1283,18 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
             if (ki >= kc) return char_error(pc);
             int64_t at_in = 0;
             int32_t id = 0;
-            ENC_TRY(hipMemcpyAsync(&at_in, d_idoff + ki, 8, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipMemcpyAsync(&at_in, L.off + ki, 8, hipMemcpyDeviceToHost, s));
             ENC_TRY(hipStreamSynchronize(s));
-            ENC_TRY(hipMemcpyAsync(&id, d_out + at_in + (pi - h_ooff[ki]), 4, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipMemcpyAsync(&id, L.out + at_in + (pi - h_ooff[ki]), 4, hipMemcpyDeviceToHost, s));
             ENC_TRY(hipStreamSynchronize(s));
             return text_index_error(id, ki, pi - h_ooff[ki]);
         }
-        n_out = h_ooff[n_texts];
-        if (n_out < 0 || n_out > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad packed length");
-        *needed = n_out;
-        if (n_out > cap) {
-            char msg[128];
-            std::snprintf(msg, sizeof msg, "bpe native: encode needs %lld values, the buffer holds %lld",
-                          (long long)n_out, (long long)cap);
-            return bpe_fail(BPE_ERR_ARG, msg);
-        }
-        if (dev) {
-            if (n_out) ENC_TRY(hipMemcpyAsync(vals_out, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToDevice, s));
-            ENC_TRY(hipMemcpyAsync(out_off, d_ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToDevice, s));
-            ENC_TRY(hipStreamSynchronize(s));
-        } else {
-            if (n_out) {
-                ENC_TRY(hipMemcpyAsync(vals_out, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
-                ENC_TRY(hipStreamSynchronize(s));
-            }
-            std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
-        }
+        if ((rc = packed_length(h_ooff, n_texts, total, cap, needed))) return rc;
+        n_out = *needed;
+        if (dev) ENC_TRY(hipMemcpyAsync(out_off, L.ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToDevice, s));
+        if ((rc = copy_packed(s, vals_out, L.ids, n_out, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)))
+            return rc;
+        if (!dev) std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
         E->st.texts_rank += n_texts;
         E->st.tokens_in += (int64_t)T.h_st[TS_CHARS];
         E->st.tokens_out += n_out;
@@ -1244,170 +1416,8 @@ int bpe_encoder_num_merges(bpe_encoder *E, int64_t *n) {
 
 int bpe_encode_batch(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n_texts,
                      int32_t *ids_out, int64_t *out_off) {
-    if (!E || n_texts < 0 || (n_texts && (!off || !out_off)))
-        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_batch arguments");
-    if (n_texts == 0) {
-        if (out_off) out_off[0] = 0;
-        return BPE_OK;
-    }
-    for (int64_t k = 0; k < n_texts; ++k)
-        if (off[k + 1] < off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
-    const int64_t base = off[0], total = off[n_texts] - base;
-    if (total && (!ids || !ids_out)) return bpe_fail(BPE_ERR_ARG, "bpe native: null id buffer");
-    ENC_TRY(hipSetDevice(E->device));
-    E->st.calls++;
-    E->st.tokens_in += total;
-    // launch shape of every text (the smallest that holds it), or the apply-pass route
-    std::vector<int32_t> lists[N_SHAPES];
-    std::vector<int64_t> replay;
-    for (int64_t k = 0; k < n_texts; ++k) {
-        const int64_t l = off[k + 1] - off[k];
-        if (!E->greedy_ok || l > CAP_MAX) {
-            replay.push_back(k);
-        } else {
-            int i = 0;
-            while (shape_cap(i) < l) ++i;
-            lists[i].push_back((int32_t)k);
-        }
-    }
-    int64_t n_rank = 0;
-    for (auto &L : lists) n_rank += (int64_t)L.size();
-    int rc;
-    if (!replay.empty()) {
-        // (only the replay's host route checks ids on the host; the kernels count bad ids)
-        for (int64_t k : replay)
-            for (int64_t i = off[k]; i < off[k + 1]; ++i)
-                if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB)
-                    return bpe_fail(BPE_ERR_VOCAB, "bpe native: token id out of range in text");
-    }
-    if ((rc = upload_table(E))) return rc;
-    if (replay.empty() && total >= 2 * GROUP_TOKENS && !getenv("BPE_ENCODE_ONE_GROUP")) {
-        std::vector<int32_t> shape_of((size_t)n_texts);
-        for (int i = 0; i < N_SHAPES; ++i)
-            for (int32_t k : lists[i]) shape_of[k] = i;
-        return encode_groups(E, ids, off, n_texts, shape_of, ids_out, out_off);
-    }
-    // device: [ooff (n+2) | ids, then the packed output | off (n+2) | which | out | len].  A small
-    // call's pinned host buffer mirrors [ooff | ids | off | which], so it moves [ids | off | which]
-    // up in one copy and [ooff | packed ids] down in one; a large call copies its ids straight from
-    // and to the caller's buffers and pins only [ooff | off | which].  off[n+1] = 0 is the bad-id
-    // counter (zeroed by the upload), which the pack kernel copies to ooff[n+1].
-    const size_t b_ids = align16((size_t)std::max<int64_t>(total, 1) * 4);
-    const size_t b_off = align16((size_t)(n_texts + 2) * 8);
-    const size_t b_which = align16((size_t)std::max<int64_t>(n_rank, 1) * 4);
-    const size_t b_len = align16((size_t)n_texts * 4);
-    const size_t bytes = b_off + b_ids + b_off + b_which + b_ids + b_len;
-    // Large calls copy the ids straight from the caller's buffer (no host staging pass); small ones
-    // through the pinned buffer (a pageable copy costs tens of microseconds of fixed overhead)
-    const bool small = (size_t)total * 4 <= SMALL_CALL_BYTES;
-    const size_t h_ids_bytes = small ? b_ids : 0;
-    if ((rc = grow_stage(E, b_off + h_ids_bytes + b_off + b_which, bytes))) return rc;
-    struct Release {
-        bpe_encoder *e;
-        ~Release() { release_stage(e); }
-    } release{E};
-    char *h = E->h_buf, *d = E->d_buf;
-    int64_t *d_ooff = reinterpret_cast<int64_t *>(d);
-    int32_t *d_ids = reinterpret_cast<int32_t *>(d + b_off);
-    int64_t *d_off = reinterpret_cast<int64_t *>(d + b_off + b_ids);
-    int32_t *d_which = reinterpret_cast<int32_t *>(d + b_off + b_ids + b_off);
-    int32_t *d_out = reinterpret_cast<int32_t *>(d + b_off + b_ids + b_off + b_which);
-    int32_t *d_len = reinterpret_cast<int32_t *>(d + b_off + 2 * b_ids + b_off + b_which);
-    unsigned long long *d_err = reinterpret_cast<unsigned long long *>(d_off + n_texts + 1);
-    int64_t *h_ooff = reinterpret_cast<int64_t *>(h);
-    int32_t *h_ids = reinterpret_cast<int32_t *>(h + b_off);   // (small calls only)
-    int64_t *h_off = reinterpret_cast<int64_t *>(h + b_off + h_ids_bytes);
-    int32_t *h_which = reinterpret_cast<int32_t *>(h + b_off + h_ids_bytes + b_off);
-    for (int64_t k = 0; k <= n_texts; ++k) h_off[k] = off[k] - base;
-    h_off[n_texts + 1] = 0;
-    size_t at = 0;
-    for (auto &L : lists) {
-        std::memcpy(h_which + at, L.data(), L.size() * 4);
-        at += L.size();
-    }
-    if (small) {
-        if (total) std::memcpy(h_ids, ids + base, (size_t)total * 4);
-        ENC_TRY(hipMemcpyAsync(d_ids, h_ids, b_ids + b_off + (size_t)n_rank * 4, hipMemcpyHostToDevice,
-                               E->stream));
-    } else {
-        ENC_TRY(hipMemcpyAsync(d_ids, ids + base, (size_t)total * 4, hipMemcpyHostToDevice, E->stream));
-        ENC_TRY(hipMemcpyAsync(d_off, h_off, b_off + (size_t)n_rank * 4, hipMemcpyHostToDevice, E->stream));
-    }
-    // replay texts keep length 0 on the device; they are written on the host below
-    if (!replay.empty()) ENC_TRY(hipMemsetAsync(d_len, 0, (size_t)n_texts * 4, E->stream));
-    // few texts: each has a CU to itself, and the table is read from LDS (when it fits)
-    const size_t tab = (size_t)E->lt.words * 4;
-    const bool few = (size_t)n_rank <= LATENCY_TEXTS;
-    ENC_TRY(hipEventRecord(E->ev0, E->stream));
-    at = 0;
-    for (int i = 0; i < N_SHAPES; ++i) {
-        if (lists[i].empty()) continue;
-        const bool tab_lds = few && shape_cap(i) > LDS_TAB_MIN_TOKENS && shape_lds(i) + tab <= LDS_BYTES;
-        launch_shape(i, E, (unsigned)lists[i].size(), tab_lds, d_ids, d_off, d_which + at, d_out, d_len,
-                     d_err);
-        at += lists[i].size();
-    }
-    ENC_TRY(hipGetLastError());
-    ENC_TRY(hipEventRecord(E->ev1, E->stream));
-    if (replay.empty()) {
-        // packed on the device, into the ids buffer (read by the kernels above, free now)
-        if (n_texts <= 1024 && total <= (1 << 18)) {   // (one workgroup copies it all)
-            k_pack_small<<<1, 1024, 0, E->stream>>>(d_out, d_off, d_len, (int)n_texts, d_ooff, d_err, d_ids);
-        } else {
-            k_scan_lens<<<1, 1024, 0, E->stream>>>(d_len, n_texts, d_ooff, d_err);
-            k_gather<<<(unsigned)((n_texts + 3) / 4), 256, 0, E->stream>>>(d_out, d_off, d_len, d_ooff,
-                                                                            n_texts, d_ids);
-        }
-        ENC_TRY(hipGetLastError());
-        if (small) {
-            ENC_TRY(hipMemcpyAsync(h_ooff, d_ooff, b_off + (size_t)total * 4, hipMemcpyDeviceToHost,
-                                   E->stream));
-            ENC_TRY(hipStreamSynchronize(E->stream));
-            if (h_ooff[n_texts + 1]) return bpe_fail(BPE_ERR_VOCAB, "bpe native: token id out of range in text");
-            std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
-            if (h_ooff[n_texts]) std::memcpy(ids_out, h_ids, (size_t)h_ooff[n_texts] * 4);
-        } else {
-            // the offsets first, then only the packed ids (merges shrink a batch: 5x on zipf words)
-            ENC_TRY(hipMemcpyAsync(h_ooff, d_ooff, (size_t)(n_texts + 2) * 8, hipMemcpyDeviceToHost, E->stream));
-            ENC_TRY(hipStreamSynchronize(E->stream));
-            if (h_ooff[n_texts + 1]) return bpe_fail(BPE_ERR_VOCAB, "bpe native: token id out of range in text");
-            const int64_t n_out = h_ooff[n_texts];
-            if (n_out < 0 || n_out > total) return bpe_fail(BPE_ERR_STATE, "bpe native: bad packed length");
-            if (n_out) {
-                ENC_TRY(hipMemcpyAsync(ids_out, d_ids, (size_t)n_out * 4, hipMemcpyDeviceToHost, E->stream));
-                ENC_TRY(hipStreamSynchronize(E->stream));
-            }
-            std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
-        }
-    } else {
-        // host assembly: the kernels' texts come back at their input offsets, the replayed ones
-        // from the scratch engine (into the same host buffer: after the copies have landed)
-        std::vector<int64_t> len((size_t)n_texts, 0);
-        std::vector<int32_t> out((size_t)std::max<int64_t>(total, 1));
-        std::vector<int32_t> lens((size_t)n_texts);
-        unsigned long long err = 0;
-        ENC_TRY(hipMemcpyAsync(out.data(), d_out, (size_t)total * 4, hipMemcpyDeviceToHost, E->stream));
-        ENC_TRY(hipMemcpyAsync(lens.data(), d_len, (size_t)n_texts * 4, hipMemcpyDeviceToHost, E->stream));
-        ENC_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, E->stream));
-        ENC_TRY(hipStreamSynchronize(E->stream));
-        if (err) return bpe_fail(BPE_ERR_VOCAB, "bpe native: token id out of range in text");
-        if ((rc = encode_replay(E, ids, off, replay, out.data(), len.data()))) return rc;
-        for (auto &L : lists)
-            for (int32_t k : L) len[k] = lens[k];
-        int64_t o = 0;
-        out_off[0] = 0;
-        for (int64_t k = 0; k < n_texts; ++k) {
-            if (len[k]) std::memcpy(ids_out + o, out.data() + (off[k] - base), (size_t)len[k] * 4);
-            o += len[k];
-            out_off[k + 1] = o;
-        }
-    }
-    float ms = 0;
-    ENC_TRY(hipEventElapsedTime(&ms, E->ev0, E->ev1));
-    E->st.kernel_ms += ms;
-    E->st.texts_rank += n_rank;
-    E->st.tokens_out += out_off[n_texts];
-    return BPE_OK;
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_batch arguments");
+    return encode_ids(E, ids, off, n_texts, ids_out, out_off);
 }
 
 int bpe_encoder_get_stats(bpe_encoder *E, bpe_encoder_stats *out) {

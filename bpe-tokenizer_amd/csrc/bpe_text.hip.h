@@ -284,58 +284,18 @@ k_txt_map(const uint16_t *__restrict__ units_al, int mis, int64_t total, CharTab
     }
 }
 
-// ---- back end: the pack kernels, writing to_vector_index[id] -----------------------------------
+// ---- back end: the pack kernels' map (k_pack_small, k_gather), writing to_vector_index[id] -----
 
-__device__ __forceinline__ int32_t txt_vec(const int32_t *__restrict__ tvi, uint32_t n_tvi, int32_t id,
-                                           unsigned long long pos, unsigned long long *__restrict__ st) {
-    const int32_t v = (uint32_t)id < n_tvi ? tvi[id] : -1;
-    if (v < 0) atomicMin(&st[TS_BADIDX], pos);
-    return v;
-}
-
-// k_pack_small's shape (at most 1024 texts: the scan, then one wave per text)
-__global__ void __launch_bounds__(1024)
-k_txt_pack_small_vec(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off,
-                     const int32_t *__restrict__ len, int n, int64_t *__restrict__ ooff,
-                     const unsigned long long *__restrict__ err, const int32_t *__restrict__ tvi,
-                     uint32_t n_tvi, int32_t *__restrict__ dst, unsigned long long *__restrict__ st) {
-    __shared__ int scn[16];
-    __shared__ int start[1025];
-    const int v = (int)threadIdx.x < n ? len[threadIdx.x] : 0;
-    int total = 0;
-    const int before = block_scan<1024>(v, scn, total);
-    if ((int)threadIdx.x < n) {
-        start[threadIdx.x] = before;
-        ooff[threadIdx.x] = before;
+struct VecMap {
+    const int32_t *tvi;
+    uint32_t n_tvi;
+    unsigned long long *st;
+    __device__ __forceinline__ int32_t operator()(int32_t id, unsigned long long pos) const {
+        const int32_t v = (uint32_t)id < n_tvi ? tvi[id] : -1;
+        if (v < 0) atomicMin(&st[TS_BADIDX], pos);
+        return v;
     }
-    if (threadIdx.x == 0) {
-        ooff[n] = total;
-        ooff[n + 1] = (long long)*err;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x >> 6; t < n; t += 16) {
-        const int32_t *s = src + in_off[t];
-        const int o = start[t];
-        const int l = len[t];
-        for (int i = threadIdx.x & 63; i < l; i += 64)
-            dst[o + i] = txt_vec(tvi, n_tvi, s[i], (unsigned long long)(o + i), st);
-    }
-}
-
-// k_gather's shape (one wave per text)
-__global__ void __launch_bounds__(256)
-k_txt_gather_vec(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off,
-                 const int32_t *__restrict__ len, const int64_t *__restrict__ ooff, int64_t n,
-                 const int32_t *__restrict__ tvi, uint32_t n_tvi, int32_t *__restrict__ dst,
-                 unsigned long long *__restrict__ st) {
-    const int64_t text = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (text >= n) return;
-    const int32_t *s = src + in_off[text];
-    const int64_t o = ooff[text];
-    const int l = len[text];
-    for (int i = threadIdx.x & 63; i < l; i += 64)
-        dst[o + i] = txt_vec(tvi, n_tvi, s[i], (unsigned long long)(o + i), st);
-}
+};
 
 }  // namespace
 

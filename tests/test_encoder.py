@@ -10,6 +10,8 @@
 The CPU-only test at the bottom checks the merge-rank greedy itself (the kernel's algorithm,
 restated in Python) against the replay, without a device.
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -225,6 +227,63 @@ def test_large_call_in_groups(monkeypatch):
         enc.encode_flat(bad, off)
     again, again_off = enc.encode_flat(flat, off)
     assert np.array_equal(again_off, got_off) and np.array_equal(again, got)
+    enc.close()
+
+
+@functools.lru_cache(maxsize=None)
+def merges_of_alphabet_30():
+    """One trained list for the tests below (test_many_short_texts_one_batch's shape)."""
+    return trained_merges(np.random.default_rng(32), 30, 200, 400)
+
+
+@pytest.mark.gpu
+def test_large_call_with_a_replayed_text():
+    """More than 2^20 tokens (the ids go straight from and to the caller's buffers), not grouped,
+    and host assembly because one text in the middle is too long for the kernels."""
+    rng = np.random.default_rng(33)
+    merges = merges_of_alphabet_30()
+    lengths = rng.integers(600, 1001, size=1500)
+    mid = 750
+    lengths[mid] = pkg.ENCODE_LDS_TOKENS + 1
+    n = len(lengths)
+    total = int(lengths.sum())
+    assert total > 1 << 20
+    flat = np.concatenate([np.full(9, 3, np.int32), rng.integers(0, 30, size=total).astype(np.int32)])
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64) + 9
+    enc = pkg.Encoder(0, merges)
+    enc.reset_stats()
+    got, got_off = enc.encode_flat(flat, off)
+    st = enc.stats()
+    assert st['texts_replay'] == 1 and st['texts_rank'] == n - 1
+    want = oracle.encode([flat[off[k]:off[k + 1]] for k in range(n)], merges)
+    # the ids of the replayed text, its neighbours, both ends and every 50th text
+    for k in sorted({mid - 1, mid, mid + 1, 0, n - 1} | set(range(0, n, 50))):
+        assert got[got_off[k]:got_off[k + 1]].tolist() == want[k].tolist(), k
+    # the offsets: the sum of the texts' lengths, at every text
+    assert got_off.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
+    assert len(got) == got_off[-1]
+    enc.close()
+
+
+def pack_edge_batches(rng, alphabet):
+    """Batches at the edges of the pack choice (one workgroup packs up to 1024 texts of up to
+    2^18 tokens together): 1024 and 1025 texts, and 64 texts of exactly 2^18 and 2^18 + 1 tokens."""
+    out = [random_texts(rng, alphabet, rng.integers(1, 4, size=n)) for n in (1024, 1025)]
+    for total in (1 << 18, (1 << 18) + 1):
+        lengths = rng.integers(3000, 5000, size=64)
+        lengths[-1] += total - lengths.sum()
+        assert lengths.sum() == total and 0 < lengths[-1] <= pkg.ENCODE_LDS_TOKENS
+        out.append(random_texts(rng, alphabet, lengths))
+    return out
+
+
+@pytest.mark.gpu
+def test_pack_choice_at_its_edges():
+    rng = np.random.default_rng(44)
+    merges = merges_of_alphabet_30()
+    enc = pkg.Encoder(0, merges)
+    for texts in pack_edge_batches(rng, 30):
+        check(enc, texts, merges)
     enc.close()
 
 

@@ -324,6 +324,42 @@ def test_more_tiles_than_one_scan_round():
         enc.close()
 
 
+@pytest.mark.gpu
+def test_pack_choice_at_its_edges():
+    """One workgroup packs a call of up to 1024 texts and 2^18 units; past either, the scan and the
+    gather do.  Both kinds on each side of both edges, and a hole of the index in the last text of
+    the 1025-text batch (the gather's last wave)."""
+    v = edge_vocab()
+    rng = np.random.default_rng(12)
+    enc = make_encoder(v)
+    try:
+        batches = [[gen(rng, int(l)) for l in rng.integers(1, 4, size=n)] for n in (1024, 1025)]
+        for total in (1 << 18, (1 << 18) + 1):
+            lens = rng.integers(3000, 5000, size=64)
+            lens[-1] += total - lens.sum()
+            assert lens.sum() == total and 0 < lens[-1] <= pkg.ENCODE_LDS_TOKENS
+            batches.append([gen(rng, int(l)) for l in lens])
+        enc.reset_stats()
+        for texts in batches:
+            units, off = flat(texts, 1)
+            assert len(units) - 1 == sum(len(t) for t in texts)
+            check_flat(enc, v, units, off)
+        assert enc.stats()['texts_replay'] == 0
+        t = v['table']
+        inputs = {x for m in v['merges'] for x in m[:2]}
+        hc = next(c for c in v['chars'][:23] if t[c] not in inputs)   # (stands alone wherever it is)
+        HC = ord(hc)
+        hole = v['index'].copy()
+        hole[t[hc]] = -1
+        enc.set_vector_index(hole)
+        texts = [np.where(x == HC, 0x61 if HC != 0x61 else 0x62, x).astype(np.uint16) for x in batches[1]]
+        texts[-1] = np.asarray([0x63, HC, 0x63], np.uint16)
+        msg = expect_error(enc, v, 'vectors', texts, hole, lead=1)
+        assert msg.startswith('unknown token index: %d (text 1024, position ' % t[hc])
+    finally:
+        enc.close()
+
+
 # ---- 3. agreement with the id form ------------------------------------------------------------------
 
 @pytest.mark.gpu
