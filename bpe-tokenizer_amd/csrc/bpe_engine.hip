@@ -24,7 +24,7 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
 hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, void *ctl, void *sums,
                              unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
-                             uint32_t *plane);
+                             uint32_t *plane, void *lists, uint32_t *rows);
 hipError_t launch_digest_build(hipStream_t s, const int32_t *ids, int64_t n_chunks, uint32_t *plane);
 hipError_t launch_step_table(int merge, unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, int32_t ma, int32_t mb,
@@ -78,7 +78,7 @@ static_assert(XCHG_HDR == BPE_XCHG_HDR && XCHG_WORDS == BPE_XCHG_WORDS && TIE_WO
                   DELTA_ROWS == BPE_DELTA_ROWS,
               "include/bpe.h exchange layout");
 static_assert(DIGEST_MOD == BPE_DIGEST_MOD && DIGEST_SEP == BPE_DIGEST_SEP &&
-                  DIGEST_DEAD == BPE_DIGEST_DEAD,
+                  DIGEST_DEAD == BPE_DIGEST_DEAD && DIGEST_CAND == BPE_DIGEST_CAND,
               "include/bpe.h digest plane");
 
 template <typename T>
@@ -189,6 +189,16 @@ struct bpe_ctx {
     uint32_t *d_digest = nullptr;
     int64_t digest_cap = 0;
     bool digest_valid = false, digest_changed = true;
+    // the hit lists of the digest stream (DigestLists: the cached pairs and the block keys the
+    // scan predicts from) and their rows (lists_cap words: R x DIGEST_CAND x ceil(cpr / 32)).
+    // They live and die with the plane: digest_stale drops them with it (lists_valid), and the
+    // batch that finds them dropped, or the geometry or the candidate cap changed, clears the
+    // device's copy before its first iteration (digest_begin_batch).
+    DigestLists *d_lists = nullptr;
+    uint32_t *d_rows = nullptr;
+    int64_t lists_cap = 0, lists_cpr = 0;
+    int lists_R = 0, lists_cand = 0;
+    bool lists_valid = false;
     int64_t last_delta = 0, last_done = 0;
     unsigned int *d_ticket = nullptr;   // last-block tickets (k_tie_fused, k_select_maint; zero between launches)
     BlockBest *d_brec = nullptr;        // k_select_maint's per-block bests
@@ -275,6 +285,7 @@ enum DigestWriter { WRITER_LOOP, WRITER_OUTSIDE };
 // d_ids is about to be written (or replaced) by something that does not keep the digest plane.
 void digest_stale(bpe_ctx *c, DigestWriter w) {
     c->digest_valid = false;
+    c->lists_valid = false;   // (a list is a view of the plane: compaction even moves its chunks)
     if (w == WRITER_OUTSIDE) c->digest_changed = true;
 }
 
@@ -286,8 +297,12 @@ void digest_stale(bpe_ctx *c, DigestWriter w) {
 // DIGEST_REBUILD_MIN and at least half of its iterations: a build costs about 1.3 int32 streams,
 // and a batch of heavy merges would clear the plane again at once.  If the plane cannot be
 // allocated the batch runs on the int32 stream.
-int digest_begin_batch(bpe_ctx *c, bool *fresh) {
+int digest_begin_batch(bpe_ctx *c, bool *fresh, int *cand) {
     *fresh = false;
+    // (BPE_DIGEST_CAND=n caps the candidates of a plane stream, 1 .. the constant; read per batch;
+    // at 1 every delta iteration scans: the A/B and checking knob)
+    const char *cknob = getenv("BPE_DIGEST_CAND");
+    *cand = cknob ? std::min(std::max(atoi(cknob), 1), DIGEST_CAND) : DIGEST_CAND;
     const char *gknob = getenv("BPE_DIGEST");
     if ((gknob && atoi(gknob) == 0) || c->n_chunks <= 0) return BPE_OK;
     if (c->digest_cap < c->n_chunks * CHUNK) {
@@ -314,6 +329,29 @@ int digest_begin_batch(bpe_ctx *c, bool *fresh) {
         c->digest_changed = false;
     }
     *fresh = c->digest_valid;
+    if (!c->digest_valid) return BPE_OK;
+    const int64_t words = (int64_t)c->R * DIGEST_CAND * ((c->cpr + 31) / 32);
+    if (c->lists_cap < words) {
+        dfree(c->d_rows);
+        c->d_rows = nullptr;
+        c->lists_cap = 0;
+        c->lists_valid = false;
+        if (dev_alloc(&c->d_rows, (size_t)words)) {
+            // (no room for the rows: the batch scans for the decided pair alone)
+            (void)hipGetLastError();
+            *cand = 1;
+            return BPE_OK;
+        }
+        c->lists_cap = words;
+    }
+    // the device's lists outlive a batch only with the plane they were read from (kept by
+    // digest_end_batch, nothing written since), in the same geometry and under the same cap
+    if (!c->lists_valid || c->lists_cpr != c->cpr || c->lists_R != c->R || c->lists_cand != *cand) {
+        HIP_TRY(hipMemsetAsync(c->d_lists, 0xFF, offsetof(DigestLists, bkey), c->stream));
+        c->lists_cpr = c->cpr;
+        c->lists_R = c->R;
+        c->lists_cand = *cand;
+    }
     return BPE_OK;
 }
 
@@ -321,6 +359,7 @@ int digest_begin_batch(bpe_ctx *c, bool *fresh) {
 // merge took its stream (a full-form merge clears digest_ok on the device); and the delta share.
 void digest_end_batch(bpe_ctx *c, const LoopCtl *h) {
     c->digest_valid = h->digest_ok != 0;
+    c->lists_valid = c->digest_valid;   // (the decision that clears digest_ok drops them too)
     c->last_delta = h->n_delta;
     c->last_done = h->n_done;
 }
@@ -703,7 +742,8 @@ int enqueue_stitch_reduce(bpe_ctx *c, const Pass &p) {
         // shard's table, replacement count and largest bin into the exchange buffer, no best key)
         k_reduce_table<<<REDUCE_TABLE_GRID, REDUCE_THREADS, 0, s>>>(
             c->d_partials, c->G, c->d_spill, x ? x + XCHG_HDR : c->d_hot, c->d_len16, p.max_length,
-            x ? nullptr : c->d_res, p.ctl, x, x ? rep : nullptr, x ? &c->d_res->bin_max : nullptr);
+            x ? nullptr : c->d_res, p.ctl, x, x ? rep : nullptr, x ? &c->d_res->bin_max : nullptr,
+            x ? nullptr : c->d_lists->bkey);
     }
     HIP_TRY(hipGetLastError());
     return span_end(c, e_red, 1);
@@ -804,7 +844,7 @@ int enqueue_loop_pass(bpe_ctx *c, const Pass &p) {
         if (p.delta)
             HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
                                                 c->d_carry, c->d_ctl, c->d_sums, rep, c->d_sites,
-                                                c->d_site_n, c->d_digest));
+                                                c->d_site_n, c->d_digest, c->d_lists, c->d_rows));
     }
     HIP_TRY(hipGetLastError());
     // (span kind 2, the incr_* statistics: the single context's maintained passes only)
@@ -1301,7 +1341,8 @@ int loop_prepare(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, 
         c->sites_cap = cap;
     }
     bool digest = false;   // the delta form's stream reads the digest plane
-    if (p->delta && (rc = digest_begin_batch(c, &digest))) return rc;
+    int cand = 1;          // ... for this many candidate pairs per stream
+    if (p->delta && (rc = digest_begin_batch(c, &digest, &cand))) return rc;
     hipStream_t s = c->stream;
     if (maint) {
         // (k_select_maint takes the best over the hot bins itself)
@@ -1312,10 +1353,13 @@ int loop_prepare(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t n, 
     } else {
         HIP_TRY(hipMemsetAsync(c->d_res, 0, sizeof(Result), s));
         k_argmax_hot<<<HOT_BINS / 256, 256, 0, s>>>(c->d_hot, c->d_len16, max_length, c->d_res);
+        // (no block keys of this table: the first scan has nothing to predict from)
+        HIP_TRY(hipMemsetAsync(c->d_lists->bkey, 0, sizeof c->d_lists->bkey, s));
     }
     LoopCtl *h = ctl_begin(c, min_weight, maint);
     h->allow_delta = p->delta ? 1 : 0;
     h->digest_ok = digest ? 1 : 0;
+    h->digest_cand = cand;
     HIP_TRY(hipMemcpyAsync(c->d_ctl, h, sizeof *h, hipMemcpyHostToDevice, s));
     return BPE_OK;
 }
@@ -1347,7 +1391,8 @@ int loop_enqueue(bpe_ctx *c, const Pass &p, int64_t n) {
                                                             c->d_ctl);
         }
         // the decision, the R3 tie pass when tied, and its commit: one launch
-        k_tie_fused<<<regions_grid(c), 256, 0, s>>>(tie, c->d_len16, c->d_log, c->d_ticket);
+        k_tie_fused<<<regions_grid(c), 256, 0, s>>>(tie, c->d_len16, c->d_log, c->d_ticket,
+                                                    c->d_lists);
         HIP_TRY(hipGetLastError());
         // (timed with the selection, so that the pass's span is the pass kernel alone)
         if ((rc = enqueue_loop_invalidate(c, p))) return rc;
@@ -1382,6 +1427,7 @@ void loop_stats(bpe_ctx *c, const LoopCtl *h) {
     c->stats.delta_chunks += (int64_t)h->delta_chunks;
     c->stats.digest_passes += h->n_digest;
     c->stats.digest_hits += (int64_t)h->digest_hits;
+    c->stats.digest_scans += h->n_scan;
 }
 
 // A batch's third part: the one host sync, then the host tables brought up to date from the log.
@@ -2712,7 +2758,11 @@ int bpe_create(bpe_ctx **out, int device) {
     if ((rc = dev_alloc(&c->d_ticket, TICKET_WORDS))) return bail(rc);
     if ((rc = dev_alloc(&c->d_brec, COLD_GRID))) return bail(rc);
     if ((rc = dev_alloc(&c->d_site_n, MAX_REGIONS))) return bail(rc);
-    if (hipMemset(c->d_ticket, 0, TICKET_WORDS * sizeof(unsigned int)) != hipSuccess)
+    if ((rc = dev_alloc(&c->d_lists, 1))) return bail(rc);
+    // (no pair cached, no row to apply from, no block keys)
+    if (hipMemset(c->d_lists, 0, sizeof(DigestLists)) != hipSuccess ||
+        hipMemset(c->d_lists, 0xFF, offsetof(DigestLists, bkey)) != hipSuccess ||
+        hipMemset(c->d_ticket, 0, TICKET_WORDS * sizeof(unsigned int)) != hipSuccess)
         return bail(fail(BPE_ERR_HIP, "bpe native: memset failed"));
     if ((rc = dev_alloc(&c->d_repl, REPLAY_BATCH))) return bail(rc);
     if (hipHostMalloc((void **)&c->h_repl, REPLAY_BATCH * sizeof(unsigned long long),
@@ -2768,7 +2818,7 @@ int bpe_destroy(bpe_ctx *c) {
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
                     c->cold.bmax, c->cold.bdirty, c->cold.blist,
                     c->d_ctl, c->d_log, c->d_repl, c->d_ticket, c->d_brec, c->d_sites,
-                    c->d_site_n, c->d_digest};
+                    c->d_site_n, c->d_digest, c->d_lists, c->d_rows};
     for (void *p : ptrs) dfree(p);
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_cand) (void)hipHostFree(c->h_cand);

@@ -327,7 +327,8 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
                int64_t max_length, Result *res, const LoopCtl *ctl,
                unsigned long long *__restrict__ hdr = nullptr,
                const unsigned long long *__restrict__ rep = nullptr,
-               unsigned long long *__restrict__ bin_max = nullptr) {
+               unsigned long long *__restrict__ bin_max = nullptr,
+               unsigned long long *__restrict__ bkey = nullptr) {
     __shared__ uint32_t s_sum[REDUCE_GROUPS][32][8];
     // A delta iteration of the device loop (LoopCtl::delta, uniform over the grid): the table is
     // already current (k_site_delta), so nothing is summed or written; the block only scans its
@@ -412,6 +413,9 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
             k = s_best[w] > k ? s_best[w] : k;
             vm = s_vmax[w] > vm ? s_vmax[w] : vm;
         }
+        // (a hot block's own best key: what the digest stream predicts the next merges from,
+        // DigestLists::bkey)
+        if (bkey && blockIdx.x < HOT) bkey[blockIdx.x] = k;
         if (k && res) atomicMax(&res->best, k);
         if (bin_max) atomicMax(bin_max, vm + 1);
     }
@@ -975,7 +979,8 @@ __device__ int decide_r3(int tie, unsigned n, const unsigned long long *pos, con
 // form when the host allows it (the table state), a != b, and the merge's W sites lie in fewer
 // than 1/16 of the chunks, the rule k_step_loop uses for a heavy merge.
 __device__ void decide_commit(LoopCtl *ctl, Result *res, const LoopCtl &C, long long W, int32_t a,
-                              int32_t b, int32_t *len16, long long *log, int64_t n_chunks = 0) {
+                              int32_t b, int32_t *len16, long long *log, int64_t n_chunks = 0,
+                              DigestLists *lists = nullptr) {
     const int32_t c = C.next_id;
     len16[c] = len16[a] + len16[b];
     const long long i = C.n_done;
@@ -997,6 +1002,20 @@ __device__ void decide_commit(LoopCtl *ctl, Result *res, const LoopCtl &C, long 
     const int32_t dg = C.digest_ok && (dl || W <= 0);
     ctl->digest_ok = dg;
     ctl->n_digest = C.n_digest + (dl && dg);
+    // The hit lists (the single-context loop): a delta iteration on the plane applies (a, b) from
+    // the row a scan cached for it, and the slot is free again; without one the stream scans the
+    // plane, which refills every slot.  The decision that clears digest_ok drops every list.
+    if (lists) {
+        int32_t use = -1;
+        if (dl && dg)
+            for (int j = 1; j < DIGEST_CAND; ++j)
+                if (j < C.digest_cand && lists->pa[j] == a && lists->pb[j] == b) use = j;
+        if (use >= 0) lists->pa[use] = -1;
+        if (C.digest_ok && !dg)
+            for (int j = 0; j < DIGEST_CAND; ++j) lists->pa[j] = -1;
+        lists->use = use;
+        ctl->n_scan = C.n_scan + (dl && dg && use < 0);
+    }
     // (a delta iteration counts nothing: unscreened describes the full passes only)
     const int32_t uns = !dl && !C.maintained && bm &&
                         (bm - 1) + 2 * (unsigned long long)W < 0x10000ull;
@@ -1670,7 +1689,7 @@ __global__ void __launch_bounds__(256) k_tie(TieArgs A) {
 // k_tie_fused 45 registers and 64 bytes of scratch)
 __device__ void fused_commit(LoopCtl *ctl, Result *res, int64_t n_chunks, const LoopCtl &C,
                              const Result &R, const int2 *sc, int prop, int32_t *len16,
-                             long long *log) {
+                             long long *log, DigestLists *lists) {
     if (!decide_check_replaced(ctl, C, R, nullptr, log)) return;
     ctl->w = -1;
     if (prop == 4) {
@@ -1706,11 +1725,11 @@ __device__ void fused_commit(LoopCtl *ctl, Result *res, int64_t n_chunks, const 
             return;
         }
     }
-    decide_commit(ctl, res, C, (long long)(R.best >> 17), a, b, len16, log, n_chunks);
+    decide_commit(ctl, res, C, (long long)(R.best >> 17), a, b, len16, log, n_chunks, lists);
 }
 
 __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, long long *log,
-                                                   unsigned int *ticket) {
+                                                   unsigned int *ticket, DigestLists *lists) {
     __shared__ LoopCtl sC;
     __shared__ Result sR;
     __shared__ int2 sc[MAX_CAND];
@@ -1737,7 +1756,7 @@ __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, lo
     const int prop = s_prop;
     if (prop == 0) return;   // (the batch has ended, or block 0 decides alone)
     if (prop != 1 && prop != 2) {
-        if (threadIdx.x == 0) fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log);   // (block 0 only)
+        if (threadIdx.x == 0) fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log, lists);   // (block 0 only)
         return;
     }
     tie_body(A, (int)sR.n_cand, prop == 1, sc);
@@ -1748,7 +1767,7 @@ __global__ void __launch_bounds__(256) k_tie_fused(TieArgs A, int32_t *len16, lo
     __syncthreads();
     if (!s_last || threadIdx.x != 0) return;
     __threadfence();
-    fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log);
+    fused_commit(const_cast<LoopCtl *>(A.ctl), A.res, A.n_chunks, sC, sR, sc, prop, len16, log, lists);
 }
 
 // Sharded loop: this shard's last tie positions as corpus-wide ones (rank << 40 | position; 0:

@@ -1040,6 +1040,7 @@ int multi_get_stats(bpe_multi *m, bpe_stats *out) {
         acc.digest_passes += x.digest_passes;
         acc.digest_hits += x.digest_hits;
         acc.digest_builds += x.digest_builds;
+        acc.digest_scans += x.digest_scans;
         acc.xchg_iters = std::max(acc.xchg_iters, x.xchg_iters);
     }
     acc.pix_fallbacks = m->pix_fallbacks;

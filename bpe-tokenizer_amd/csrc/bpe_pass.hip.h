@@ -235,7 +235,34 @@ struct LoopCtl {
     unsigned long long delta_chunks;   // chunks listed by the delta iterations of this batch
     unsigned long long digest_hits;    // chunks the digest stream took to the exact path
     int32_t n_digest;       // delta iterations on the plane, in this batch
+    int32_t n_scan;         // ... of which streamed the plane (the others took a cached hit list)
+    // candidate pairs a stream of the plane answers for, 1 .. DIGEST_CAND (the host's, per batch:
+    // BPE_DIGEST_CAND); at 1 every delta iteration on the plane scans
+    int32_t digest_cand;
     int32_t pad_;
+};
+
+// The hit lists of the digest stream (include/bpe.h BPE_DIGEST_CAND: candidate slots).  One
+// stream of the plane answers "can this chunk hold a site?" for the decided pair (slot 0, applied
+// at once, never stored) and for up to DIGEST_CAND - 1 predicted pairs, whose answers are kept:
+// one bit per chunk, region r's row of slot j at rows[(r * DIGEST_CAND + j) * wpr], wpr =
+// ceil(cpr / 32) words.  A merge only replaces two adjacent tokens by a fresh id and never moves
+// a token to another chunk, so the chunks that hold a site of (p, q) after any number of merges
+// are among those flagged for (p, q) at the scan: a cached row stays a superset (a chunk with no
+// site left is one more false hit) while the plane stays valid and the geometry unchanged.
+// The state lives outside the LoopCtl (re-sent at every batch start) and survives a batch exactly
+// when the plane does (digest_begin_batch clears it with every build).
+constexpr int DIGEST_CAND = 4;
+static_assert(DIGEST_CAND >= 1 && DIGEST_CAND <= 8, "candidate slots of a plane stream");
+struct DigestLists {
+    int32_t pa[DIGEST_CAND], pb[DIGEST_CAND];   // slot j holds the row of (pa, pb); pa < 0: free
+    // this iteration (set by the decision): the slot whose row the merge is applied from, or -1:
+    // stream the plane
+    int32_t use;
+    int32_t pad_;
+    // the best key of each block of 256 hot bins (bins b * 256 + a of one b), left by the last
+    // k_reduce_table: the scan predicts the next merges from the largest of them
+    unsigned long long bkey[HOT];
 };
 
 
@@ -1805,10 +1832,21 @@ static_assert(4 * DG_RING == 32, "a round's chunks fill a 32-bit hit mask");
 // Chunks the region sums' walks read from either end of a rewritten region before its wave
 // tallies the whole region instead (region_tally).
 constexpr int DG_WALK = 2;
+// Hit chunks whose loads are in flight while the exact path applies the first of them.
+constexpr int DG_PF = 4;
 
 // Zero-halfword test of y, before the 0x80008000 mask (exact as an any-test: a borrow reaches a
 // halfword only from a zero halfword below it).
 __device__ __forceinline__ uint32_t hz16(uint32_t y) { return (y - 0x00010001u) & ~y; }
+
+// The smaller of each halfword of x and y (v_pk_min_u16): over many values a halfword of the
+// result is zero iff it is zero in one of them, so a chain of these keeps one zero-halfword test
+// for the end.
+__device__ __forceinline__ uint32_t pk_min16(uint32_t x, uint32_t y) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, x),
+                                                                  __builtin_bit_cast(u16x2, y)));
+}
 
 // The sums of one region tallied from its int32 slots (the apply-only pass's count, chunk by
 // chunk with synchronous loads): the digest stream's slow path, for a region whose first or last
@@ -1962,6 +2000,11 @@ __device__ __forceinline__ RegionSum region_resum(const __amdgpu_buffer_rsrc_t r
 // A rewritten chunk's digests are stored with it and the chunk is listed for k_site_delta.  The
 // region's sums are left as the last pass wrote them unless a chunk was rewritten; then n_live
 // loses the removed slots and the edge fields are read again (region_resum).
+// A scan (use < 0) streams the plane once and answers the first two conditions for up to `ncand`
+// pairs: the decided one, whose hit chunks are applied at once, and the predicted next ones, whose
+// answers are stored as rows of bits (DigestLists).  With use >= 0 nothing is streamed: the decided
+// pair's hit chunks are those of its cached row `use`.  Either way the hit chunks are applied in
+// order by one copy of the exact path, the loads of the next DG_PF of them in flight (apply_words).
 __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t *__restrict__ plane,
                                             int64_t n_chunks, int64_t cpr, int R,
                                             const RegionCarry *__restrict__ carry, int32_t ma,
@@ -1969,7 +2012,10 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                                             unsigned long long *__restrict__ replaced,
                                             uint32_t *__restrict__ site_list,
                                             uint32_t *__restrict__ site_n,
-                                            unsigned long long *__restrict__ n_hits) {
+                                            unsigned long long *__restrict__ n_hits,
+                                            DigestLists *__restrict__ dl,
+                                            uint32_t *__restrict__ rows, int ncand, int use,
+                                            uint32_t *wg_acc) {
     const int lane = threadIdx.x & 63;
     const int r = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6)));
     if (r >= R) return;
@@ -2011,13 +2057,19 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
     };
     uint32_t hits = 0;
     int32_t removed = 0;
-    // the exact path of chunk c: what the int32 stream's stage does for it
-    auto exact = [&](int c) {
+    // A chunk's 1 KiB of slots, and slot 0 of its successor in the same round trip (of the
+    // region's last chunk live_from takes next_tok instead).
+    auto load_chunk = [&](int c) __attribute__((always_inline)) {
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, c * (CHUNK * 4), 0);
+    };
+    auto load_slot0 = [&](int c) __attribute__((always_inline)) {
+        return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, 0, c * (CHUNK * 4), 0);
+    };
+    using Slots = decltype(load_chunk(0));
+    // the exact path of chunk c, its slots x and its successor's slot 0 loaded: what the int32
+    // stream's stage does for it
+    auto exact = [&](int c, const Slots x, const int32_t f1) __attribute__((always_inline)) {
         Chunk q;
-        const auto x = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, c * (CHUNK * 4), 0);
-        // (slot 0 of the next chunk in the same round trip; past the region the load returns 0
-        // and live_from takes next_tok)
-        const int32_t f1 = slot0(c + 1);
         q.t[0] = (int)x[0];
         q.t[1] = (int)x[1];
         q.t[2] = (int)x[2];
@@ -2038,9 +2090,68 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
         // does the token before the region match the region's first live token?
         const int32_t f = live_from(0, slot0(0));
         ap.match = ((uint32_t)(ap.prev ^ ma) | (uint32_t)(f ^ mb)) == 0u;
-        const uint32_t da = digest_of(ma), db = digest_of(mb);
-        const uint32_t K1 = (da | (db << 8)) * 0x00010001u;
-        const uint32_t K2 = (da | (DIGEST_DEAD << 8)) * 0x00010001u;
+        const bool scan = use < 0;
+        // The candidates of a scan: the decided pair in slot 0, and in slots 1 .. ncand - 1 the
+        // pairs of the largest block keys the last k_reduce_table left (DigestLists::bkey), the
+        // table's order by pack_key being the order of the next merges unless a merge between
+        // disturbs it.  Only a guess: a != b, 16 W < n_chunks (the delta form's rule), not the
+        // decided pair itself; every wave derives the same ones, wave 0 records them.
+        int32_t ca[DIGEST_CAND], cb[DIGEST_CAND];
+        static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+            ca[decltype(J)::value] = -1;
+            cb[decltype(J)::value] = -1;
+        });
+        ca[0] = ma;
+        cb[0] = mb;
+        if (scan && ncand > 1) {
+            // (key << 8 | 255 - block: one owner per value)
+            unsigned long long s[HOT / 64];
+#pragma unroll
+            for (int q = 0; q < HOT / 64; ++q) {
+                const unsigned long long k = dl->bkey[q * 64 + lane];
+                s[q] = k ? (k << 8) | (unsigned long long)(255 - (q * 64 + lane)) : 0ull;
+            }
+            static_for<1, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                if (j >= ncand) return;
+                for (int t = 0; t < 3 && ca[j] < 0; ++t) {
+                    unsigned long long m = 0;
+#pragma unroll
+                    for (int q = 0; q < HOT / 64; ++q) m = s[q] > m ? s[q] : m;
+                    m = wave_max_u64(m);
+                    if (m == 0ull) break;
+#pragma unroll
+                    for (int q = 0; q < HOT / 64; ++q) s[q] = s[q] == m ? 0ull : s[q];
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
+                    const unsigned long long key = (((unsigned long long)hi << 32) | lo) >> 8;
+                    const int32_t pb = 255 - (int32_t)(lo & 255u);
+                    const int32_t pa = (int32_t)(0x1FFFFu - (uint32_t)(key & 0x1FFFFu)) - pb;
+                    const bool ok = pa >= 0 && pa < HOT && pa != pb && !(pa == ma && pb == mb) &&
+                                    (int64_t)(key >> 17) * 16 < n_chunks;
+                    ca[j] = ok ? pa : -1;
+                    cb[j] = ok ? pb : -1;
+                }
+            });
+        }
+        if (scan && r == 0 && lane == 0)
+            static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                dl->pa[j] = j ? ca[j] : -1;   // (slot 0 is applied now and never cached)
+                dl->pb[j] = j ? cb[j] : -1;
+            });
+        uint32_t K1[DIGEST_CAND], K2[DIGEST_CAND];
+        static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+            constexpr int j = decltype(J)::value;
+            const uint32_t da = digest_of(ca[j]), db = digest_of(cb[j]);
+            K1[j] = (da | (db << 8)) * 0x00010001u;
+            K2[j] = (da | (DIGEST_DEAD << 8)) * 0x00010001u;
+        });
+        // the rows of this region's slots: words [j * wpr, j * wpr + nw) of its block, the index
+        // in the bounds-checked offset (a word past the block reads 0 and is never written)
+        const int wpr = (int)((cpr + 31) >> 5), nw = (nc + 31) >> 5;
+        const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(
+            rows + (int64_t)r * DIGEST_CAND * wpr, 0, DIGEST_CAND * wpr * 4, 0x00020000);
         // the byte after the region's last: the digest of the first live token after the region,
         // in byte 0 of lane lp of wave-load gp
         const uint32_t dnext = digest_of(rc.next_tok);
@@ -2052,7 +2163,7 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
             q.z = x[2];
             q.w = x[3];
         };
-        uint32_t rm = 0;   // the round's hit chunks
+        uint32_t rm[DIGEST_CAND];   // the round's hit chunks, per candidate
         auto stage = [&](const uint4 &cur, const uint4 &nxt, uint4 &fre, int g, int i)
                          __attribute__((always_inline)) {
             load(fre, g + DG_LEAD);
@@ -2062,46 +2173,134 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                                                            : (uint32_t)bcast((int32_t)nxt.x, 0);
             const uint32_t d[5] = {d0, cur.y, cur.z, cur.w,
                                    (uint32_t)from_next((int32_t)d0, (int32_t)fill)};
-            uint32_t h = 0;
+            uint32_t sft[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t sft = __builtin_amdgcn_alignbyte(d[e + 1], d[e], 1);
-                h |= hz16(d[e] ^ K1) | hz16(d[e] ^ K2) | hz16(sft ^ K1) | hz16(sft ^ K2);
-            }
+            for (int e = 0; e < 4; ++e) sft[e] = __builtin_amdgcn_alignbyte(d[e + 1], d[e], 1);
             // (the chunks of the wave-load that lie in the region)
             const int v = nc - 4 * g;
             const unsigned long long valid = v >= 4 ? ~0ull : v <= 0 ? 0ull : ((1ull << (16 * v)) - 1ull);
-            const unsigned long long H = __ballot((h & 0x80008000u) != 0u) & valid;
-            if (H != 0ull) {
-                const uint32_t lo = (uint32_t)H, hi = (uint32_t)(H >> 32);
-                const uint32_t b = (uint32_t)((lo & 0xFFFFu) != 0u) | ((uint32_t)((lo >> 16) != 0u) << 1) |
-                                   ((uint32_t)((hi & 0xFFFFu) != 0u) << 2) | ((uint32_t)((hi >> 16) != 0u) << 3);
-                rm |= b << (4 * i);
+            // one more candidate costs compares on the bytes already in registers
+            static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                if (ca[j] < 0) return;
+                // (the stream is bound by these: two instructions per key and two byte pairs)
+                uint32_t m = ~0u;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    m = pk_min16(m, d[e] ^ K1[j]);
+                    m = pk_min16(m, d[e] ^ K2[j]);
+                    m = pk_min16(m, sft[e] ^ K1[j]);
+                    m = pk_min16(m, sft[e] ^ K2[j]);
+                }
+                const unsigned long long H = __ballot((hz16(m) & 0x80008000u) != 0u) & valid;
+                if (H != 0ull) {
+                    const uint32_t lo = (uint32_t)H, hi = (uint32_t)(H >> 32);
+                    const uint32_t b = (uint32_t)((lo & 0xFFFFu) != 0u) | ((uint32_t)((lo >> 16) != 0u) << 1) |
+                                       ((uint32_t)((hi & 0xFFFFu) != 0u) << 2) | ((uint32_t)((hi >> 16) != 0u) << 3);
+                    rm[j] |= b << (4 * i);
+                }
+            });
+        };
+        // The hit chunks of row words [wb, wb + n) (word wb + L in lane L of v) in order, the
+        // loads of the next DG_PF of them in flight: a chunk's content changes only when the
+        // chunk itself is processed, and the wave goes forward, so a chunk loaded early is the
+        // chunk as it will be met.  A pending match takes the chunks from `nextc` on as they are
+        // (synchronous loads), listed or not; `last`: after the region's last word, up to its end.
+        int nextc = 0;   // every chunk before it is done
+        auto apply_words = [&](const uint32_t v, const int wb, const int n, const bool last)
+                               __attribute__((always_inline)) {
+            unsigned long long nz = __ballot(v != 0u);
+            if (n < 64) nz &= (1ull << n) - 1ull;
+            uint32_t bits = 0;
+            int wj = 0;
+            bool fin = !last;   // (the end of the region is met once, as the hit `nc`)
+            auto next_hit = [&]() __attribute__((always_inline)) -> int {
+                if (bits == 0u && nz != 0ull) {
+                    wj = (int)__builtin_ctzll(nz);
+                    nz &= nz - 1ull;
+                    bits = (uint32_t)bcast((int32_t)v, wj);
+                }
+                if (bits != 0u) {
+                    const int c = 32 * (wb + wj) + (int)__builtin_ctz(bits);
+                    bits &= bits - 1u;
+                    if (c < nc) return c;
+                    bits = 0u;   // (no row holds a bit past the region: the scan masks them)
+                    nz = 0ull;
+                }
+                if (fin) return -1;
+                fin = true;
+                return nc;
+            };
+            int cs[DG_PF];
+            Slots X[DG_PF];
+            int32_t F[DG_PF];
+            auto fetch = [&](auto I) __attribute__((always_inline)) {
+                constexpr int i = decltype(I)::value;
+                cs[i] = next_hit();
+                if (cs[i] >= 0 && cs[i] < nc) {
+                    X[i] = load_chunk(cs[i]);
+                    F[i] = load_slot0(cs[i] + 1);
+                }
+            };
+            static_for<0, DG_PF>(fetch);
+            while (cs[0] >= 0) {
+                const int c = cs[0];
+                for (;;) {
+                    const bool pre = ap.match && nextc < c;
+                    if (!pre && c >= nc) break;
+                    const int cc = pre ? nextc : c;
+                    Slots x = X[0];
+                    int32_t f1 = F[0];
+                    if (pre) {
+                        x = load_chunk(cc);
+                        f1 = load_slot0(cc + 1);
+                    }
+                    exact(cc, x, __builtin_amdgcn_readfirstlane(f1));
+                    nextc = cc + 1;
+                    if (!pre) break;
+                }
+                static_for<1, DG_PF>([&](auto I) __attribute__((always_inline)) {
+                    constexpr int i = decltype(I)::value;
+                    cs[i - 1] = cs[i];
+                    X[i - 1] = X[i];
+                    F[i - 1] = F[i];
+                });
+                fetch(std::integral_constant<int, DG_PF - 1>{});
             }
         };
         uint4 S[DG_RING];   // (constant indices only: the ring stays in registers)
-        static_for<0, DG_LEAD>([&](auto i) __attribute__((always_inline)) { load(S[i], i); });
-        const int ng = (nc + 3) >> 2;
-        for (int g0 = 0; g0 < ng; g0 += DG_RING) {
-            rm = 0;
-            static_for<0, DG_RING>([&](auto I) __attribute__((always_inline)) {
-                constexpr int i = decltype(I)::value;
-                stage(S[i], S[(i + 1) % DG_RING], S[(i + DG_LEAD) % DG_RING], g0 + i, i);
-            });
-            if ((rm | (uint32_t)ap.match) != 0u) {
-                // the round's hit chunks in order (a pending match takes the next chunk as it is)
-                const int cb = 4 * g0;
-                for (int k = 0; k < 32;) {
-                    if (!ap.match) {
-                        const uint32_t rest = rm >> k;
-                        if (rest == 0u) break;
-                        k += __builtin_ctz(rest);
-                    }
-                    if (cb + k >= nc) break;
-                    exact(cb + k);
-                    ++k;
+        if (scan) static_for<0, DG_LEAD>([&](auto i) __attribute__((always_inline)) { load(S[i], i); });
+        for (int wb = 0; wb < nw; wb += 64) {
+            const int n = min(64, nw - wb);
+            uint32_t v = 0;
+            if (!scan) {
+                // the decided pair's cached row
+                if (lane < n)
+                    v = __builtin_amdgcn_raw_buffer_load_b32(rws, (use * wpr + wb + lane) * 4, 0, 0);
+            } else {
+                // the plane streamed once: a round's masks are a word of each candidate's row
+                uint32_t row[DIGEST_CAND];
+                static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) { row[decltype(J)::value] = 0; });
+                for (int w = 0; w < n; ++w) {
+                    const int g0 = (wb + w) * DG_RING;
+                    static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) { rm[decltype(J)::value] = 0; });
+                    static_for<0, DG_RING>([&](auto I) __attribute__((always_inline)) {
+                        constexpr int i = decltype(I)::value;
+                        stage(S[i], S[(i + 1) % DG_RING], S[(i + DG_LEAD) % DG_RING], g0 + i, i);
+                    });
+                    static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                        constexpr int j = decltype(J)::value;
+                        row[j] = lane == w ? rm[j] : row[j];
+                    });
                 }
+                static_for<1, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                    constexpr int j = decltype(J)::value;
+                    if (ca[j] >= 0 && lane < n)
+                        __builtin_amdgcn_raw_buffer_store_b32(row[j], rws, (j * wpr + wb + lane) * 4, 0, 0);
+                });
+                v = row[0];
             }
+            apply_words(v, wb, n, wb + 64 >= nw);
         }
     }
     if (ap.n_sites) {
@@ -2109,9 +2308,21 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
         if (lane == 0) sums[r] = o;
     }
     if (lane == 0) {
-        if (ap.n_match) atomicAdd(replaced, (unsigned long long)ap.n_match);
-        if (hits) atomicAdd(n_hits, (unsigned long long)hits);
         site_n[r] = ap.n_sites;
+        // The two counters go through the workgroup (wg_acc: replaced, hits, waves done; zero at
+        // the start): a list iteration's waves all end within microseconds of each other, and
+        // thousands of atomics on one address would then be the launch's critical path.  The
+        // wave that finds itself last adds the workgroup's sums.
+        if (ap.n_match) __hip_atomic_fetch_add(&wg_acc[0], (uint32_t)ap.n_match, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (hits) __hip_atomic_fetch_add(&wg_acc[1], hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const int active = min(WAVES_PER_WG, R - (int)blockIdx.x * WAVES_PER_WG);
+        const uint32_t done = __hip_atomic_fetch_add(&wg_acc[2], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if ((int)done + 1 == active) {
+            const uint32_t m = __hip_atomic_load(&wg_acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const uint32_t h = __hip_atomic_load(&wg_acc[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (m) atomicAdd(replaced, (unsigned long long)m);
+            if (h) atomicAdd(n_hits, (unsigned long long)h);
+        }
     }
 }
 
@@ -2125,12 +2336,18 @@ k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
              const RegionCarry *__restrict__ carry, LoopCtl *__restrict__ ctl,
              RegionSum *__restrict__ sums, unsigned long long *__restrict__ replaced,
              uint32_t *__restrict__ site_list, uint32_t *__restrict__ site_n,
-             uint32_t *__restrict__ plane) {
+             uint32_t *__restrict__ plane, DigestLists *__restrict__ dl,
+             uint32_t *__restrict__ rows) {
     if (ctl->status != LOOP_RUN || !ctl->delta) return;
-    if (ctl->digest_ok)
+    if (ctl->digest_ok) {
+        // (from the decided pair's cached row when the decision found one, DigestLists::use; else
+        // the plane streamed for it and the predicted pairs)
+        __shared__ uint32_t wg_acc[3];
+        if (threadIdx.x < 3) wg_acc[threadIdx.x] = 0;
+        __syncthreads();
         digest_body(ids, plane, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, sums, replaced,
-                    site_list, site_n, &ctl->digest_hits);
-    else
+                    site_list, site_n, &ctl->digest_hits, dl, rows, ctl->digest_cand, dl->use, wg_acc);
+    } else
         step_body<MERGE_XY, MODE_NONE, true, true, true>(
             nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,
             ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n);

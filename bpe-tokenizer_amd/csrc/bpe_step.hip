@@ -37,15 +37,16 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
 
 // The delta form's apply-only stream (k_apply_loop): the same ring, built with the same flags,
 // and beside it the stream over the digest plane (digest_body; plane: one byte per slot, read
-// only when the LoopCtl says it is fresh).
+// only when the LoopCtl says it is fresh; lists, rows: the hit lists of the candidate pairs).
 hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, void *ctl, void *sums,
                              unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
-                             uint32_t *plane) {
+                             uint32_t *plane, void *lists, uint32_t *rows) {
     using namespace bpe;
     k_apply_loop<<<grid, WG, 0, s>>>(ids, n_chunks, cpr, R, static_cast<const RegionCarry *>(carry),
                                      static_cast<LoopCtl *>(ctl), static_cast<RegionSum *>(sums),
-                                     replaced, site_list, site_n, plane);
+                                     replaced, site_list, site_n, plane,
+                                     static_cast<DigestLists *>(lists), rows);
     return hipGetLastError();
 }
 

@@ -167,6 +167,11 @@ int bpe_merge_until(bpe_ctx *ctx, int64_t max_length, int64_t min_weight, int64_
 #define BPE_DIGEST_MOD 254
 #define BPE_DIGEST_SEP 254
 #define BPE_DIGEST_DEAD 255
+/* Candidate pairs one stream of the plane answers for: the decided merge and the predicted next
+ * ones, whose hit lists (one bit per chunk) are kept and applied from without another stream.
+ * BPE_DIGEST_CAND=n in the environment caps the candidates in use (1 .. this constant, read per
+ * batch); at 1 every delta iteration streams the plane. */
+#define BPE_DIGEST_CAND 4
 /* out[i] = the digest of the slot value ids[i] (host arrays; needs no context and no device). */
 int bpe_digest(const int32_t *ids, int64_t n, uint8_t *out);
 
@@ -344,6 +349,9 @@ typedef struct {
     int64_t digest_hits;      /* ... the chunks those streams took to the exact path (true sites,
                                  digest aliases, an a-alike last in its chunk, pending matches) */
     int64_t digest_builds;    /* builds of the digest plane (one pass over the int32 corpus each) */
+    int64_t digest_scans;     /* ... of the digest_passes, those that streamed the plane (and filled the
+                                 hit lists of up to BPE_DIGEST_CAND pairs); the others applied their
+                                 merge from a cached list */
 } bpe_stats;
 
 int bpe_stats_enable(bpe_ctx *ctx, int on);
