@@ -46,6 +46,8 @@ C_API = [
     'bpe_decode_batch', 'bpe_decode_batch_device', 'bpe_decoder_get_stats', 'bpe_decoder_reset_stats',
     'bpe_encoder_set_chars', 'bpe_encoder_set_vector_index', 'bpe_encode_text_batch',
     'bpe_encode_text_batch_device', 'bpe_encoder_get_text_stats', 'bpe_encoder_reset_text_stats',
+    'bpe_set_chars', 'bpe_add_text_batch', 'bpe_add_text_batch_device', 'bpe_get_ingest_stats',
+    'bpe_reset_ingest_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -145,6 +147,15 @@ class TextStats(ctypes.Structure):
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units_in', ctypes.c_int64),
                 ('chars', ctypes.c_int64), ('values_out', ctypes.c_int64),
                 ('front_ms', ctypes.c_double), ('back_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class IngestStats(ctypes.Structure):
+    """bpe_ingest_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units', ctypes.c_int64),
+                ('chars', ctypes.c_int64), ('new_chars', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -252,6 +263,13 @@ def lib():
                                           i64p], ctypes.c_int),
         'bpe_encoder_get_text_stats': ([vp, ctypes.POINTER(TextStats)], ctypes.c_int),
         'bpe_encoder_reset_text_stats': ([vp], ctypes.c_int),
+        'bpe_set_chars': ([vp, vp, i32p, ctypes.c_int64], ctypes.c_int),
+        'bpe_add_text_batch': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64],
+                               ctypes.c_int),
+        'bpe_add_text_batch_device': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p,
+                                       ctypes.c_int64], ctypes.c_int),
+        'bpe_get_ingest_stats': ([vp, ctypes.POINTER(IngestStats)], ctypes.c_int),
+        'bpe_reset_ingest_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -379,6 +397,72 @@ class Engine:
                                     hist.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
                'bpe_add_latin1')
         return cmap, nt.value, hist
+
+    # corpus from text: addToCorpus (core.ts:182-207) for batches of UTF-16 texts -------------------
+    def set_chars(self, mapping):
+        """Replaces the context's char table (char_to_token): a dict of a str of one code point (a
+        lone surrogate included), or an int code point, to a token id.  An empty dict drops it."""
+        cps = np.asarray([ord(k) if isinstance(k, str) else int(k) for k in mapping], dtype=np.uint32)
+        ids = _i32(list(mapping.values()))
+        cbuf = cps if cps.size else np.zeros(1, np.uint32)
+        ibuf = ids if ids.size else np.zeros(1, np.int32)
+        _check(lib().bpe_set_chars(self._ctx, cbuf.ctypes.data, ibuf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                   cps.size), 'bpe_set_chars')
+
+    def _add_text(self, fn, what, units_ptr, off_ptr, n, new_cap):
+        """One call; a new_chars buffer that turns out too small is retried once with room."""
+        hist = np.zeros(MAX_VOCAB, np.int64)
+        n_new = ctypes.c_int64()
+        for _ in range(2):
+            new = np.zeros(max(new_cap, 1), np.uint32)
+            rc = fn(self._ctx, units_ptr, off_ptr, n, new.ctypes.data, new_cap, ctypes.byref(n_new),
+                    hist.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), MAX_VOCAB)
+            if rc == ERR_ARG and n_new.value > new_cap:
+                new_cap = n_new.value
+                continue
+            break
+        _check(rc, what)
+        return new[:n_new.value].copy(), hist[:self.num_tokens()].copy()
+
+    def add_text_flat(self, units, off, new_cap=1024):
+        """Flat form (bpe_add_text_batch): texts units[off[k]:off[k+1]] (UTF-16 units), each one
+        sample -> (new_chars uint32: the code point of every char token the call created, in id
+        order from the token count before it; hist int64: this call's occurrences per token id)."""
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        return self._add_text(lib().bpe_add_text_batch, 'bpe_add_text_batch', src.ctypes.data,
+                              off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1, new_cap)
+
+    def add_text(self, texts, new_cap=1024):
+        """texts: a list of str (encoded with surrogatepass: lone surrogates survive) -> (new_chars, hist)."""
+        parts = [_units(t) for t in texts]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        units = np.concatenate(parts).astype(np.uint16) if parts and off[-1] else np.zeros(0, np.uint16)
+        return self.add_text_flat(units, off, new_cap)
+
+    def add_text_tensors(self, units, off, new_cap=1024):
+        """Device form (bpe_add_text_batch_device): units a torch int16 or uint16 tensor and off a
+        torch int64 tensor on the context's device -> (new_chars, hist) as numpy arrays."""
+        import torch
+        if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+            raise BpeError('add_text_tensors takes int16 or uint16 units and int64 offsets', ERR_ARG)
+        if not (units.is_cuda and off.is_cuda and units.device == off.device):
+            raise BpeError('add_text_tensors takes tensors on the context\'s device', ERR_ARG)
+        units, off = units.contiguous(), off.contiguous()
+        torch.cuda.synchronize(units.device)   # (the context runs on a stream of its own)
+        up = units.data_ptr() if units.numel() else None
+        return self._add_text(lib().bpe_add_text_batch_device, 'bpe_add_text_batch_device', up,
+                              off.data_ptr(), off.numel() - 1, new_cap)
+
+    def ingest_stats(self):
+        s = IngestStats()
+        _check(lib().bpe_get_ingest_stats(self._ctx, ctypes.byref(s)), 'bpe_get_ingest_stats')
+        return s.as_dict()
+
+    def reset_ingest_stats(self):
+        _check(lib().bpe_reset_ingest_stats(self._ctx), 'bpe_reset_ingest_stats')
 
     def clear_corpus(self):
         _check(lib().bpe_clear_corpus(self._ctx), 'bpe_clear_corpus')

@@ -17,9 +17,8 @@ namespace {
 
 // An engine handle: the context behind a JS external.  destroyEngine() frees the context (its
 // device memory) at once; the holder itself goes with the external's finalizer.
-struct Holder {
-    bpe_ctx *c = nullptr;
-};
+// (napi_util.h: bpe_ingest_napi.cc reads the same handle)
+using Holder = EngineHolder;
 
 void finalize_ctx(napi_env, void *data, void *) {
     Holder *h = static_cast<Holder *>(data);

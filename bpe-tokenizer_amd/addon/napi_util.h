@@ -1,5 +1,6 @@
-// napi_util.h — what the two N-API modules (bpe_napi.cc, bpe_decode_napi.cc) share: errors as JS
-// exceptions carrying bpe_last_error(), and argument access.
+// napi_util.h — what the N-API modules (bpe_napi.cc, bpe_decode_napi.cc, bpe_text_napi.cc,
+// bpe_ingest_napi.cc) share: errors as JS exceptions carrying bpe_last_error(), argument access, and
+// the engine handle.
 #pragma once
 #include <node_api.h>
 
@@ -9,6 +10,12 @@
 #include "bpe.h"
 
 namespace {
+
+// What an engine handle (bpe_napi.node createEngine's JS external) points to; the modules that take
+// such a handle read the context through it.
+struct EngineHolder {
+    bpe_ctx *c = nullptr;
+};
 
 napi_value throw_native(napi_env env, const char *what) {
     char buf[1024];
@@ -29,7 +36,7 @@ bool get_args(napi_env env, napi_callback_info info, size_t want, napi_value *ar
     return argc >= want;
 }
 
-int64_t get_i64(napi_env env, napi_value v) {
+inline int64_t get_i64(napi_env env, napi_value v) {
     int64_t x = 0;
     napi_get_value_int64(env, v, &x);
     return x;

@@ -44,6 +44,7 @@
 
 #include "bpe.h"
 #include "bpe_multi.h"   // bpe_fail
+#include "bpe_text_front.hip.h"   // wave scans and the text front end shared with the corpus ingest
 
 namespace {
 
@@ -74,13 +75,8 @@ __host__ __device__ __forceinline__ uint32_t rank_home(uint32_t key, uint32_t sh
     return (key * 0x9E3779B1u) >> shift;
 }
 
-// Wave reductions on the VALU: DPP row rotations / shifts inside each 16-lane row, then the four
-// row results through v_readlane (no LDS crossbar round trips, unlike __shfl_*).
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v, uint32_t old) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, 0xF, 0xF, false);
-}
-
+// Wave reductions on the VALU (dpp, wave_incl and block_scan: bpe_text_front.hip.h): DPP row
+// rotations inside each 16-lane row, then the four row results through v_readlane.
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     v = min(v, dpp<0x128>(v, v));   // row_ror:8
     v = min(v, dpp<0x124>(v, v));   // row_ror:4
@@ -89,18 +85,6 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     const uint32_t a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
     const uint32_t c = __builtin_amdgcn_readlane((int)v, 32), d = __builtin_amdgcn_readlane((int)v, 48);
     return min(min(a, b), min(c, d));
-}
-
-__device__ __forceinline__ int wave_incl(int v, int lane) {
-    uint32_t u = (uint32_t)v;
-    u += dpp<0x111>(u, 0);   // row_shr:1 (lanes without a source add 0)
-    u += dpp<0x112>(u, 0);   // row_shr:2
-    u += dpp<0x114>(u, 0);   // row_shr:4
-    u += dpp<0x118>(u, 0);   // row_shr:8
-    const int r = lane >> 4;
-    const int t0 = __builtin_amdgcn_readlane((int)u, 15), t1 = __builtin_amdgcn_readlane((int)u, 31);
-    const int t2 = __builtin_amdgcn_readlane((int)u, 47);
-    return (int)u + (r >= 1 ? t0 : 0) + (r >= 2 ? t1 : 0) + (r >= 3 ? t2 : 0);
 }
 
 // minimum over the workgroup (one barrier; `m` holds one word per wave)
@@ -115,30 +99,6 @@ __device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t *m) {
 #pragma unroll
     for (int i = 1; i < WG / 64; ++i) r = min(r, m[i]);
     return r;
-}
-
-// exclusive prefix and total over the workgroup (one barrier; `s` holds one word per wave)
-template <int WG>
-__device__ __forceinline__ int block_scan(int v, int *s, int &total) {
-    const int lane = threadIdx.x & 63;
-    const int incl = wave_incl(v, lane);
-    if (WG == 64) {
-        total = __builtin_amdgcn_readlane(incl, 63);
-        __syncthreads();   // (this step's flags, written by other lanes, are read next)
-        return incl - v;
-    }
-    const int w = threadIdx.x >> 6;
-    if (lane == 63) s[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < WG / 64; ++i) {
-        const int x = s[i];
-        before += i < w ? x : 0;
-        all += x;
-    }
-    total = all;
-    return before + incl - v;
 }
 
 // The rank table copied into LDS (the latency form: few texts per call, each on a CU of its own):

@@ -11,6 +11,7 @@
 #include "bpe_kernels.hip.h"
 #include "bpe_pix.hip.h"
 #include "bpe.h"
+#include "bpe_ingest.hip.h"   // the corpus ingest from text (with bpe_text_front.hip.h, the encoder's front end)
 #include "bpe_multi.h"
 #include "bpe_tools.h"
 
@@ -236,7 +237,11 @@ struct bpe_ctx {
     uint32_t pix_lane[3] = {0, 0, 0}, pix_lane_prev[3] = {0, 0, 0};
     int64_t pix_nw_last = 0;   // words the last rank-loop batch all-reduced (its pending merge's)
     bool pix_first_pending = false;
+    // the corpus ingest from text: char table, scratch and counters (made by its first call)
+    struct IngestState *ing = nullptr;
 };
+
+void ingest_free(bpe_ctx *c);
 
 namespace {
 
@@ -2813,6 +2818,7 @@ int bpe_destroy(bpe_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rank_rccl_forget(c);
     pix_free(c);
+    ingest_free(c);
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -3467,6 +3473,372 @@ int bpe_get_stream(bpe_ctx *c, void **stream) {
     if (stream) MULTI(get_stream(c->multi, stream));
     if (!c || !stream) return fail(BPE_ERR_ARG, "bpe native: null argument");
     *stream = (void *)c->stream;
+    return BPE_OK;
+}
+
+}  // extern "C"
+
+// ---- corpus from text (bpe_add_text_batch, include/bpe.h): bpe_ingest.hip.h's kernels around the
+// host's numbering of the new chars, appended through append_begin / seal_packed ------------------
+struct IngestState {
+    // the char table (host copy; uploaded when dirty): an empty one knows no char
+    std::vector<uint16_t> bmp;
+    std::vector<uint2> pairs;
+    uint32_t pair_bits = 4;
+    int64_t n_pairs = 0;
+    bool dirty = true;
+    uint16_t *d_bmp = nullptr;
+    uint2 *d_pairs = nullptr;
+    size_t d_pairs_n = 0;
+    // a call's device words: the new chars' planes and list, the counts, the status words
+    unsigned long long *d_first = nullptr, *d_sup_pos = nullptr, *d_hist = nullptr, *d_st = nullptr, *d_out = nullptr;
+    uint32_t *d_sup_keys = nullptr, *d_list = nullptr;
+    char *d_buf = nullptr;   // tile counts, first texts, tile marks, and the host form's units and offsets
+    size_t buf_bytes = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bpe_ingest_stats st{};
+    IngestState() : bmp(65536, CHAR_UNKNOWN), pairs(16, make_uint2(PAIR_EMPTY, 0u)) {}
+};
+
+void ingest_free(bpe_ctx *c) {
+    IngestState *I = c->ing;
+    if (!I) return;
+    void *ptrs[] = {I->d_bmp, I->d_pairs, I->d_first, I->d_sup_pos, I->d_hist, I->d_st,
+                    I->d_out, I->d_sup_keys, I->d_list, I->d_buf};
+    for (void *p : ptrs) dfree(p);
+    for (hipEvent_t ev : I->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    delete I;
+    c->ing = nullptr;
+}
+
+namespace {
+
+constexpr size_t ING_OUT_CAP = BPE_MAX_VOCAB;   // (more new chars than that: the call fails first)
+
+// The context's ingest state, with its fixed device words (made by the first call that needs them).
+int ingest_state(bpe_ctx *c, IngestState **out, bool device) {
+    if (!c->ing) c->ing = new IngestState();
+    IngestState *I = *out = c->ing;
+    if (!device || I->d_st) return BPE_OK;
+    int rc;
+    if ((rc = dev_alloc(&I->d_bmp, 65536)) || (rc = dev_alloc(&I->d_first, 65536)) ||
+        (rc = dev_alloc(&I->d_sup_pos, ING_SUP_SLOTS)) || (rc = dev_alloc(&I->d_sup_keys, ING_SUP_SLOTS)) ||
+        (rc = dev_alloc(&I->d_list, ING_LIST_CAP)) || (rc = dev_alloc(&I->d_hist, BPE_MAX_VOCAB)) ||
+        (rc = dev_alloc(&I->d_out, 2 * ING_OUT_CAP)))
+        return rc;
+    for (hipEvent_t &ev : I->ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    if ((rc = dev_alloc(&I->d_st, IS_WORDS))) return rc;   // (last: marks the state complete)
+    return BPE_OK;
+}
+
+void ingest_table_put(IngestState *I, uint32_t cp, uint32_t id) {
+    I->dirty = true;
+    if (cp <= 0xFFFFu) {
+        I->bmp[cp] = (uint16_t)id;
+        return;
+    }
+    if (2 * (I->n_pairs + 1) > (int64_t)I->pairs.size()) {   // grow: load factor <= 1/2
+        std::vector<uint2> old;
+        old.swap(I->pairs);
+        I->pair_bits += 1;
+        I->pairs.assign((size_t)1 << I->pair_bits, make_uint2(PAIR_EMPTY, 0u));
+        I->n_pairs = 0;
+        for (const uint2 &e : old)
+            if (e.x != PAIR_EMPTY) ingest_table_put(I, e.x, e.y);
+    }
+    const uint32_t mask = (1u << I->pair_bits) - 1;
+    uint32_t h = pair_home(cp, 32 - I->pair_bits);
+    while (I->pairs[h].x != PAIR_EMPTY && I->pairs[h].x != cp) h = (h + 1) & mask;
+    if (I->pairs[h].x == PAIR_EMPTY) I->n_pairs += 1;
+    I->pairs[h] = make_uint2(cp, id);
+}
+
+int ingest_table_upload(bpe_ctx *c, IngestState *I) {
+    if (!I->dirty) return BPE_OK;
+    if (I->pairs.size() > I->d_pairs_n) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dfree(I->d_pairs);
+        I->d_pairs_n = 0;
+        int rc = dev_alloc(&I->d_pairs, I->pairs.size());
+        if (rc) return rc;
+        I->d_pairs_n = I->pairs.size();
+    }
+    HIP_TRY(hipMemcpyAsync(I->d_bmp, I->bmp.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(I->d_pairs, I->pairs.data(), I->pairs.size() * sizeof(uint2), hipMemcpyHostToDevice,
+                           c->stream));
+    // (the host vectors may change right after: the copies must be done)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    I->dirty = false;
+    return BPE_OK;
+}
+
+size_t ing_align(size_t n) { return (n + 15) & ~(size_t)15; }
+
+}  // namespace
+
+// New char tokens nt, nt + 1, ... for the code points cps[0 .. n) (nt = the token count): registered
+// with their len16 and put into the char table.  (bpe_multi.cpp: every shard learns every token.)
+int ingest_learn(bpe_ctx *c, const uint32_t *cps, int64_t n) {
+    if (!c || c->multi || n < 0 || (n && !cps)) return fail(BPE_ERR_ARG, "bpe native: bad ingest_learn arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    IngestState *I;
+    if ((rc = ingest_state(c, &I, false))) return rc;
+    const int64_t nt0 = (int64_t)c->h_len16.size();
+    if (nt0 + n > BPE_MAX_VOCAB) return fail(BPE_ERR_VOCAB, "bpe native: vocab limit");
+    if ((rc = ensure_vocab(c, nt0 + n))) return rc;
+    for (int64_t i = 0; i < n; ++i) {
+        ingest_table_put(I, cps[i], (uint32_t)(nt0 + i));
+        c->h_len16[nt0 + i] = cps[i] > 0xFFFFu ? 2 : 1;
+    }
+    if (n) mark_len16(c, nt0);
+    return BPE_OK;
+}
+
+// The pipeline.  dev: units and off are device buffers.  number_only: the new chars are numbered
+// and reported (every check made) and nothing is changed (bpe_multi.cpp numbers a whole batch on
+// one shard before its shards take their parts).
+int ingest_text(bpe_ctx *c, const uint16_t *units, const int64_t *off, int64_t n_texts, bool dev, bool number_only,
+                uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    if (!c || c->multi || !n_new || n_texts < 0 || n_texts >= 0x7FFFFFFF || new_cap < 0 || hist_cap < 0 ||
+        (n_texts && !off) || (new_cap && !new_chars) || (hist_cap && !id_hist))
+        return fail(BPE_ERR_ARG, "bpe native: bad add_text_batch arguments");
+    *n_new = 0;
+    int rc = set_device(c);
+    if (rc) return rc;
+    IngestState *I;
+    if ((rc = ingest_state(c, &I, true))) return rc;
+    hipStream_t s = c->stream;
+    if (!number_only) I->st.calls++;
+    std::vector<int64_t> off_copy;
+    const int64_t *h_off = off;
+    if (dev && n_texts) {
+        off_copy.resize((size_t)n_texts + 1);
+        HIP_TRY(hipMemcpyAsync(off_copy.data(), off, off_copy.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        h_off = off_copy.data();
+    }
+    if (n_texts && h_off[0] < 0) return fail(BPE_ERR_ARG, "bpe native: negative text offset");
+    for (int64_t k = 0; k < n_texts; ++k)
+        if (h_off[k + 1] < h_off[k]) return fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+    const int64_t base = n_texts ? h_off[0] : 0, total = n_texts ? h_off[n_texts] - base : 0;
+    if (total && !units) return fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+    const int64_t nt0 = (int64_t)c->h_len16.size();
+    const int mis = dev && total ? (int)(((uintptr_t)(units + base) >> 1) & (TXT_RUN - 1)) : 0;
+    const int64_t n_tiles = (total + mis + TXT_TILE - 1) / TXT_TILE;
+    if (n_tiles > 0x7FFFFFFF) return fail(BPE_ERR_ARG, "bpe native: text batch too large");
+
+    // device: [tile counts, then bases | first text of each tile | tile marks | units | off]
+    // (the last two: the host form's staging)
+    const uint16_t *units_al = nullptr;
+    const int64_t *k_off = nullptr;
+    unsigned long long *d_tiles = nullptr;
+    long long *d_tfirst = nullptr;
+    uint32_t *d_edge = nullptr;
+    int64_t chars = 0, n_list = 0;
+    std::vector<unsigned long long> fresh;   // (position, code point) pairs
+    std::vector<unsigned long long> h_st(IS_WORDS, 0);
+    float ms = 0, ms2 = 0;
+    if (total) {
+        if ((rc = ingest_table_upload(c, I))) return rc;
+        const size_t b_tiles = ing_align((size_t)n_tiles * 8), b_edge = ing_align((size_t)n_tiles * 4);
+        const size_t b_units = dev ? 0 : ing_align((size_t)total * 2), b_off = dev ? 0 : (size_t)(n_texts + 1) * 8;
+        const size_t bytes = 2 * b_tiles + b_edge + b_units + b_off;
+        if (bytes > I->buf_bytes) {
+            HIP_TRY(hipStreamSynchronize(s));
+            dfree(I->d_buf);
+            I->buf_bytes = 0;
+            if ((rc = dev_alloc(&I->d_buf, bytes + bytes / 4))) return rc;
+            I->buf_bytes = bytes + bytes / 4;
+        }
+        char *d = I->d_buf;
+        d_tiles = reinterpret_cast<unsigned long long *>(d);
+        d_tfirst = reinterpret_cast<long long *>(d += b_tiles);
+        d_edge = reinterpret_cast<uint32_t *>(d += b_tiles);
+        uint16_t *d_units = reinterpret_cast<uint16_t *>(d += b_edge);
+        int64_t *d_uoff = reinterpret_cast<int64_t *>(d += b_units);
+        if (dev) {
+            units_al = units + base - mis;
+            k_off = off;
+        } else {
+            HIP_TRY(hipMemcpyAsync(d_units, units + base, (size_t)total * 2, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_uoff, off, (size_t)(n_texts + 1) * 8, hipMemcpyHostToDevice, s));
+            units_al = d_units;
+            k_off = d_uoff;
+        }
+        HIP_TRY(hipMemsetAsync(I->d_st, 0, IS_WORDS * 8, s));
+        HIP_TRY(hipMemsetAsync(I->d_first, 0xFF, 65536 * 8, s));
+        HIP_TRY(hipMemsetAsync(I->d_sup_pos, 0xFF, (size_t)ING_SUP_SLOTS * 8, s));
+        HIP_TRY(hipMemsetAsync(I->d_sup_keys, 0xFF, (size_t)ING_SUP_SLOTS * 4, s));
+        HIP_TRY(hipMemsetAsync(d_tfirst, 0xFF, (size_t)n_tiles * 8, s));
+        HIP_TRY(hipMemsetAsync(d_edge, 0, (size_t)n_tiles * 4, s));
+        const CharTab ct{I->d_bmp, I->d_pairs, (1u << I->pair_bits) - 1, 32 - I->pair_bits};
+        const IngNew nw{I->d_first, I->d_sup_keys, I->d_sup_pos, I->d_list, I->d_st};
+        HIP_TRY(hipEventRecord(I->ev[0], s));
+        k_txt_count<<<(unsigned)((n_tiles + TXT_CNT_TILES - 1) / TXT_CNT_TILES), TXT_WG, 0, s>>>(units_al, mis, total,
+                                                                                              n_tiles, d_tiles);
+        k_txt_texts<<<(unsigned)std::min<int64_t>((n_texts + 256) / 256, 2048), 256, 0, s>>>(
+            units_al, mis, total, k_off, n_texts, base, n_tiles, d_tfirst, d_edge, d_tiles);
+        k_txt_scan<<<1, 1024, 0, s>>>(d_tiles, n_tiles, I->d_st);
+        k_ing_discover<<<(unsigned)n_tiles, TXT_WG, 0, s>>>(units_al, mis, total, ct, d_tfirst, d_edge, k_off, n_texts,
+                                                           base, nw);
+        k_ing_collect<<<64, 256, 0, s>>>(nw, I->d_out, (uint32_t)ING_OUT_CAP);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(I->ev[1], s));
+        HIP_TRY(hipMemcpyAsync(h_st.data(), I->d_st, IS_WORDS * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipEventElapsedTime(&ms, I->ev[0], I->ev[1]));
+        I->st.kernel_ms += ms;
+        chars = (int64_t)h_st[TS_CHARS];
+        n_list = (int64_t)h_st[IS_NLIST];
+        if (chars < 0 || chars > total) return fail(BPE_ERR_STATE, "bpe native: bad char count");
+        if (h_st[IS_OVER] || nt0 + n_list > BPE_MAX_VOCAB) {
+            if (!h_st[IS_OVER]) *n_new = n_list;
+            return fail(BPE_ERR_VOCAB, "bpe native: vocab is limited to 55295 tokens (UTF-16 surrogates)");
+        }
+        if (n_list) {
+            // first-appearance order for unseen chars (core.ts:186-199)
+            fresh.resize(2 * (size_t)n_list);
+            HIP_TRY(hipMemcpyAsync(fresh.data(), I->d_out, fresh.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            std::vector<std::pair<unsigned long long, uint32_t>> order((size_t)n_list);
+            for (int64_t i = 0; i < n_list; ++i) order[i] = {fresh[2 * i], (uint32_t)fresh[2 * i + 1]};
+            std::sort(order.begin(), order.end());
+            for (int64_t i = 0; i < n_list; ++i) fresh[i] = order[i].second;
+        }
+    }
+    const int64_t nt1 = nt0 + n_list;
+    *n_new = n_list;
+    if (n_list > new_cap) return fail(BPE_ERR_ARG, "bpe native: new_chars too small (see *n_new)");
+    if (hist_cap < nt1) return fail(BPE_ERR_ARG, "bpe native: id_hist too small for the token count after the call");
+    if (number_only) {
+        for (int64_t i = 0; i < n_list; ++i) new_chars[i] = (uint32_t)fresh[i];
+        return BPE_OK;
+    }
+    if (n_texts == 0) {
+        std::fill(id_hist, id_hist + nt1, (int64_t)0);
+        return BPE_OK;
+    }
+    // from here on the call succeeds (device failures aside)
+    const int64_t extra = chars + n_texts;
+    if ((rc = append_begin(c, extra))) return rc;
+    if (n_list) {
+        std::vector<uint32_t> cps((size_t)n_list);
+        for (int64_t i = 0; i < n_list; ++i) cps[i] = (uint32_t)fresh[i];
+        if ((rc = ingest_learn(c, cps.data(), n_list))) return rc;
+        for (int64_t i = 0; i < n_list; ++i) new_chars[i] = cps[i];
+    }
+    int32_t *dst = c->d_ids + c->live_slots;
+    std::vector<unsigned long long> hist((size_t)nt1, 0);
+    if (total) {
+        if ((rc = ingest_table_upload(c, I))) return rc;   // (a batch with no new char uploads nothing)
+        const CharTab ct{I->d_bmp, I->d_pairs, (1u << I->pair_bits) - 1, 32 - I->pair_bits};
+        if (nt1) HIP_TRY(hipMemsetAsync(I->d_hist, 0, (size_t)nt1 * 8, s));
+        int64_t grid = std::min<int64_t>(n_tiles, 1024);
+        grid = std::max(grid, (n_tiles + ING_MAX_TILES_PER_WG - 1) / ING_MAX_TILES_PER_WG);
+        HIP_TRY(hipEventRecord(I->ev[2], s));
+        k_ing_map<<<(unsigned)grid, TXT_WG, 0, s>>>(units_al, mis, total, n_tiles, ct, d_tiles, d_tfirst, d_edge, k_off,
+                                                    n_texts, base, SEP, dst, I->d_hist, I->d_st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(I->ev[3], s));
+        if (nt1) HIP_TRY(hipMemcpyAsync(hist.data(), I->d_hist, (size_t)nt1 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_st.data(), I->d_st, IS_WORDS * 8, hipMemcpyDeviceToHost, s));
+    } else {
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)dst, SEP, (size_t)n_texts, s));
+    }
+    c->live_slots += extra;
+    c->n_samples += n_texts;
+    c->n_live += chars;
+    if ((rc = seal_packed(c))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (total) {
+        HIP_TRY(hipEventElapsedTime(&ms2, I->ev[2], I->ev[3]));
+        I->st.kernel_ms += ms2;
+        if (h_st[IS_OVER]) return fail(BPE_ERR_STATE, "bpe native: the char table lost a char of the batch");
+    }
+    for (int64_t id = 0; id < nt1; ++id) {
+        c->h_count[id] += (int64_t)hist[id];
+        id_hist[id] = (int64_t)hist[id];
+    }
+    I->st.texts += n_texts;
+    I->st.units += total;
+    I->st.chars += chars;
+    I->st.new_chars += n_list;
+    return BPE_OK;
+}
+
+int ingest_kernel_ms(bpe_ctx *c, double *ms, bool reset) {
+    if (!c || c->multi || !ms) return fail(BPE_ERR_ARG, "bpe native: bad shard context");
+    *ms = c->ing ? c->ing->st.kernel_ms : 0.0;
+    if (reset && c->ing) c->ing->st = bpe_ingest_stats{};
+    return BPE_OK;
+}
+
+extern "C" {
+
+int bpe_set_chars(bpe_ctx *c, const uint32_t *code_points, const int32_t *ids, int64_t n) {
+    if (!c || n < 0 || (n && (!code_points || !ids))) return fail(BPE_ERR_ARG, "bpe native: bad set_chars arguments");
+    MULTI(set_chars(c->multi, code_points, ids, n));
+    int rc = set_device(c);
+    if (rc) return rc;
+    IngestState *I;
+    if ((rc = ingest_state(c, &I, false))) return rc;
+    // checked and built aside: a failed call changes nothing
+    int32_t mx = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        if (code_points[i] > 0x10FFFFu) return fail(BPE_ERR_ARG, "bpe native: code point above U+10FFFF");
+        if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB) return fail(BPE_ERR_VOCAB, "bpe native: char token id out of range");
+        mx = std::max(mx, ids[i]);
+    }
+    IngestState T;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t cp = code_points[i];
+        const int64_t before = T.n_pairs;
+        if (cp <= 0xFFFFu && T.bmp[cp] != CHAR_UNKNOWN) return fail(BPE_ERR_ARG, "bpe native: duplicate code point");
+        ingest_table_put(&T, cp, (uint32_t)ids[i]);
+        if (cp > 0xFFFFu && T.n_pairs == before) return fail(BPE_ERR_ARG, "bpe native: duplicate code point");
+    }
+    const int64_t nt0 = (int64_t)c->h_len16.size();
+    if ((rc = ensure_vocab(c, (int64_t)mx + 1))) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        if (ids[i] >= nt0) c->h_len16[ids[i]] = code_points[i] > 0xFFFFu ? 2 : 1;
+    I->bmp.swap(T.bmp);
+    I->pairs.swap(T.pairs);
+    I->pair_bits = T.pair_bits;
+    I->n_pairs = T.n_pairs;
+    I->dirty = true;
+    return BPE_OK;
+}
+
+int bpe_add_text_batch(bpe_ctx *c, const uint16_t *units, const int64_t *off, int64_t n_texts, uint32_t *new_chars,
+                       int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    if (c && c->multi && n_new)
+        return multi_add_text_batch(c->multi, units, off, n_texts, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+    return ingest_text(c, units, off, n_texts, false, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_add_text_batch_device(bpe_ctx *c, const uint16_t *d_units, const int64_t *d_off, int64_t n_texts,
+                              uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                              int64_t hist_cap) {
+    if (c && c->multi && n_new)
+        return multi_add_text_batch(c->multi, d_units, d_off, n_texts, true, new_chars, new_cap, n_new, id_hist,
+                                    hist_cap);
+    return ingest_text(c, d_units, d_off, n_texts, true, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_get_ingest_stats(bpe_ctx *c, bpe_ingest_stats *out) {
+    if (out) MULTI(get_ingest_stats(c->multi, out));
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = c->ing ? c->ing->st : bpe_ingest_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_ingest_stats(bpe_ctx *c) {
+    MULTI(reset_ingest_stats(c->multi));
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    if (c->ing) c->ing->st = bpe_ingest_stats{};
     return BPE_OK;
 }
 

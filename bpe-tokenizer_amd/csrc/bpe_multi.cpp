@@ -69,6 +69,7 @@ struct bpe_multi {
     int64_t cold_cap = 0;
     unsigned long long *h_buf = nullptr, *h_sum = nullptr;   // pinned, BPE_XCHG_WORDS each
     std::vector<std::vector<int32_t>> staged;            // samples not yet on a device
+    bpe_ingest_stats ing{};                              // text ingest calls (kernel_ms: the shards')
     bool distributed = false;
     // the maintained state (every shard holds the global tables, bpe_set_global_counts), and the
     // host-protocol iterations in a row that needed exact cold counts (two: enter that state)
@@ -539,6 +540,105 @@ int multi_add_latin1(bpe_multi *m, const uint8_t *bytes, int64_t n, int64_t samp
     // every shard knows every token (new ids are numbered by the vocabulary size)
     for (int32_t id = nt0; id < *n_tokens_io; ++id) MTRY(multi_set_token_len16(m, id, 1));
     return drop_global(m);
+}
+
+// ---- corpus from text (bpe_add_text_batch) -----------------------------------------------------------
+// One char table: every shard holds a copy, and every shard learns every new char before any shard
+// takes its part of the batch.
+int multi_set_chars(bpe_multi *m, const uint32_t *code_points, const int32_t *ids, int64_t n) {
+    for (auto s : m->sh) MTRY(bpe_set_chars(s, code_points, ids, n));   // (a bad argument fails on the first)
+    return BPE_OK;
+}
+
+int multi_add_text_batch(bpe_multi *m, const uint16_t *units, const int64_t *off, int64_t n_texts, bool dev,
+                         uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                         int64_t hist_cap) {
+    *n_new = 0;
+    m->ing.calls++;
+    if (n_texts < 0 || (n_texts && !off)) return bpe_fail(BPE_ERR_ARG, "bpe native: bad add_text_batch arguments");
+    // the device form: the shards may sit on other devices, so the batch comes to the host
+    std::vector<int64_t> h_off;
+    std::vector<uint16_t> h_units;
+    if (dev && n_texts) {
+        h_off.resize((size_t)n_texts + 1);
+        MHIP(hipSetDevice(m->dev[0]));
+        MHIP(hipMemcpy(h_off.data(), off, h_off.size() * 8, hipMemcpyDeviceToHost));
+        if (h_off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+        for (int64_t k = 0; k < n_texts; ++k)
+            if (h_off[k + 1] < h_off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+        const int64_t b = h_off[0], t = h_off[n_texts] - b;
+        if (t && !units) return bpe_fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+        h_units.resize((size_t)std::max<int64_t>(t, 1));
+        if (t) MHIP(hipMemcpy(h_units.data(), units + b, (size_t)t * 2, hipMemcpyDeviceToHost));
+        for (auto &o : h_off) o -= b;
+        units = h_units.data();
+        off = h_off.data();
+    }
+    // the whole batch's new chars numbered on one shard (every check of the call made, nothing
+    // changed), then learnt by all: the parts below meet no unknown char
+    int32_t nt0 = 0;
+    MTRY(check_vocab(m, &nt0));
+    MTRY(ingest_text(m->sh[0], units, off, n_texts, false, true, new_chars, new_cap, n_new, id_hist, hist_cap));
+    if (n_texts == 0) {
+        std::fill(id_hist, id_hist + nt0, (int64_t)0);
+        return BPE_OK;
+    }
+    for (auto s : m->sh) MTRY(ingest_learn(s, new_chars, *n_new));
+    const int64_t nt1 = (int64_t)nt0 + *n_new;
+    std::vector<int64_t> hist((size_t)nt1, 0), part((size_t)std::max<int64_t>(nt1, 1));
+    auto run = [&](bpe_ctx *s, int64_t k0, int64_t k1) -> int {
+        int64_t none = 0;
+        MTRY(ingest_text(s, units, off + k0, k1 - k0, false, false, nullptr, 0, &none, part.data(), nt1));
+        for (int64_t i = 0; i < nt1; ++i) hist[i] += part[i];
+        return BPE_OK;
+    };
+    const int64_t total = off[n_texts] - off[0];
+    if (m->distributed || !m->staged.empty()) {
+        // after other samples: all of it to the end of the corpus
+        MTRY(distribute(m));
+        MTRY(run(m->sh.back(), 0, n_texts));
+    } else {
+        // a fresh corpus: whole texts cut into n contiguous runs of about equal units, in order
+        int64_t k0 = 0;
+        for (int r = 0; r < m->n; ++r) {
+            int64_t k1 = k0;
+            while (k1 < n_texts) {
+                const int64_t acc = off[k1] - off[0], len = off[k1 + 1] - off[k1];
+                const int at = total ? (int)std::min<int64_t>(m->n - 1, (acc + len / 2) * m->n / total) : 0;
+                if (at > r) break;
+                ++k1;
+            }
+            if (r == m->n - 1) k1 = n_texts;
+            if (k1 > k0) MTRY(run(m->sh[r], k0, k1));
+            k0 = k1;
+        }
+        m->distributed = true;
+    }
+    for (int64_t i = 0; i < nt1; ++i) id_hist[i] = hist[i];
+    m->ing.texts += n_texts;
+    m->ing.units += total;
+    for (int64_t i = 0; i < nt1; ++i) m->ing.chars += hist[i];
+    m->ing.new_chars += *n_new;
+    return drop_global(m);
+}
+
+int multi_get_ingest_stats(bpe_multi *m, bpe_ingest_stats *out) {
+    *out = m->ing;
+    for (auto s : m->sh) {
+        double ms = 0;
+        MTRY(ingest_kernel_ms(s, &ms, false));
+        out->kernel_ms += ms;
+    }
+    return BPE_OK;
+}
+
+int multi_reset_ingest_stats(bpe_multi *m) {
+    m->ing = bpe_ingest_stats{};
+    for (auto s : m->sh) {
+        double ms = 0;
+        MTRY(ingest_kernel_ms(s, &ms, true));
+    }
+    return BPE_OK;
 }
 
 int multi_clear_corpus(bpe_multi *m) {

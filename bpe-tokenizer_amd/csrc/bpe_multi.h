@@ -16,6 +16,12 @@ int multi_num_tokens(bpe_multi *m, int32_t *n);
 int multi_add_sample(bpe_multi *m, const int32_t *ids, int64_t n);
 int multi_add_latin1(bpe_multi *m, const uint8_t *bytes, int64_t n, int64_t sample_bytes,
                      int32_t char_to_id[256], int32_t *n_tokens_io, int64_t char_hist[256]);
+int multi_set_chars(bpe_multi *m, const uint32_t *code_points, const int32_t *ids, int64_t n);
+int multi_add_text_batch(bpe_multi *m, const uint16_t *units, const int64_t *off, int64_t n_texts, bool dev,
+                         uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                         int64_t hist_cap);
+int multi_get_ingest_stats(bpe_multi *m, bpe_ingest_stats *out);
+int multi_reset_ingest_stats(bpe_multi *m);
 int multi_clear_corpus(bpe_multi *m);
 int multi_corpus_size(bpe_multi *m, int64_t *n_samples, int64_t *n_tokens);
 int multi_read_corpus(bpe_multi *m, int32_t *ids_out, int64_t ids_cap, int64_t *sample_off,
@@ -49,6 +55,15 @@ void rank_rccl_forget(bpe_ctx *ctx);
 // (bpe_engine.hip) the exchange and tie buffers and the exchange's word count of the context's
 // open rank-loop batch (bpe_rank_loop_begin); BPE_ERR_STATE when no batch is open
 int rank_loop_buffers(bpe_ctx *c, unsigned long long **xchg, unsigned long long **tie, int64_t *words);
+
+// (bpe_engine.hip) the text ingest of one shard (bpe_add_text_batch): the whole pipeline, or with
+// number_only the new chars numbered and reported, every check made and nothing changed;
+// ingest_learn registers new char tokens (ids from the token count on) and puts them into the
+// shard's char table; ingest_kernel_ms reads (and with reset clears) the shard's counters
+int ingest_text(bpe_ctx *c, const uint16_t *units, const int64_t *off, int64_t n_texts, bool dev, bool number_only,
+                uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap);
+int ingest_learn(bpe_ctx *c, const uint32_t *code_points, int64_t n);
+int ingest_kernel_ms(bpe_ctx *c, double *ms, bool reset);
 
 // error reporting shared with bpe_engine.hip
 int bpe_fail(int code, const char *msg);

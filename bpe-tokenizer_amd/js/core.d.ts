@@ -65,6 +65,11 @@ export declare class BPETokenizer {
    * device (or with BPE_ENCODE_DEVICE=0) that map runs in JS.
    */
   encodeToVectorBatch(texts: string[]): number[][]
+  /**
+   * addToCorpus for many contents at once on the GPU: leaves the tables, toJSON() and the corpus as
+   * `for (let c of contents) this.addToCorpus(c)` would.  Needs a HIP device.
+   */
+  addToCorpusBatch(contents: string[]): void
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

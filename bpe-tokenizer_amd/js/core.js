@@ -20,11 +20,14 @@
  */
 const {
   loadNative,
+  loadNativeIngest,
   maxLengthArg,
   minWeightArg,
   encodeIdsMaybeOnDevice,
   decodeVectorsOnDevice,
   encodeTextsMaybeOnDevice,
+  textsToUnits,
+  syncEngineChars,
   idsToCode,
 } = require('./native')
 
@@ -261,6 +264,46 @@ class BPETokenizer {
     }
     let engine = this.engine()
     loadNative().addSample(engine, Int32Array.from(ids))
+  }
+
+  /**
+   * @description addToCorpus for many contents at once on the GPU (bpe_add_text_batch: the chars are
+   * looked up, unseen ones numbered in order of first appearance, counted, and written as samples on
+   * the device): leaves char_to_token, code_to_token, token_table, toJSON() and the corpus exactly
+   * as `for (let c of contents) this.addToCorpus(c)` would.  An addition to the reference's surface,
+   * like encodeToVectorBatch; addToCorpus itself stays on its host loop.  Needs a HIP device.
+   */
+  addToCorpusBatch(contents) {
+    if (contents.length === 0) return
+    if (!contents.every(c => typeof c === 'string')) {
+      for (let content of contents) this.addToCorpus(content)
+      return
+    }
+    // (pending tokens are registered first: the engine numbers new chars from its token count)
+    let engine = this.engine()
+    syncEngineChars(this, engine)
+    let [units, off] = textsToUnits(contents)
+    let [new_chars, hist] = loadNativeIngest().addTextBatch(engine, units, off)
+    let { char_to_token, code_to_token, token_table } = this
+    let first = token_table.length
+    for (let index = 0; index < first; index++) {
+      if (hist[index]) {
+        token_table[index].weight += hist[index]
+        token_table[index].original_weight += hist[index]
+      }
+    }
+    for (let i = 0; i < new_chars.length; i++) {
+      let index = first + i
+      let char = String.fromCodePoint(new_chars[i])
+      let code = String.fromCodePoint(index + 1)
+      let token = { chars: char, weight: hist[index], original_weight: hist[index], code, index }
+      char_to_token[char] = token
+      code_to_token[code] = token
+      token_table.push(token)
+    }
+    // (the native call registered its new tokens and put them into the engine's char table)
+    this._registered = token_table.length
+    this._eng_nchars += new_chars.length
   }
 
   /**

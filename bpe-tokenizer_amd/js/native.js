@@ -18,6 +18,13 @@ function loadNativeDecode() {
   return nativeDecode
 }
 
+// the text ingest's addon (addon/bpe_ingest_napi.node: setChars, addTextBatch on an engine handle)
+let nativeIngest = null
+function loadNativeIngest() {
+  if (!nativeIngest) nativeIngest = require(path.join(__dirname, '..', 'addon', 'bpe_ingest_napi.node'))
+  return nativeIngest
+}
+
 // the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
 let nativeText = null
 function loadNativeText() {
@@ -325,6 +332,36 @@ function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
   return out
 }
 
+/**
+ * The engine's char table (bpe_set_chars) follows `owner.char_to_token`: sent whole when the object
+ * was replaced (fromJSON), when the engine is new, or when it has gained keys the engine did not make
+ * itself (addToCorpus maps chars on the host and does not feed the table).  addToCorpusBatch counts
+ * the chars the engine numbered (`owner._eng_nchars`).  Keys that are not exactly one code point are
+ * skipped, as syncTextEncoder skips them.
+ */
+function syncEngineChars(owner, engine) {
+  for (let k of ['_eng_chars', '_eng_nchars', '_eng_for'])
+    if (!Object.prototype.hasOwnProperty.call(owner, k))
+      Object.defineProperty(owner, k, { value: null, writable: true, enumerable: false })
+  let table = owner.char_to_token
+  let keys = Object.keys(table)
+  if (owner._eng_for === engine && owner._eng_chars === table && owner._eng_nchars === keys.length) return
+  let cps = new Uint32Array(keys.length)
+  let ids = new Int32Array(keys.length)
+  let m = 0
+  for (let key of keys) {
+    let cp = key.codePointAt(0)
+    if (cp === undefined || key.length !== (cp > 0xffff ? 2 : 1)) continue
+    cps[m] = cp
+    ids[m++] = table[key].index
+  }
+  owner._eng_chars = null
+  loadNativeIngest().setChars(engine, cps.subarray(0, m), ids.subarray(0, m))
+  owner._eng_for = engine
+  owner._eng_chars = table
+  owner._eng_nchars = keys.length
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -360,6 +397,7 @@ module.exports = {
   loadNative,
   loadNativeDecode,
   loadNativeText,
+  loadNativeIngest,
   maxLengthArg,
   minWeightArg,
   encodeOnDevice,
@@ -369,5 +407,7 @@ module.exports = {
   decodeVectorsOnDevice,
   syncTextEncoder,
   encodeTextsMaybeOnDevice,
+  textsToUnits,
+  syncEngineChars,
   idsToCode,
 }

@@ -466,6 +466,62 @@ int bpe_encode_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_u
 int bpe_encoder_get_text_stats(bpe_encoder *enc, bpe_text_stats *out);
 int bpe_encoder_reset_text_stats(bpe_encoder *enc);
 
+/* ---- corpus from text --------------------------------------------------------------------------
+ * addToCorpus (core.ts:182-207) for a batch of UTF-16 texts, on the device: the call leaves the
+ * context exactly as `for (t of texts) addToCorpus(t)` would.  Chars follow bpe_encode_text_batch's
+ * rule (above): a low surrogate right after a high one inside the same text continues the char, every
+ * other unit starts one; a char's key is its code point, a lone surrogate's its unit value.
+ *
+ * The context owns a char table (char_to_token: code point -> id).  bpe_set_chars replaces it, with
+ * bpe_encoder_set_chars's argument rules and error codes (a code point above 0x10FFFF or a duplicate:
+ * BPE_ERR_ARG; an id outside [0, BPE_MAX_VOCAB): BPE_ERR_VOCAB; a failed call changes nothing);
+ * n == 0 drops the table.  An id at or past bpe_num_tokens() is registered by the call (len16 2 for
+ * a supplementary code point, else 1; ids between get len16 1, as bpe_add_sample registers them), so
+ * new chars are never numbered into the table's ids.  Use it after fromJSON, and whenever chars were
+ * added some other way: the table knows only what this call and the text ingest put into it.
+ * bpe_add_sample and bpe_add_latin1 do not feed it, and bpe_clear_corpus keeps it.
+ *
+ * bpe_add_text_batch: text k is units[off[k] .. off[k+1]) (host buffers; any 2-byte aligned unit
+ * pointer); off[0] need not be 0 and units before it are never read; offsets must not decrease or be
+ * negative (BPE_ERR_ARG); n_texts == 0 is fine.  A char that is not in the table becomes a new token:
+ * new tokens get the ids bpe_num_tokens(), +1, ... (after any merged tokens) in order of first
+ * appearance over the whole batch (text 0 before text 1; inside a text by unit position), are
+ * registered with len16 2 for a supplementary code point and 1 otherwise, and enter the table.
+ * new_chars[i] receives the code point (or lone unit value) of token bpe_num_tokens() + i, *n_new
+ * their number.  Every text becomes one sample, its ids then the separator; an empty text is an empty
+ * sample.  id_hist[id] receives the char occurrences of this call for every id below the token count
+ * after the call (the weight / original_weight increments of core.ts:192-202; the engine's own
+ * per-token counts take them too); hist_cap = BPE_MAX_VOCAB always suffices.
+ * A failed call changes nothing (corpus, sample count, char table, vocabulary, counts, maintained
+ * state) and the context stays usable: new_cap < the new chars gives BPE_ERR_ARG with *n_new written
+ * (retry with room), hist_cap below the token count after the call BPE_ERR_ARG, new chars that would
+ * pass BPE_MAX_VOCAB BPE_ERR_VOCAB.
+ * bpe_add_text_batch_device is the same with units and offsets already on the context's device; the
+ * small outputs (new_chars, id_hist) stay host-side; it runs on the context's stream and synchronises
+ * before returning.  (A multi-device context copies them to the host and takes the host form.)
+ * A multi-device context takes the call as it takes bpe_add_latin1: on a fresh corpus the texts are
+ * cut into contiguous runs of whole texts of about equal units, one per shard; otherwise all go to
+ * the last shard.  Numbering, counts, corpus and merges equal a single context's.
+ * The kernels work on bpe_encode_text_batch's tiles (BPE_TEXT_TILE, BPE_TEXT_SCAN_ROUND;
+ * csrc/bpe_ingest.hip.h). */
+typedef struct {
+    int64_t calls;            /* text ingest calls */
+    int64_t texts;            /* texts of the calls that succeeded */
+    int64_t units;            /* ... their UTF-16 units */
+    int64_t chars;            /* ... their chars (corpus tokens added) */
+    int64_t new_chars;        /* ... the char tokens they created */
+    double kernel_ms;         /* HIP-event time of the ingest kernels (discover and map spans) */
+} bpe_ingest_stats;
+int bpe_set_chars(bpe_ctx *ctx, const uint32_t *code_points, const int32_t *ids, int64_t n);
+int bpe_add_text_batch(bpe_ctx *ctx, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                       uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                       int64_t hist_cap);
+int bpe_add_text_batch_device(bpe_ctx *ctx, const uint16_t *d_units, const int64_t *d_off, int64_t n_texts,
+                              uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                              int64_t hist_cap);
+int bpe_get_ingest_stats(bpe_ctx *ctx, bpe_ingest_stats *out);
+int bpe_reset_ingest_stats(bpe_ctx *ctx);
+
 /* ---- decoding ----------------------------------------------------------------------------------
  * decodeVector / decodeTokens (core.ts:447-471) for a batch of texts: `content += token.chars` for
  * every value of a text (core.ts:462-468), the values being vector indices (mapped through
