@@ -54,7 +54,7 @@ TABLE_BINS = 81920
 DIGEST_MOD = 254    # BPE_DIGEST_MOD: the digest plane's code of a token id t >= 0 is t % DIGEST_MOD
 DIGEST_SEP = 254    # BPE_DIGEST_SEP: ... of a sample separator (-1)
 DIGEST_DEAD = 255   # BPE_DIGEST_DEAD: ... of a dead slot (anything below -1)
-DIGEST_CAND = 4     # BPE_DIGEST_CAND: candidate pairs one stream of the plane answers for
+DIGEST_CAND = 8     # BPE_DIGEST_CAND: candidate pairs one stream of the plane answers for
 MAX_CAND = 16       # BPE_MAX_CAND
 REDUCE_RCCL = 0     # BPE_REDUCE_RCCL
 REDUCE_HOST = 1     # BPE_REDUCE_HOST

@@ -252,7 +252,7 @@ struct LoopCtl {
 // site left is one more false hit) while the plane stays valid and the geometry unchanged.
 // The state lives outside the LoopCtl (re-sent at every batch start) and survives a batch exactly
 // when the plane does (digest_begin_batch clears it with every build).
-constexpr int DIGEST_CAND = 4;
+constexpr int DIGEST_CAND = 8;
 static_assert(DIGEST_CAND >= 1 && DIGEST_CAND <= 8, "candidate slots of a plane stream");
 struct DigestLists {
     int32_t pa[DIGEST_CAND], pb[DIGEST_CAND];   // slot j holds the row of (pa, pb); pa < 0: free
@@ -1835,18 +1835,11 @@ constexpr int DG_WALK = 2;
 // Hit chunks whose loads are in flight while the exact path applies the first of them.
 constexpr int DG_PF = 4;
 
-// Zero-halfword test of y, before the 0x80008000 mask (exact as an any-test: a borrow reaches a
-// halfword only from a zero halfword below it).
-__device__ __forceinline__ uint32_t hz16(uint32_t y) { return (y - 0x00010001u) & ~y; }
-
-// The smaller of each halfword of x and y (v_pk_min_u16): over many values a halfword of the
-// result is zero iff it is zero in one of them, so a chain of these keeps one zero-halfword test
-// for the end.
-__device__ __forceinline__ uint32_t pk_min16(uint32_t x, uint32_t y) {
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, x),
-                                                                  __builtin_bit_cast(u16x2, y)));
-}
+// The scan's candidate-mask table, in dynamic LDS (k_apply_loop is launched with DG_TABLE bytes):
+// one byte per byte pair lo | hi << 8, bit j set when the pair is a key of candidate j.  The
+// pair test of a scan is then one byte read per pair, whatever the number of candidates.
+constexpr int DG_TABLE = 65536;
+static_assert(DG_TABLE % (16 * WG) == 0, "the workgroup zeroes the table in 16-byte stores");
 
 // The sums of one region tallied from its int32 slots (the apply-only pass's count, chunk by
 // chunk with synchronous loads): the digest stream's slow path, for a region whose first or last
@@ -1995,8 +1988,14 @@ __device__ __forceinline__ RegionSum region_resum(const __amdgpu_buffer_rsrc_t r
 //    `b`, is this chunk's first live token and has to go (an empty chunk hands the match on).
 // Complete for a != b: a site is a live `a` whose next live token is `b`, and that `b` is either
 // the next byte of the same chunk or `a` is its chunk's last live token.  A false hit (a digest
-// alias) costs one chunk load.  The halfword pairs of a dword and of the dword shifted down one
-// byte are compared with the two keys at once: xor, then the zero-halfword test.
+// alias) costs one chunk load.  The test is a lookup: a scan first fills a table in LDS (`tab`,
+// DG_TABLE bytes, one per byte pair lo | hi << 8) with bit j set at the two keys of candidate j,
+// (da, db) and (da, DIGEST_DEAD); a lane then reads the byte of each of its 16 pairs and ors them,
+// and a wave-load whose lanes all read zero is done with one ballot.  Two candidates may share a
+// byte (digests alias, and the second key depends on `a` alone): each keeps its own bit.  The
+// table is the workgroup's: every wave zeroes a part, wave 0 derives the candidates, sets their
+// entries and publishes the set of slots in use (wg_acc[3]); waves without a region take part
+// up to the second barrier and leave.
 // A rewritten chunk's digests are stored with it and the chunk is listed for k_site_delta.  The
 // region's sums are left as the last pass wrote them unless a chunk was rewritten; then n_live
 // loses the removed slots and the edge fields are read again (region_resum).
@@ -2015,9 +2014,81 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                                             unsigned long long *__restrict__ n_hits,
                                             DigestLists *__restrict__ dl,
                                             uint32_t *__restrict__ rows, int ncand, int use,
-                                            uint32_t *wg_acc) {
+                                            uint32_t *wg_acc, uint4 *tab) {
     const int lane = threadIdx.x & 63;
     const int r = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6)));
+    const bool scan = use < 0;   // (the same in every wave of the grid)
+    uint32_t cmask = 1u;         // the candidate slots in use: bit j
+    if (scan) {
+        // (both barriers are met by every wave of the workgroup, with a region or without)
+#pragma unroll
+        for (int i = 0; i < DG_TABLE / 16 / WG; ++i) tab[i * WG + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            // The candidates of a scan: the decided pair in slot 0, and in slots 1 .. ncand - 1
+            // the pairs of the largest block keys the last k_reduce_table left
+            // (DigestLists::bkey), the table's order by pack_key being the order of the next
+            // merges unless a merge between disturbs it.  Only a guess: a != b, 16 W < n_chunks
+            // (the delta form's rule), not the decided pair itself; wave 0 of every workgroup
+            // derives the same ones, that of workgroup 0 records them.
+            int32_t ca[DIGEST_CAND], cb[DIGEST_CAND];
+            static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                ca[decltype(J)::value] = -1;
+                cb[decltype(J)::value] = -1;
+            });
+            ca[0] = ma;
+            cb[0] = mb;
+            if (ncand > 1) {
+                // (key << 8 | 255 - block: one owner per value)
+                unsigned long long s[HOT / 64];
+#pragma unroll
+                for (int q = 0; q < HOT / 64; ++q) {
+                    const unsigned long long k = dl->bkey[q * 64 + lane];
+                    s[q] = k ? (k << 8) | (unsigned long long)(255 - (q * 64 + lane)) : 0ull;
+                }
+                static_for<1, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                    constexpr int j = decltype(J)::value;
+                    if (j >= ncand) return;
+                    for (int t = 0; t < 3 && ca[j] < 0; ++t) {
+                        unsigned long long m = 0;
+#pragma unroll
+                        for (int q = 0; q < HOT / 64; ++q) m = s[q] > m ? s[q] : m;
+                        m = wave_max_u64(m);
+                        if (m == 0ull) break;
+#pragma unroll
+                        for (int q = 0; q < HOT / 64; ++q) s[q] = s[q] == m ? 0ull : s[q];
+                        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+                        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
+                        const unsigned long long key = (((unsigned long long)hi << 32) | lo) >> 8;
+                        const int32_t pb = 255 - (int32_t)(lo & 255u);
+                        const int32_t pa = (int32_t)(0x1FFFFu - (uint32_t)(key & 0x1FFFFu)) - pb;
+                        const bool ok = pa >= 0 && pa < HOT && pa != pb && !(pa == ma && pb == mb) &&
+                                        (int64_t)(key >> 17) * 16 < n_chunks;
+                        ca[j] = ok ? pa : -1;
+                        cb[j] = ok ? pb : -1;
+                    }
+                });
+            }
+            uint32_t *const tabw = reinterpret_cast<uint32_t *>(tab);
+            static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
+                constexpr int j = decltype(J)::value;
+                if (blockIdx.x == 0 && lane == 0) {
+                    dl->pa[j] = j ? ca[j] : -1;   // (slot 0 is applied now and never cached)
+                    dl->pb[j] = j ? cb[j] : -1;
+                }
+                if (ca[j] < 0) return;
+                cmask |= 1u << j;
+                // lane 0 sets the entry of (da, db), lane 1 that of (da, DIGEST_DEAD)
+                const uint32_t k = digest_of(ca[j]) | ((lane ? DIGEST_DEAD : digest_of(cb[j])) << 8);
+                if (lane < 2)
+                    __hip_atomic_fetch_or(&tabw[k >> 2], (1u << j) << (8 * (k & 3u)), __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_WORKGROUP);
+            });
+            if (lane == 0) wg_acc[3] = cmask;
+        }
+        __syncthreads();
+        cmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)wg_acc[3]);
+    }
     if (r >= R) return;
     const int64_t c0 = (int64_t)r * cpr;
     const int64_t c1 = min(c0 + cpr, n_chunks);
@@ -2090,63 +2161,7 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
         // does the token before the region match the region's first live token?
         const int32_t f = live_from(0, slot0(0));
         ap.match = ((uint32_t)(ap.prev ^ ma) | (uint32_t)(f ^ mb)) == 0u;
-        const bool scan = use < 0;
-        // The candidates of a scan: the decided pair in slot 0, and in slots 1 .. ncand - 1 the
-        // pairs of the largest block keys the last k_reduce_table left (DigestLists::bkey), the
-        // table's order by pack_key being the order of the next merges unless a merge between
-        // disturbs it.  Only a guess: a != b, 16 W < n_chunks (the delta form's rule), not the
-        // decided pair itself; every wave derives the same ones, wave 0 records them.
-        int32_t ca[DIGEST_CAND], cb[DIGEST_CAND];
-        static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
-            ca[decltype(J)::value] = -1;
-            cb[decltype(J)::value] = -1;
-        });
-        ca[0] = ma;
-        cb[0] = mb;
-        if (scan && ncand > 1) {
-            // (key << 8 | 255 - block: one owner per value)
-            unsigned long long s[HOT / 64];
-#pragma unroll
-            for (int q = 0; q < HOT / 64; ++q) {
-                const unsigned long long k = dl->bkey[q * 64 + lane];
-                s[q] = k ? (k << 8) | (unsigned long long)(255 - (q * 64 + lane)) : 0ull;
-            }
-            static_for<1, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
-                constexpr int j = decltype(J)::value;
-                if (j >= ncand) return;
-                for (int t = 0; t < 3 && ca[j] < 0; ++t) {
-                    unsigned long long m = 0;
-#pragma unroll
-                    for (int q = 0; q < HOT / 64; ++q) m = s[q] > m ? s[q] : m;
-                    m = wave_max_u64(m);
-                    if (m == 0ull) break;
-#pragma unroll
-                    for (int q = 0; q < HOT / 64; ++q) s[q] = s[q] == m ? 0ull : s[q];
-                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
-                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32));
-                    const unsigned long long key = (((unsigned long long)hi << 32) | lo) >> 8;
-                    const int32_t pb = 255 - (int32_t)(lo & 255u);
-                    const int32_t pa = (int32_t)(0x1FFFFu - (uint32_t)(key & 0x1FFFFu)) - pb;
-                    const bool ok = pa >= 0 && pa < HOT && pa != pb && !(pa == ma && pb == mb) &&
-                                    (int64_t)(key >> 17) * 16 < n_chunks;
-                    ca[j] = ok ? pa : -1;
-                    cb[j] = ok ? pb : -1;
-                }
-            });
-        }
-        if (scan && r == 0 && lane == 0)
-            static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
-                constexpr int j = decltype(J)::value;
-                dl->pa[j] = j ? ca[j] : -1;   // (slot 0 is applied now and never cached)
-                dl->pb[j] = j ? cb[j] : -1;
-            });
-        uint32_t K1[DIGEST_CAND], K2[DIGEST_CAND];
-        static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
-            constexpr int j = decltype(J)::value;
-            const uint32_t da = digest_of(ca[j]), db = digest_of(cb[j]);
-            K1[j] = (da | (db << 8)) * 0x00010001u;
-            K2[j] = (da | (DIGEST_DEAD << 8)) * 0x00010001u;
-        });
+        const uint8_t *const tb = reinterpret_cast<const uint8_t *>(tab);
         // the rows of this region's slots: words [j * wpr, j * wpr + nw) of its block, the index
         // in the bounds-checked offset (a word past the block reads 0 and is never written)
         const int wpr = (int)((cpr + 31) >> 5), nw = (nc + 31) >> 5;
@@ -2173,26 +2188,25 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                                                            : (uint32_t)bcast((int32_t)nxt.x, 0);
             const uint32_t d[5] = {d0, cur.y, cur.z, cur.w,
                                    (uint32_t)from_next((int32_t)d0, (int32_t)fill)};
-            uint32_t sft[4];
+            // the table bytes of the lane's 16 pairs (byte k with the byte to its right), ored:
+            // the candidates some pair of the lane is a key of
+            uint32_t m = 0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sft[e] = __builtin_amdgcn_alignbyte(d[e + 1], d[e], 1);
+            for (int e = 0; e < 4; ++e) {
+                m |= tb[d[e] & 0xFFFFu];
+                m |= tb[(d[e] >> 8) & 0xFFFFu];
+                m |= tb[d[e] >> 16];
+                m |= tb[__builtin_amdgcn_alignbyte(d[e + 1], d[e], 3) & 0xFFFFu];
+            }
             // (the chunks of the wave-load that lie in the region)
             const int v = nc - 4 * g;
             const unsigned long long valid = v >= 4 ? ~0ull : v <= 0 ? 0ull : ((1ull << (16 * v)) - 1ull);
-            // one more candidate costs compares on the bytes already in registers
+            // (nearly every wave-load ends here)
+            if ((__ballot(m != 0u) & valid) == 0ull) return;
             static_for<0, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
                 constexpr int j = decltype(J)::value;
-                if (ca[j] < 0) return;
-                // (the stream is bound by these: two instructions per key and two byte pairs)
-                uint32_t m = ~0u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    m = pk_min16(m, d[e] ^ K1[j]);
-                    m = pk_min16(m, d[e] ^ K2[j]);
-                    m = pk_min16(m, sft[e] ^ K1[j]);
-                    m = pk_min16(m, sft[e] ^ K2[j]);
-                }
-                const unsigned long long H = __ballot((hz16(m) & 0x80008000u) != 0u) & valid;
+                if (!(cmask >> j & 1u)) return;
+                const unsigned long long H = __ballot((m >> j & 1u) != 0u) & valid;
                 if (H != 0ull) {
                     const uint32_t lo = (uint32_t)H, hi = (uint32_t)(H >> 32);
                     const uint32_t b = (uint32_t)((lo & 0xFFFFu) != 0u) | ((uint32_t)((lo >> 16) != 0u) << 1) |
@@ -2295,7 +2309,7 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                 }
                 static_for<1, DIGEST_CAND>([&](auto J) __attribute__((always_inline)) {
                     constexpr int j = decltype(J)::value;
-                    if (ca[j] >= 0 && lane < n)
+                    if ((cmask >> j & 1u) && lane < n)
                         __builtin_amdgcn_raw_buffer_store_b32(row[j], rws, (j * wpr + wb + lane) * 4, 0, 0);
                 });
                 v = row[0];
@@ -2309,8 +2323,8 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
     }
     if (lane == 0) {
         site_n[r] = ap.n_sites;
-        // The two counters go through the workgroup (wg_acc: replaced, hits, waves done; zero at
-        // the start): a list iteration's waves all end within microseconds of each other, and
+        // The two counters go through the workgroup (wg_acc: replaced, hits, waves done, and the
+        // scan's candidate slots; zero at the start): a list iteration's waves all end within microseconds of each other, and
         // thousands of atomics on one address would then be the launch's critical path.  The
         // wave that finds itself last adds the workgroup's sums.
         if (ap.n_match) __hip_atomic_fetch_add(&wg_acc[0], (uint32_t)ap.n_match, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2342,11 +2356,14 @@ k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
     if (ctl->digest_ok) {
         // (from the decided pair's cached row when the decision found one, DigestLists::use; else
         // the plane streamed for it and the predicted pairs)
-        __shared__ uint32_t wg_acc[3];
-        if (threadIdx.x < 3) wg_acc[threadIdx.x] = 0;
+        // (dg_table: the scan's DG_TABLE bytes of dynamic LDS, which only a scan touches)
+        extern __shared__ uint4 dg_table[];
+        __shared__ uint32_t wg_acc[4];
+        if (threadIdx.x < 4) wg_acc[threadIdx.x] = 0;
         __syncthreads();
         digest_body(ids, plane, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, sums, replaced,
-                    site_list, site_n, &ctl->digest_hits, dl, rows, ctl->digest_cand, dl->use, wg_acc);
+                    site_list, site_n, &ctl->digest_hits, dl, rows, ctl->digest_cand, dl->use, wg_acc,
+                    dg_table);
     } else
         step_body<MERGE_XY, MODE_NONE, true, true, true>(
             nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,

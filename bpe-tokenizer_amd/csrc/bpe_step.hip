@@ -12,6 +12,7 @@
 // layout: the same header).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include <type_traits>
 
 #pragma clang diagnostic push
@@ -43,7 +44,22 @@ hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t
                              unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
                              uint32_t *plane, void *lists, uint32_t *rows) {
     using namespace bpe;
-    k_apply_loop<<<grid, WG, 0, s>>>(ids, n_chunks, cpr, R, static_cast<const RegionCarry *>(carry),
+    // The scan's candidate-mask table is DG_TABLE bytes of dynamic LDS: beside the kernel's few
+    // static bytes that is more than the 64 KiB a launch gets unasked, so the limit is raised
+    // once per device.  One 1024-thread workgroup per CU is the shape already: the bytes cost no
+    // occupancy, and the int32 body and a list iteration never touch them.
+    static std::atomic<uint64_t> raised{0};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    const uint64_t bit = 1ull << (dev & 63);
+    if (!(raised.load(std::memory_order_relaxed) & bit)) {
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_apply_loop),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, DG_TABLE);
+            e != hipSuccess)
+            return e;
+        raised.fetch_or(bit, std::memory_order_relaxed);
+    }
+    k_apply_loop<<<grid, WG, DG_TABLE, s>>>(ids, n_chunks, cpr, R, static_cast<const RegionCarry *>(carry),
                                      static_cast<LoopCtl *>(ctl), static_cast<RegionSum *>(sums),
                                      replaced, site_list, site_n, plane,
                                      static_cast<DigestLists *>(lists), rows);

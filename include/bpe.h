@@ -169,9 +169,12 @@ int bpe_merge_until(bpe_ctx *ctx, int64_t max_length, int64_t min_weight, int64_
 #define BPE_DIGEST_DEAD 255
 /* Candidate pairs one stream of the plane answers for: the decided merge and the predicted next
  * ones, whose hit lists (one bit per chunk) are kept and applied from without another stream.
+ * The stream tests a byte pair by one lookup in a 64 KiB table of candidate masks, a bit per
+ * candidate in a byte per pair, so its cost does not grow with the candidates and eight, the bits
+ * of the byte, is the most there can be.
  * BPE_DIGEST_CAND=n in the environment caps the candidates in use (1 .. this constant, read per
  * batch); at 1 every delta iteration streams the plane. */
-#define BPE_DIGEST_CAND 4
+#define BPE_DIGEST_CAND 8
 /* out[i] = the digest of the slot value ids[i] (host arrays; needs no context and no device). */
 int bpe_digest(const int32_t *ids, int64_t n, uint8_t *out);
 
