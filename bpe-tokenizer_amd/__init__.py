@@ -48,6 +48,7 @@ C_API = [
     'bpe_encode_text_batch_device', 'bpe_encoder_get_text_stats', 'bpe_encoder_reset_text_stats',
     'bpe_set_chars', 'bpe_add_text_batch', 'bpe_add_text_batch_device', 'bpe_get_ingest_stats',
     'bpe_reset_ingest_stats',
+    'bpe_encoder_set_long_texts', 'bpe_encoder_get_split_stats', 'bpe_encoder_reset_split_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -65,7 +66,10 @@ XCHG_HDR = 8        # BPE_XCHG_HDR
 DELTA_ROWS = 6      # BPE_DELTA_ROWS
 XCHG_WORDS = XCHG_HDR + DELTA_ROWS * MAX_VOCAB   # BPE_XCHG_WORDS
 TIE_WORDS = 32      # BPE_TIE_WORDS
-ENCODE_LDS_TOKENS = 16384   # BPE_ENCODE_LDS_TOKENS: longer texts are replayed by apply passes
+ENCODE_LDS_TOKENS = 16384   # BPE_ENCODE_LDS_TOKENS: longer texts are replayed by apply passes, or split
+LONG_REPLAY = 0     # BPE_LONG_REPLAY: long texts are replayed (the default)
+LONG_SPLIT = 1      # BPE_LONG_SPLIT: long texts are cut at boundaries no merge can cross
+ENCODE_SPLIT_WINDOW = 1024  # BPE_ENCODE_SPLIT_WINDOW: boundaries per window of the cut search
 DECODE_TILE = 1024  # BPE_DECODE_TILE: values per workgroup of the decode kernels
 DECODE_SCAN_ROUND = 8192   # BPE_DECODE_SCAN_ROUND: tile sums per round of the decode kernels' scan
 DECODE_IDS = 0      # BPE_DECODE_IDS: decodeTokens, values are token ids
@@ -127,6 +131,16 @@ class EncoderStats(ctypes.Structure):
                 ('texts_rank', ctypes.c_int64), ('texts_replay', ctypes.c_int64),
                 ('tokens_in', ctypes.c_int64), ('tokens_out', ctypes.c_int64),
                 ('steps', ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SplitStats(ctypes.Structure):
+    """bpe_split_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts_split', ctypes.c_int64),
+                ('texts_fallback', ctypes.c_int64), ('windows', ctypes.c_int64),
+                ('segments', ctypes.c_int64), ('plan_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -242,6 +256,9 @@ def lib():
         'bpe_encode_batch': ([vp, i32p, i64p, ctypes.c_int64, i32p, i64p], ctypes.c_int),
         'bpe_encoder_get_stats': ([vp, ctypes.POINTER(EncoderStats)], ctypes.c_int),
         'bpe_encoder_reset_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_set_long_texts': ([vp, ctypes.c_int], ctypes.c_int),
+        'bpe_encoder_get_split_stats': ([vp, ctypes.POINTER(SplitStats)], ctypes.c_int),
+        'bpe_encoder_reset_split_stats': ([vp], ctypes.c_int),
         'bpe_decoder_create': ([ctypes.POINTER(vp), ctypes.c_int], ctypes.c_int),
         'bpe_decoder_destroy': ([vp], ctypes.c_int),
         'bpe_decoder_clear': ([vp], ctypes.c_int),
@@ -694,13 +711,19 @@ class Encoder:
     """encodeToCode (core.ts:392-409) for batches of texts with a trained merge list, apart from
     any corpus (bpe_encoder_*, include/bpe.h): the merge list lives on the device as a rank table;
     texts up to ENCODE_LDS_TOKENS tokens are encoded by the merge-rank kernel (csrc/bpe_encode.hip), longer
-    ones by apply-only replay passes.  No CPU fallback."""
+    ones by apply-only replay passes, or (long_texts='split') as segments cut at boundaries no
+    merge can cross.  long_texts=None keeps the library's choice (BPE_ENCODE_LONG in the
+    environment, else 'replay').  No CPU fallback."""
 
-    def __init__(self, device=0, merges=None):
+    _LONG = {'replay': LONG_REPLAY, 'split': LONG_SPLIT}
+
+    def __init__(self, device=0, merges=None, long_texts=None):
         p = ctypes.c_void_p()
         _check(lib().bpe_encoder_create(ctypes.byref(p), int(device)), 'bpe_encoder_create')
         self._enc = p
         self.device = int(device)
+        if long_texts is not None:
+            self.set_long_texts(long_texts)
         if merges is not None and len(merges):
             self.add_merges(merges)
 
@@ -761,6 +784,20 @@ class Encoder:
 
     def reset_stats(self):
         _check(lib().bpe_encoder_reset_stats(self._enc), 'bpe_encoder_reset_stats')
+
+    def set_long_texts(self, mode):
+        """'replay' or 'split' (or LONG_REPLAY / LONG_SPLIT): how texts of more than
+        ENCODE_LDS_TOKENS tokens are encoded (bpe_encoder_set_long_texts)."""
+        _check(lib().bpe_encoder_set_long_texts(self._enc, int(self._LONG.get(mode, mode))),
+               'bpe_encoder_set_long_texts')
+
+    def split_stats(self):
+        s = SplitStats()
+        _check(lib().bpe_encoder_get_split_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_split_stats')
+        return s.as_dict()
+
+    def reset_split_stats(self):
+        _check(lib().bpe_encoder_reset_split_stats(self._enc), 'bpe_encoder_reset_split_stats')
 
     # the text form: encodeToVector (core.ts:392-445) from UTF-16 units ---------------------------
     _KINDS = {'ids': ENCODE_IDS, 'tokens': ENCODE_IDS, 'vectors': ENCODE_VECTORS,

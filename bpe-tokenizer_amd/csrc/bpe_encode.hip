@@ -28,6 +28,9 @@
 // Two workgroup barriers per step.  Texts longer than an LDS buffer, and merge lists for which the
 // greedy would differ, go through the apply-only streaming passes of a scratch engine
 // (bpe_apply_merges: the same M replaceAll rewrites, one pass each, all long texts together).
+// With BPE_LONG_SPLIT a long text is first cut at boundaries no merge can cross (k_cuts: one wave
+// per window of boundaries against the cut set of the list) and its segments are encoded as texts
+// are; only a text with a stretch longer than an LDS buffer without such a boundary is replayed.
 //
 // The text form (bpe_encode_text_batch, at the end of this file) puts bpe_text.hip.h's kernels
 // around k_encode: a front end from UTF-16 units to the compact ids and id offsets k_encode reads,
@@ -392,6 +395,79 @@ k_gather(const int32_t *__restrict__ src, const int64_t *__restrict__ in_off,
 // faster probes save over their few steps)
 constexpr int LDS_TAB_MIN_TOKENS = 128;
 
+// ---- long texts in segments (BPE_LONG_SPLIT, include/bpe.h) --------------------------------------
+// ends[id] = first(id) << 16 | last(id) for the ids below the merges' vocab (an id at or past it
+// is its own first and last), and the cut set {last(a) << 16 | first(b)} as an open-addressed u32
+// hash (empty = ~0, load factor <= 1/2, home slot rank_home).
+constexpr int SPLIT_H = BPE_ENCODE_SPLIT_WINDOW;
+static_assert((SPLIT_H & (SPLIT_H - 1)) == 0 && SPLIT_H >= 64 && 2 * SPLIT_H <= CAP_MAX, "include/bpe.h");
+constexpr uint32_t CUT_EMPTY = 0xFFFFFFFFu;
+
+struct CutTab {
+    const uint32_t *ends;
+    uint32_t vocab;
+    const uint32_t *slots;
+    uint32_t mask, shift;
+};
+
+__device__ __forceinline__ long long uniform64(long long v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// One wave per window: win[w] = (lo, hi), the window's boundaries as positions of `ids` (boundary p
+// lies between ids[p - 1] and ids[p]; lo <= hi, and both tokens of every boundary belong to the
+// window's text).  The wave walks from hi downwards, 64 boundaries per round, lane l testing
+// r - l; the first round with a safe boundary ends the walk, and its lowest lane holds the
+// largest safe p: cut[w], or -1 when the window has none.  An id outside [0, BPE_MAX_VOCAB) makes
+// its boundaries unsafe and indexes nothing (k_encode fails the call for it later).
+__global__ void __launch_bounds__(256)
+k_cuts(const int32_t *__restrict__ ids, const longlong2 *__restrict__ win, int64_t n_win, CutTab t,
+       long long *__restrict__ cut) {
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // (the same in every lane of a wave)
+    if (w >= n_win) return;
+    const int lane = threadIdx.x & 63;
+    const longlong2 lh = win[w];
+    const long long lo = uniform64(lh.x), hi = uniform64(lh.y);
+    long long found = -1;
+    for (long long r = hi; r >= lo; r -= 64) {
+        const long long p = r - lane;
+        bool safe = false;
+        if (p >= lo) {
+            const uint32_t x = (uint32_t)ids[p - 1], y = (uint32_t)ids[p];
+            if (x < (uint32_t)BPE_MAX_VOCAB && y < (uint32_t)BPE_MAX_VOCAB) {
+                const uint32_t lx = x < t.vocab ? t.ends[x] & 0xFFFFu : x;
+                const uint32_t fy = y < t.vocab ? t.ends[y] >> 16 : y;
+                const uint32_t key = (lx << 16) | fy;
+                uint32_t h = rank_home(key, t.shift);
+                safe = true;
+                for (;;) {
+                    const uint32_t e = t.slots[h];
+                    if (e == key) safe = false;
+                    if (e == key || e == CUT_EMPTY) break;
+                    h = (h + 1) & t.mask;
+                }
+            }
+        }
+        const unsigned long long b = __ballot(safe);
+        if (b) {
+            found = r - __builtin_ctzll(b);
+            break;
+        }
+    }
+    if (lane == 0) cut[w] = found;
+}
+
+// out_off[k] = ooff[seg_of[k]] for k in [0, n]: the texts' packed offsets from their first
+// segments' (the device form of a split call)
+__global__ void __launch_bounds__(256)
+k_text_ooff(const int64_t *__restrict__ ooff, const int64_t *__restrict__ seg_of, int64_t n,
+            int64_t *__restrict__ out_off) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k <= n) out_off[k] = ooff[seg_of[k]];
+}
+
 }  // namespace
 
 #include "bpe_text.hip.h"   // the text front end and the vector back end (bpe_encode_text_batch)
@@ -427,6 +503,22 @@ struct bpe_encoder {
     int32_t scratch_known = 0;
     bpe_encoder_stats st{};
     bpe_text_state txt;                       // the text form (bpe_encode_text_batch)
+    // long texts in segments (BPE_LONG_SPLIT): first and last base id of every id (identity until
+    // a merge makes it), the ids made so far, and the tables k_cuts reads (built and uploaded
+    // with the rank table when dirty)
+    int long_mode = BPE_LONG_REPLAY;
+    std::vector<uint16_t> first_of, last_of;
+    std::vector<uint8_t> is_made;
+    bool split_ok = true;                     // greedy_ok, and no id is the c of two merges
+    std::vector<uint32_t> ends, cut_slots;
+    uint32_t cut_bits = 0;
+    uint32_t *d_ends = nullptr, *d_cut_slots = nullptr;
+    size_t d_ends_n = 0, d_cut_slots_n = 0;
+    longlong2 *d_win = nullptr;               // a call's windows and their cuts
+    long long *d_cut = nullptr;
+    size_t d_win_n = 0, d_cut_n = 0;
+    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
+    bpe_split_stats sst{};
 };
 
 namespace {
@@ -490,9 +582,37 @@ void build_lds_image(bpe_encoder *E) {
     E->lt.shift = 32 - bits;
 }
 
+// k_cuts' tables from first_of / last_of (kept by bpe_encoder_add_merges in list order)
+void build_split_tables(bpe_encoder *E) {
+    const size_t m = E->c_of.size();
+    E->ends.resize((size_t)E->vocab);
+    for (int32_t i = 0; i < E->vocab; ++i) E->ends[i] = ((uint32_t)E->first_of[i] << 16) | E->last_of[i];
+    uint32_t bits = 4;
+    while (((size_t)1 << bits) < 2 * m) ++bits;
+    E->cut_bits = bits;
+    E->cut_slots.assign((size_t)1 << bits, CUT_EMPTY);
+    const uint32_t mask = (1u << bits) - 1;
+    // (in list order first_of[a] and last_of[b] are final at the merge's turn under greedy_ok,
+    // and so they are here; a list that is not split_ok never reads the set)
+    for (size_t r = 0; r < m; ++r) {
+        const uint32_t key = ((uint32_t)E->last_of[E->abc[3 * r]] << 16) | E->first_of[E->abc[3 * r + 1]];
+        uint32_t h = rank_home(key, 32 - bits);
+        while (E->cut_slots[h] != CUT_EMPTY && E->cut_slots[h] != key) h = (h + 1) & mask;
+        E->cut_slots[h] = key;
+    }
+}
+
 int upload_table(bpe_encoder *E) {
     if (!E->dirty) return BPE_OK;
     int rc;
+    build_split_tables(E);
+    if ((rc = grow_dev(&E->d_ends, &E->d_ends_n, E->ends.size())) ||
+        (rc = grow_dev(&E->d_cut_slots, &E->d_cut_slots_n, E->cut_slots.size())))
+        return rc;
+    if (!E->ends.empty())
+        ENC_TRY(hipMemcpyAsync(E->d_ends, E->ends.data(), E->ends.size() * 4, hipMemcpyHostToDevice, E->stream));
+    ENC_TRY(hipMemcpyAsync(E->d_cut_slots, E->cut_slots.data(), E->cut_slots.size() * 4, hipMemcpyHostToDevice,
+                           E->stream));
     if ((rc = grow_dev(&E->d_slots, &E->d_slots_n, E->slots.size()))) return rc;
     ENC_TRY(hipMemcpyAsync(E->d_slots, E->slots.data(), E->slots.size() * 8, hipMemcpyHostToDevice,
                            E->stream));
@@ -782,6 +902,198 @@ int encode_replay(bpe_encoder *E, const int32_t *ids, const int64_t *off, const 
     return BPE_OK;
 }
 
+// ---- long texts in segments (BPE_LONG_SPLIT) ------------------------------------
+
+// The segments of a call: the texts no longer than CAP_MAX and the replayed ones are one segment
+// each, a split text is the segments between its cuts.  Texts lie back to back in the stage's ids,
+// so segments do too: seg_off is Stage::off of the segments.
+struct SplitPlan {
+    std::vector<int64_t> seg_off;    // n_seg + 1 positions in the stage's ids
+    std::vector<int64_t> seg_of;     // n_texts + 1: each text's first segment (the last entry: n_seg)
+    std::vector<int64_t> fallback;   // the long texts with a stretch over CAP_MAX between cuts, ascending
+    bpe_split_stats st{};            // the call's counts: added to the encoder's by the form that
+                                     // goes on with the plan (split_commit)
+    int64_t n_seg() const { return (int64_t)seg_off.size() - 1; }
+};
+
+bool split_route(const bpe_encoder *E) {
+    return E->long_mode == BPE_LONG_SPLIT && E->greedy_ok && E->split_ok;
+}
+
+// at most this many segments come out of n texts of these lengths (an upper bound will do)
+int64_t max_segments(const int64_t *off, int64_t n) {
+    int64_t s = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t l = off[k + 1] - off[k];
+        s += l > CAP_MAX ? (l - 2) / SPLIT_H + 2 : 1;   // (a cut per window)
+    }
+    return s;
+}
+
+void split_commit(bpe_encoder *E, const SplitPlan &P) {
+    if (!P.st.windows) return;
+    E->sst.calls++;
+    E->sst.texts_split += P.st.texts_split;
+    E->sst.texts_fallback += P.st.texts_fallback;
+    E->sst.windows += P.st.windows;
+    E->sst.segments += P.st.segments;
+    E->sst.plan_ms += P.st.plan_ms;
+}
+
+// The plan of n texts whose ids are on the device at d_ids, text k at [off[k] - off[0],
+// off[k + 1] - off[0]) (off on the host): k_cuts over the windows of every text longer than
+// CAP_MAX, the cuts back (8 B per window), and the segments from them.  Waits for the stream.
+int plan_split(bpe_encoder *E, const int32_t *d_ids, const int64_t *off, int64_t n, SplitPlan &P) {
+    const int64_t base = off[0];
+    std::vector<longlong2> win;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t l = off[k + 1] - off[k], t0 = off[k] - base;
+        if (l <= CAP_MAX) continue;
+        for (int64_t lo = 1; lo <= l - 1; lo += SPLIT_H) {
+            longlong2 w;
+            w.x = t0 + lo;
+            w.y = t0 + std::min<int64_t>(lo + SPLIT_H - 1, l - 1);
+            win.push_back(w);
+        }
+    }
+    const int64_t n_win = (int64_t)win.size();
+    std::vector<long long> cut((size_t)n_win);
+    if (n_win) {
+        if (n_win > (int64_t)0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: encode batch too large");
+        int rc;
+        if ((rc = grow_dev(&E->d_win, &E->d_win_n, (size_t)n_win)) ||
+            (rc = grow_dev(&E->d_cut, &E->d_cut_n, (size_t)n_win)))
+            return rc;
+        ENC_TRY(hipMemcpyAsync(E->d_win, win.data(), (size_t)n_win * 16, hipMemcpyHostToDevice, E->stream));
+        const CutTab t{E->d_ends, (uint32_t)E->vocab, E->d_cut_slots, (1u << E->cut_bits) - 1, 32 - E->cut_bits};
+        ENC_TRY(hipEventRecord(E->ev_p0, E->stream));
+        k_cuts<<<(unsigned)((n_win + 3) / 4), 256, 0, E->stream>>>(d_ids, E->d_win, n_win, t, E->d_cut);
+        ENC_TRY(hipGetLastError());
+        ENC_TRY(hipEventRecord(E->ev_p1, E->stream));
+        ENC_TRY(hipMemcpyAsync(cut.data(), E->d_cut, (size_t)n_win * 8, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipStreamSynchronize(E->stream));
+        float ms = 0;
+        ENC_TRY(hipEventElapsedTime(&ms, E->ev_p0, E->ev_p1));
+        P.st.plan_ms = ms;
+        P.st.windows = n_win;
+    }
+    P.seg_off.clear();
+    P.seg_of.assign((size_t)n + 1, 0);
+    int64_t wi = 0;
+    std::vector<int64_t> cuts;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t l = off[k + 1] - off[k], t0 = off[k] - base;
+        P.seg_of[(size_t)k] = (int64_t)P.seg_off.size();
+        P.seg_off.push_back(t0);
+        if (l <= CAP_MAX) continue;
+        cuts.clear();
+        int64_t prev = t0;
+        bool ok = true;
+        for (int64_t lo = 1; lo <= l - 1; lo += SPLIT_H, ++wi) {
+            const int64_t c = cut[(size_t)wi];
+            if (c < 0) continue;
+            if (c < win[(size_t)wi].x || c > win[(size_t)wi].y)
+                return bpe_fail(BPE_ERR_STATE, "bpe native: cut outside its window");
+            ok &= c - prev <= CAP_MAX;
+            cuts.push_back(c);
+            prev = c;
+        }
+        ok &= t0 + l - prev <= CAP_MAX;
+        if (ok) {
+            P.seg_off.insert(P.seg_off.end(), cuts.begin(), cuts.end());
+            P.st.texts_split++;
+            P.st.segments += (int64_t)cuts.size() + 1;
+        } else {
+            P.fallback.push_back(k);
+            P.st.texts_fallback++;
+        }
+    }
+    P.seg_of[(size_t)n] = (int64_t)P.seg_off.size();
+    P.seg_off.push_back(off[n] - base);
+    return BPE_OK;
+}
+
+// The id form of a call with long texts on the split route: the ids go up, the plan is made on
+// them, and the kernels and the pack run over segments as they do over texts.  Texts that fall
+// back make the call take the host assembly, as a replayed text does on the default route.
+int encode_ids_split(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n_texts, int32_t *ids_out,
+                     int64_t *out_off) {
+    const int64_t base = off[0], total = off[n_texts] - base;
+    int rc;
+    if ((rc = upload_table(E))) return rc;
+    const int64_t n_max = max_segments(off, n_texts);
+    if (n_max >= 0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: encode batch too large");
+    Stage L(n_max, total);
+    // pinned: [ooff | off | which], sized for n_max segments
+    if ((rc = grow_stage(E, 2 * L.b_off + L.b_which, L.bytes()))) return rc;
+    Release release{E};
+    L.place(E->d_buf, n_max);
+    ENC_TRY(hipMemcpyAsync(L.ids, ids + base, (size_t)total * 4, hipMemcpyHostToDevice, E->stream));
+    SplitPlan P;
+    if ((rc = plan_split(E, L.ids, off, n_texts, P))) return rc;
+    split_commit(E, P);
+    const int64_t n_seg = P.n_seg();
+    L.place(E->d_buf, n_seg);   // (the err word follows the segments' offsets)
+    for (int64_t k : P.fallback)
+        for (int64_t i = off[k]; i < off[k + 1]; ++i)
+            if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB) return bpe_fail(BPE_ERR_VOCAB, BAD_ID);
+    int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf);
+    int64_t *h_off = reinterpret_cast<int64_t *>(E->h_buf + L.b_off);
+    int32_t *h_which = reinterpret_cast<int32_t *>(E->h_buf + 2 * L.b_off);
+    std::memcpy(h_off, P.seg_off.data(), (size_t)(n_seg + 1) * 8);
+    h_off[n_seg + 1] = 0;
+    ShapeLists lists;
+    std::vector<int64_t> whole;   // (the replayed texts' segments: one each)
+    classify(E, h_off, n_seg, lists, whole);
+    if (whole.size() != P.fallback.size()) return bpe_fail(BPE_ERR_STATE, "bpe native: split plan mismatch");
+    fill_which(lists, h_which);
+    ENC_TRY(hipMemcpyAsync(L.off, h_off, L.b_off + (size_t)lists.n * 4, hipMemcpyHostToDevice, E->stream));
+    if (!whole.empty()) ENC_TRY(hipMemsetAsync(L.len, 0, (size_t)n_seg * 4, E->stream));
+    if ((rc = launch_lists(E, lists, true, L, E->ev0, E->ev1))) return rc;
+    if (P.fallback.empty()) {
+        int64_t n_out = 0;
+        if ((rc = pack(E->stream, L, n_seg, total, MapId{})) ||
+            (rc = fetch_ooff(E->stream, L, h_ooff, n_seg, 0, BPE_ERR_VOCAB, BAD_ID)) ||
+            (rc = packed_length(h_ooff, n_seg, total, -1, &n_out)) ||
+            (rc = copy_packed(E->stream, ids_out, L.ids, n_out, hipMemcpyDeviceToHost)))
+            return rc;
+        for (int64_t k = 0; k <= n_texts; ++k) out_off[k] = h_ooff[P.seg_of[(size_t)k]];
+    } else {
+        std::vector<int64_t> tlen((size_t)n_texts, 0);
+        std::vector<int32_t> out((size_t)std::max<int64_t>(total, 1));
+        std::vector<int32_t> lens((size_t)n_seg);
+        unsigned long long err = 0;
+        ENC_TRY(hipMemcpyAsync(out.data(), L.out, (size_t)total * 4, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipMemcpyAsync(lens.data(), L.len, (size_t)n_seg * 4, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipMemcpyAsync(&err, L.err, 8, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipStreamSynchronize(E->stream));
+        if (err) return bpe_fail(BPE_ERR_VOCAB, BAD_ID);
+        if ((rc = encode_replay(E, ids, off, P.fallback, out.data(), tlen.data()))) return rc;
+        int64_t o = 0;
+        size_t fi = 0;
+        out_off[0] = 0;
+        for (int64_t k = 0; k < n_texts; ++k) {
+            if (fi < P.fallback.size() && P.fallback[fi] == k) {
+                ++fi;
+                if (tlen[(size_t)k]) std::memcpy(ids_out + o, out.data() + (off[k] - base), (size_t)tlen[(size_t)k] * 4);
+                o += tlen[(size_t)k];
+            } else {
+                for (int64_t g = P.seg_of[(size_t)k]; g < P.seg_of[(size_t)k + 1]; ++g) {
+                    if (lens[(size_t)g]) std::memcpy(ids_out + o, out.data() + P.seg_off[(size_t)g], (size_t)lens[(size_t)g] * 4);
+                    o += lens[(size_t)g];
+                }
+            }
+            out_off[k + 1] = o;
+        }
+    }
+    float ms = 0;
+    ENC_TRY(hipEventElapsedTime(&ms, E->ev0, E->ev1));
+    E->st.kernel_ms += ms;
+    E->st.texts_rank += n_texts - (int64_t)P.fallback.size();
+    E->st.tokens_out += out_off[n_texts];
+    return BPE_OK;
+}
+
 // A large call (at least 2 x GROUP_TOKENS input tokens) whose texts all take the kernels, in a few
 // groups (BPE_ENCODE_GROUPS, default 3) through two slots: the copy stream takes group g's ids up (a pageable copy: the host waits for
 // it) while the kernel stream encodes group g - 1, and group g - 1's packed ids come down while
@@ -908,6 +1220,8 @@ int encode_ids(bpe_encoder *E, const int32_t *ids, const int64_t *off, int64_t n
         if ((rc = upload_table(E))) return rc;
         return encode_groups(E, ids, off, n_texts, ids_out, out_off);
     }
+    // long texts in segments, where that route is chosen and the list allows it
+    if (longest > CAP_MAX && split_route(E)) return encode_ids_split(E, ids, off, n_texts, ids_out, out_off);
     // per text: the kernels, or the apply-pass route
     ShapeLists lists;
     std::vector<int64_t> replay;
@@ -1102,17 +1416,25 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     ShapeLists lists;
     std::vector<int64_t> no_kernel;
     classify(E, h_off, n_texts, lists, no_kernel);
-    const bool replay = !no_kernel.empty();
+    // On the split route a text of more than CAP_MAX units is planned after the front end, by its
+    // chars: the stage is sized for the segments there can be, and only a text that falls back
+    // sends the call through the replay.
+    const bool seg = !no_kernel.empty() && split_route(E);
+    bool replay = !no_kernel.empty() && !seg;
+    const int64_t n_max = seg ? max_segments(h_off, n_texts) : n_texts;
+    if (n_max >= 0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: text batch too large");
     const int mis = dev ? (int)(((uintptr_t)(units + base) >> 1) & (TXT_RUN - 1)) : 0;
     const int64_t n_tiles = (total + mis + TXT_TILE - 1) / TXT_TILE;
     if (n_tiles > 0x7FFFFFFF) return bpe_fail(BPE_ERR_ARG, "bpe native: text batch too large");
     // device: the stage (its ids and off written by k_txt_map: the chars are at most the units), then
-    //   [tile counts, then bases | first text of each tile | tile marks | units | off]
-    // (the last two: the host form's staging); pinned: [which | ooff]
-    Stage L(n_texts, total);
+    //   [tile counts, then bases | first text of each tile | tile marks | units | off | seg_of]
+    // (units and off: the host form's staging; seg_of: the device form's on the split route);
+    // pinned: [which | ooff]
+    Stage L(n_max, total);
     const size_t b_tiles = align16((size_t)n_tiles * 8), b_edge = align16((size_t)n_tiles * 4);
     const size_t b_units = dev ? 0 : align16((size_t)total * 2);
-    const size_t bytes = L.bytes() + 2 * b_tiles + b_edge + b_units + (dev ? 0 : L.b_off);
+    const size_t b_uoff = dev ? 0 : L.b_off, b_segof = dev && seg ? align16((size_t)(n_texts + 1) * 8) : 0;
+    const size_t bytes = L.bytes() + 2 * b_tiles + b_edge + b_units + b_uoff + b_segof;
     if ((rc = grow_stage(E, L.b_which + L.b_off, bytes))) return rc;
     Release release{E};
     char *d = L.place(E->d_buf, n_texts);
@@ -1121,6 +1443,7 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     uint32_t *d_edge = reinterpret_cast<uint32_t *>(d += b_tiles);
     uint16_t *d_units = reinterpret_cast<uint16_t *>(d += b_edge);
     int64_t *d_uoff = reinterpret_cast<int64_t *>(d += b_units);
+    int64_t *d_segof = reinterpret_cast<int64_t *>(d += b_uoff);
     int32_t *h_which = reinterpret_cast<int32_t *>(E->h_buf);
     int64_t *h_ooff = reinterpret_cast<int64_t *>(E->h_buf + L.b_which);
     const uint16_t *units_al;
@@ -1171,6 +1494,38 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
     int64_t n_out = 0;
     float ms = 0;
 
+    // the split route: the texts' id offsets back (8 B per text), the plan on the ids, and from
+    // here on the kernels' units are the n_k segments
+    SplitPlan P;
+    int64_t n_k = n_texts;
+    if (seg) {
+        std::vector<int64_t> idoff((size_t)n_texts + 1);
+        ENC_TRY(hipMemcpyAsync(idoff.data(), L.off, idoff.size() * 8, hipMemcpyDeviceToHost, s));
+        ENC_TRY(hipStreamSynchronize(s));
+        for (int64_t k = 0; k < n_texts; ++k)
+            if (idoff[(size_t)k] < 0 || idoff[(size_t)k + 1] < idoff[(size_t)k] || idoff[(size_t)k + 1] > total)
+                return bpe_fail(BPE_ERR_STATE, "bpe native: bad id offsets");
+        if (idoff[0] != 0) return bpe_fail(BPE_ERR_STATE, "bpe native: bad id offsets");
+        if ((rc = plan_split(E, L.ids, idoff.data(), n_texts, P))) return rc;
+        if (!P.fallback.empty()) {
+            replay = true;   // (encode_ids makes the plan again, and counts it)
+        } else {
+            split_commit(E, P);
+            n_k = P.n_seg();
+            L.place(E->d_buf, n_k);   // (the err word follows the segments' offsets)
+            lists = ShapeLists{};
+            std::vector<int64_t> none;
+            classify(E, P.seg_off.data(), n_k, lists, none);
+            if (!none.empty()) return bpe_fail(BPE_ERR_STATE, "bpe native: split plan mismatch");
+            ENC_TRY(hipMemcpyAsync(L.off, P.seg_off.data(), (size_t)(n_k + 1) * 8, hipMemcpyHostToDevice, s));
+            ENC_TRY(hipMemsetAsync(L.err, 0, 8, s));
+            if (dev)
+                ENC_TRY(hipMemcpyAsync(d_segof, P.seg_of.data(), (size_t)(n_texts + 1) * 8, hipMemcpyHostToDevice, s));
+        }
+    }
+    // text k's packed offset (h_ooff: one per segment)
+    auto text_ooff = [&](int64_t k) { return n_k == n_texts ? h_ooff[k] : h_ooff[P.seg_of[(size_t)k]]; };
+
     if (replay) {
         // host assembly, as the id form does for these texts: the front end's ids come back (they
         // must: encode_ids lays its own stage over this one), encode_ids replays them, counting
@@ -1215,17 +1570,17 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
         T.st.chars += n_ids;
     } else {
         fill_which(lists, h_which);
-        ENC_TRY(hipMemcpyAsync(L.which, h_which, (size_t)n_texts * 4, hipMemcpyHostToDevice, s));
+        ENC_TRY(hipMemcpyAsync(L.which, h_which, (size_t)n_k * 4, hipMemcpyHostToDevice, s));
         if ((rc = launch_lists(E, lists, true, L, E->ev0, E->ev1))) return rc;
         const bool vec = kind == BPE_ENCODE_VECTORS;
         ENC_TRY(hipEventRecord(T.ev[2], s));
-        if ((rc = vec ? pack(s, L, n_texts, total, VecMap{T.d_tvi, (uint32_t)T.tvi.size(), T.d_st})
-                      : pack(s, L, n_texts, total, MapId{})))
+        if ((rc = vec ? pack(s, L, n_k, total, VecMap{T.d_tvi, (uint32_t)T.tvi.size(), T.d_st})
+                      : pack(s, L, n_k, total, MapId{})))
             return rc;
         ENC_TRY(hipEventRecord(T.ev[3], s));
         ENC_TRY(hipMemcpyAsync(T.h_st, T.d_st, TS_WORDS * 8, hipMemcpyDeviceToHost, s));
         // (here the bad-id word counts ids of the char table; the call's times are counted first)
-        const int bad_id = fetch_ooff(s, L, h_ooff, n_texts, 0, BPE_ERR_STATE, "bpe native: char table id out of range");
+        const int bad_id = fetch_ooff(s, L, h_ooff, n_k, 0, BPE_ERR_STATE, "bpe native: char table id out of range");
         ENC_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
         T.st.front_ms += ms;
         ENC_TRY(hipEventElapsedTime(&ms, T.ev[2], T.ev[3]));
@@ -1238,23 +1593,34 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
         if (bad_char || bad_idx) {
             const int64_t pc = (int64_t)T.h_st[TS_BADCHAR], pi = (int64_t)T.h_st[TS_BADIDX];
             const int64_t kc = bad_char ? text_of_unit(pc) : n_texts;
-            const int64_t ki = bad_idx ? (int64_t)(std::upper_bound(h_ooff, h_ooff + n_texts + 1, pi) - h_ooff) - 1
-                                       : n_texts;
+            // (the hole's segment gi, and the text ki it belongs to: the same without a plan)
+            const int64_t gi = bad_idx ? (int64_t)(std::upper_bound(h_ooff, h_ooff + n_k + 1, pi) - h_ooff) - 1 : n_k;
+            const int64_t ki = !bad_idx ? n_texts
+                               : n_k == n_texts ? gi
+                               : (int64_t)(std::upper_bound(P.seg_of.begin(), P.seg_of.end(), gi) - P.seg_of.begin()) - 1;
             if (ki >= kc) return char_error(pc);
             int64_t at_in = 0;
             int32_t id = 0;
-            ENC_TRY(hipMemcpyAsync(&at_in, L.off + ki, 8, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipMemcpyAsync(&at_in, L.off + gi, 8, hipMemcpyDeviceToHost, s));
             ENC_TRY(hipStreamSynchronize(s));
-            ENC_TRY(hipMemcpyAsync(&id, L.out + at_in + (pi - h_ooff[ki]), 4, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipMemcpyAsync(&id, L.out + at_in + (pi - h_ooff[gi]), 4, hipMemcpyDeviceToHost, s));
             ENC_TRY(hipStreamSynchronize(s));
-            return text_index_error(id, ki, pi - h_ooff[ki]);
+            return text_index_error(id, ki, pi - text_ooff(ki));
         }
-        if ((rc = packed_length(h_ooff, n_texts, total, cap, needed))) return rc;
+        if ((rc = packed_length(h_ooff, n_k, total, cap, needed))) return rc;
         n_out = *needed;
-        if (dev) ENC_TRY(hipMemcpyAsync(out_off, L.ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToDevice, s));
+        if (dev) {
+            if (n_k == n_texts)
+                ENC_TRY(hipMemcpyAsync(out_off, L.ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToDevice, s));
+            else {
+                k_text_ooff<<<(unsigned)((n_texts + 256) / 256), 256, 0, s>>>(L.ooff, d_segof, n_texts, out_off);
+                ENC_TRY(hipGetLastError());
+            }
+        }
         if ((rc = copy_packed(s, vals_out, L.ids, n_out, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)))
             return rc;
-        if (!dev) std::memcpy(out_off, h_ooff, (size_t)(n_texts + 1) * 8);
+        if (!dev)
+            for (int64_t k = 0; k <= n_texts; ++k) out_off[k] = text_ooff(k);
         E->st.texts_rank += n_texts;
         E->st.tokens_in += (int64_t)T.h_st[TS_CHARS];
         E->st.tokens_out += n_out;
@@ -1286,6 +1652,7 @@ int bpe_encoder_create(bpe_encoder **out, int device) {
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&E->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&E->ev0) != hipSuccess || hipEventCreate(&E->ev1) != hipSuccess ||
+        hipEventCreate(&E->ev_p0) != hipSuccess || hipEventCreate(&E->ev_p1) != hipSuccess ||
         hipStreamCreateWithFlags(&E->cstream, hipStreamNonBlocking) != hipSuccess)
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: encoder stream/events"));
     for (int i = 0; i < 2; ++i)
@@ -1298,6 +1665,8 @@ int bpe_encoder_create(bpe_encoder **out, int device) {
     if (set_lds_attrs<0>() != hipSuccess)
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: encoder LDS attribute"));
     table_rebuild(E, 10);
+    if (const char *v = getenv("BPE_ENCODE_LONG"))
+        if (!std::strcmp(v, "split")) E->long_mode = BPE_LONG_SPLIT;
     *out = E;
     return BPE_OK;
 }
@@ -1311,6 +1680,12 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     if (E->d_slots) (void)hipFree(E->d_slots);
     if (E->d_limg) (void)hipFree(E->d_limg);
     if (E->d_steps) (void)hipFree(E->d_steps);
+    if (E->d_ends) (void)hipFree(E->d_ends);
+    if (E->d_cut_slots) (void)hipFree(E->d_cut_slots);
+    if (E->d_win) (void)hipFree(E->d_win);
+    if (E->d_cut) (void)hipFree(E->d_cut);
+    if (E->ev_p0) (void)hipEventDestroy(E->ev_p0);
+    if (E->ev_p1) (void)hipEventDestroy(E->ev_p1);
     if (E->d_buf) (void)hipFree(E->d_buf);
     if (E->h_buf) (void)hipHostFree(E->h_buf);
     text_free(E);
@@ -1330,6 +1705,12 @@ int bpe_encoder_clear(bpe_encoder *E) {
     E->abc.clear();
     E->c_of.clear();
     E->is_input.clear();
+    E->first_of.clear();
+    E->last_of.clear();
+    E->is_made.clear();
+    E->ends.clear();
+    E->cut_slots.clear();
+    E->split_ok = true;
     E->greedy_ok = true;
     E->vocab = 0;
     table_rebuild(E, 10);
@@ -1346,6 +1727,12 @@ int bpe_encoder_add_merges(bpe_encoder *E, const int32_t *abc, int64_t n) {
     if ((int64_t)E->c_of.size() + n > BPE_MAX_VOCAB)
         return bpe_fail(BPE_ERR_VOCAB, "bpe native: more merges than token ids");
     if (E->is_input.size() < (size_t)BPE_MAX_VOCAB) E->is_input.assign(BPE_MAX_VOCAB, 0);
+    if (E->first_of.size() < (size_t)BPE_MAX_VOCAB) {
+        E->first_of.resize(BPE_MAX_VOCAB);
+        for (int32_t i = 0; i < BPE_MAX_VOCAB; ++i) E->first_of[i] = (uint16_t)i;
+        E->last_of = E->first_of;
+        E->is_made.assign(BPE_MAX_VOCAB, 0);
+    }
     const size_t m = E->c_of.size() + (size_t)n;
     uint32_t bits = E->bits;
     while (((size_t)1 << bits) < 2 * m) ++bits;
@@ -1355,6 +1742,10 @@ int bpe_encoder_add_merges(bpe_encoder *E, const int32_t *abc, int64_t n) {
         E->is_input[a] = E->is_input[b] = 1;
         // the greedy needs every new token to be new to the merges up to and including its own
         if (E->is_input[c]) E->greedy_ok = false;
+        if (E->is_made[c] || !E->greedy_ok) E->split_ok = false;
+        E->is_made[c] = 1;
+        E->first_of[c] = E->first_of[a];
+        E->last_of[c] = E->last_of[b];
         E->abc.push_back(a);
         E->abc.push_back(b);
         E->abc.push_back(c);
@@ -1395,6 +1786,25 @@ int bpe_encoder_reset_stats(bpe_encoder *E) {
     ENC_TRY(hipSetDevice(E->device));
     ENC_TRY(hipMemset(E->d_steps, 0, 64));
     E->st = bpe_encoder_stats{};
+    return BPE_OK;
+}
+
+int bpe_encoder_set_long_texts(bpe_encoder *E, int mode) {
+    if (!E || (mode != BPE_LONG_REPLAY && mode != BPE_LONG_SPLIT))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad set_long_texts arguments");
+    E->long_mode = mode;
+    return BPE_OK;
+}
+
+int bpe_encoder_get_split_stats(bpe_encoder *E, bpe_split_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->sst;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_split_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->sst = bpe_split_stats{};
     return BPE_OK;
 }
 

@@ -405,6 +405,38 @@ int bpe_encode_batch(bpe_encoder *enc, const int32_t *ids, const int64_t *off, i
 int bpe_encoder_get_stats(bpe_encoder *enc, bpe_encoder_stats *out);
 int bpe_encoder_reset_stats(bpe_encoder *enc);
 
+/* Long texts (more than BPE_ENCODE_LDS_TOKENS tokens).  BPE_LONG_REPLAY, the default, replays them
+ * as described above.  BPE_LONG_SPLIT cuts them into segments at boundaries no merge can cross
+ * and encodes the segments with the merge-rank kernels like any other text.  With first(x) and
+ * last(x) the first and last base id a token id expands to (an id no merge makes is itself; for
+ * (a, b) -> c, first(c) = first(a) and last(c) = last(b)), the boundary between tokens x | y is
+ * safe iff (last(x), first(y)) differs from (last(a), first(b)) of every merge: the last base id
+ * left of it and the first one right of it never change, so no merge can ever join across it, and
+ * the replay of the whole text is the concatenation of the replays of both sides.  The text's
+ * boundaries p (between tokens p - 1 and p) are searched in windows of BPE_ENCODE_SPLIT_WINDOW,
+ * window j being [j * H + 1, min((j + 1) * H, n - 1)]; each window's cut is its largest safe p.
+ * A text with a stretch of more than BPE_ENCODE_LDS_TOKENS tokens between cuts is replayed, and so
+ * is every long text under a list the greedy cannot take or one that makes an id twice.  Output is
+ * identical either way.  A split text counts in bpe_encoder_stats.texts_rank, a replayed one in
+ * texts_replay.  BPE_ENCODE_LONG=split in the environment of bpe_encoder_create selects
+ * BPE_LONG_SPLIT for the new encoder. */
+#define BPE_LONG_REPLAY 0
+#define BPE_LONG_SPLIT 1
+#ifndef BPE_ENCODE_SPLIT_WINDOW   /* (-D at build time: tools/encode_long_bench.py compares windows) */
+#define BPE_ENCODE_SPLIT_WINDOW 1024   /* H: a power of two, at most BPE_ENCODE_LDS_TOKENS / 2; the fastest of 1024, 2048, 4096, 8192 (profiles/encode_long_bench.jsonl) */
+#endif
+int bpe_encoder_set_long_texts(bpe_encoder *enc, int mode);   /* other values: BPE_ERR_ARG */
+typedef struct {
+    int64_t calls;          /* calls that planned at least one long text */
+    int64_t texts_split;    /* long texts encoded as segments by the merge-rank kernels */
+    int64_t texts_fallback; /* long texts with a stretch > BPE_ENCODE_LDS_TOKENS without a safe boundary: replayed */
+    int64_t windows;        /* windows searched */
+    int64_t segments;       /* segments of the texts_split texts */
+    double plan_ms;         /* HIP-event time of the cut kernel */
+} bpe_split_stats;
+int bpe_encoder_get_split_stats(bpe_encoder *enc, bpe_split_stats *out);
+int bpe_encoder_reset_split_stats(bpe_encoder *enc);
+
 /* ---- encoding from text ------------------------------------------------------------------------
  * encodeToVector (core.ts:392-445) for a batch of UTF-16 texts, all three of its stages on the
  * device: chars -> token ids (`for (let char of content)` + char_to_token, core.ts:396-402), the
@@ -439,6 +471,9 @@ int bpe_encoder_reset_stats(bpe_encoder *enc);
  * Launch shapes and the replay route are chosen by a text's unit count (its char count is at most
  * that); texts longer than BPE_ENCODE_LDS_TOKENS units and lists the greedy cannot take make the
  * call assemble on the host, as bpe_encode_batch does.  Output is identical either way.
+ * With BPE_LONG_SPLIT a text longer than that is planned on its char count after the front end
+ * and stays on the device, segment by segment; only a text that falls back to the replay makes
+ * the call assemble on the host.  Error places stay relative to the text.
  * bpe_encode_text_batch_device is the same pipeline on buffers already on the encoder's device
  * (any 2-byte aligned unit pointer); values and offsets stay there; it reads the offsets back
  * (8 B per text) for the launch lists, runs on the encoder's stream and synchronises before
