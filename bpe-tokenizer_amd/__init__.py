@@ -49,6 +49,8 @@ C_API = [
     'bpe_set_chars', 'bpe_add_text_batch', 'bpe_add_text_batch_device', 'bpe_get_ingest_stats',
     'bpe_reset_ingest_stats',
     'bpe_encoder_set_long_texts', 'bpe_encoder_get_split_stats', 'bpe_encoder_reset_split_stats',
+    'bpe_add_sample_batch', 'bpe_add_sample_batch_device', 'bpe_restore_text_batch',
+    'bpe_restore_text_batch_device', 'bpe_token_counts', 'bpe_get_append_stats', 'bpe_reset_append_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -78,6 +80,7 @@ TEXT_TILE = 2048    # BPE_TEXT_TILE: UTF-16 units per workgroup of the text fron
 TEXT_SCAN_ROUND = 2048   # BPE_TEXT_SCAN_ROUND: tile counts per round of the front end's scan
 ENCODE_IDS = 0      # BPE_ENCODE_IDS: text -> token ids
 ENCODE_VECTORS = 1  # BPE_ENCODE_VECTORS: text -> vector indices (encodeToVector)
+APPEND_TILE = 2048  # BPE_APPEND_TILE: corpus slots per tile of the append kernel
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -170,6 +173,15 @@ class IngestStats(ctypes.Structure):
     """bpe_ingest_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units', ctypes.c_int64),
                 ('chars', ctypes.c_int64), ('new_chars', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class AppendStats(ctypes.Structure):
+    """bpe_append_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('samples', ctypes.c_int64), ('tokens', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -287,6 +299,13 @@ def lib():
                                        ctypes.c_int64], ctypes.c_int),
         'bpe_get_ingest_stats': ([vp, ctypes.POINTER(IngestStats)], ctypes.c_int),
         'bpe_reset_ingest_stats': ([vp], ctypes.c_int),
+        'bpe_add_sample_batch': ([vp, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_add_sample_batch_device': ([vp, vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_text_batch': ([vp, vp, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_text_batch_device': ([vp, vp, vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_token_counts': ([vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_get_append_stats': ([vp, ctypes.POINTER(AppendStats)], ctypes.c_int),
+        'bpe_reset_append_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -480,6 +499,87 @@ class Engine:
 
     def reset_ingest_stats(self):
         _check(lib().bpe_reset_ingest_stats(self._ctx), 'bpe_reset_ingest_stats')
+
+    # corpus from encoded samples, and restoreToCorpus (core.ts:213-216) for batches of texts ----------
+    def add_samples_flat(self, ids, off):
+        """Flat form (bpe_add_sample_batch): sample k is ids[off[k]:off[k+1]]; the context ends up as
+        after add_sample(sample) for each of them, and a failed call changes nothing."""
+        ids = _i32(ids).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = ids if ids.size else np.zeros(1, np.int32)
+        _check(lib().bpe_add_sample_batch(self._ctx, src.ctypes.data,
+                                          off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1),
+               'bpe_add_sample_batch')
+
+    def add_samples(self, samples):
+        """samples: a list of id lists, each one sample."""
+        off = np.zeros(len(samples) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in samples], out=off[1:])
+        ids = np.concatenate([_i32(x).ravel() for x in samples]) if len(samples) and off[-1] else np.zeros(0, np.int32)
+        self.add_samples_flat(ids, off)
+
+    def add_samples_tensors(self, ids, off):
+        """Device form (bpe_add_sample_batch_device): ids a torch int32 tensor and off a torch int64
+        tensor on the context's device."""
+        import torch
+        if ids.dtype != torch.int32 or off.dtype != torch.int64:
+            raise BpeError('add_samples_tensors takes int32 ids and int64 offsets', ERR_ARG)
+        if not (ids.is_cuda and off.is_cuda and ids.device == off.device):
+            raise BpeError('add_samples_tensors takes tensors on the context\'s device', ERR_ARG)
+        ids, off = ids.contiguous(), off.contiguous()
+        torch.cuda.synchronize(ids.device)   # (the context runs on a stream of its own)
+        _check(lib().bpe_add_sample_batch_device(self._ctx, ids.data_ptr() if ids.numel() else None,
+                                                 off.data_ptr(), off.numel() - 1),
+               'bpe_add_sample_batch_device')
+
+    def restore_text_flat(self, enc, units, off):
+        """Flat form (bpe_restore_text_batch): texts units[off[k]:off[k+1]] (UTF-16 units) are encoded
+        by `enc` (an Encoder on the context's device: its chars, merges and long-text mode) and
+        appended, each one sample.  The batch is atomic: on any error no text has been added."""
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        _check(lib().bpe_restore_text_batch(self._ctx, enc._enc if enc is not None else None, src.ctypes.data,
+                                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1),
+               'bpe_restore_text_batch')
+
+    def restore_text(self, enc, texts):
+        """texts: a list of str (encoded with surrogatepass: lone surrogates survive)."""
+        parts = [_units(t) for t in texts]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        units = np.concatenate(parts).astype(np.uint16) if parts and off[-1] else np.zeros(0, np.uint16)
+        self.restore_text_flat(enc, units, off)
+
+    def restore_text_tensors(self, enc, units, off):
+        """Device form (bpe_restore_text_batch_device): units a torch int16 or uint16 tensor and off a
+        torch int64 tensor on the context's device; no id comes to the host."""
+        import torch
+        if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+            raise BpeError('restore_text_tensors takes int16 or uint16 units and int64 offsets', ERR_ARG)
+        if not (units.is_cuda and off.is_cuda and units.device == off.device):
+            raise BpeError('restore_text_tensors takes tensors on the context\'s device', ERR_ARG)
+        units, off = units.contiguous(), off.contiguous()
+        torch.cuda.synchronize(units.device)   # (the context and the encoder run on streams of their own)
+        _check(lib().bpe_restore_text_batch_device(self._ctx, enc._enc if enc is not None else None,
+                                                   units.data_ptr() if units.numel() else None,
+                                                   off.data_ptr(), off.numel() - 1),
+               'bpe_restore_text_batch_device')
+
+    def token_counts(self):
+        """Occurrences of every token id in the corpus (int64; the engine's own exact counts)."""
+        out = np.zeros(MAX_VOCAB, np.int64)
+        _check(lib().bpe_token_counts(self._ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), MAX_VOCAB),
+               'bpe_token_counts')
+        return out[:self.num_tokens()].copy()
+
+    def append_stats(self):
+        s = AppendStats()
+        _check(lib().bpe_get_append_stats(self._ctx, ctypes.byref(s)), 'bpe_get_append_stats')
+        return s.as_dict()
+
+    def reset_append_stats(self):
+        _check(lib().bpe_reset_append_stats(self._ctx), 'bpe_reset_append_stats')
 
     def clear_corpus(self):
         _check(lib().bpe_clear_corpus(self._ctx), 'bpe_clear_corpus')

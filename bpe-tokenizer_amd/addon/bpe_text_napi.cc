@@ -15,11 +15,9 @@
 
 namespace {
 
-// An encoder handle behind a JS external.  destroyTextEncoder() frees it at once; the holder goes
-// with the external's finalizer.
-struct EncoderHolder {
-    bpe_encoder *e = nullptr;
-};
+// An encoder handle behind a JS external (napi_util.h TextEncoderHolder: bpe_restore_napi.node reads
+// it too).
+using EncoderHolder = TextEncoderHolder;
 
 void finalize_encoder(napi_env, void *data, void *) {
     EncoderHolder *h = static_cast<EncoderHolder *>(data);

@@ -1,6 +1,6 @@
 // napi_util.h — what the N-API modules (bpe_napi.cc, bpe_decode_napi.cc, bpe_text_napi.cc,
-// bpe_ingest_napi.cc) share: errors as JS exceptions carrying bpe_last_error(), argument access, and
-// the engine handle.
+// bpe_ingest_napi.cc, bpe_restore_napi.cc) share: errors as JS exceptions carrying bpe_last_error(),
+// argument access, and the engine and text encoder handles.
 #pragma once
 #include <node_api.h>
 
@@ -15,6 +15,12 @@ namespace {
 // such a handle read the context through it.
 struct EngineHolder {
     bpe_ctx *c = nullptr;
+};
+
+// What a text encoder handle (bpe_text_napi.node createTextEncoder's JS external) points to.
+// destroyTextEncoder() frees the encoder at once; the holder goes with the external's finalizer.
+struct TextEncoderHolder {
+    bpe_encoder *e = nullptr;
 };
 
 napi_value throw_native(napi_env env, const char *what) {

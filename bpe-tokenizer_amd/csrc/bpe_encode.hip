@@ -1634,6 +1634,12 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
 
 }  // namespace
 
+int encoder_device(bpe_encoder *E, int *device) {
+    if (!E || !device) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    *device = E->device;
+    return BPE_OK;
+}
+
 extern "C" {
 
 int bpe_encoder_create(bpe_encoder **out, int device) {

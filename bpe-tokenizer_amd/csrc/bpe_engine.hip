@@ -12,6 +12,7 @@
 #include "bpe_pix.hip.h"
 #include "bpe.h"
 #include "bpe_ingest.hip.h"   // the corpus ingest from text (with bpe_text_front.hip.h, the encoder's front end)
+#include "bpe_append.hip.h"   // the corpus append from encoded samples (bpe_add_sample_batch, the restore)
 #include "bpe_multi.h"
 #include "bpe_tools.h"
 
@@ -239,9 +240,12 @@ struct bpe_ctx {
     bool pix_first_pending = false;
     // the corpus ingest from text: char table, scratch and counters (made by its first call)
     struct IngestState *ing = nullptr;
+    // the corpus append from encoded samples: scratch and counters (made by its first call)
+    struct AppendState *app = nullptr;
 };
 
 void ingest_free(bpe_ctx *c);
+void append_free(bpe_ctx *c);
 
 namespace {
 
@@ -2819,6 +2823,7 @@ int bpe_destroy(bpe_ctx *c) {
     rank_rccl_forget(c);
     pix_free(c);
     ingest_free(c);
+    append_free(c);
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -3839,6 +3844,284 @@ int bpe_reset_ingest_stats(bpe_ctx *c) {
     MULTI(reset_ingest_stats(c->multi));
     if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
     if (c->ing) c->ing->st = bpe_ingest_stats{};
+    return BPE_OK;
+}
+
+}  // extern "C"
+
+// ---- corpus from encoded samples / restore (bpe_add_sample_batch, bpe_restore_text_batch,
+// include/bpe.h): bpe_append.hip.h's kernel between append_begin and seal_packed --------------------
+struct AppendState {
+    unsigned long long *d_hist = nullptr, *d_st = nullptr;   // BPE_MAX_VOCAB counts, APP_WORDS status words
+    char *d_buf = nullptr;   // grow-only: the host forms' staging, the restore's encoded values and offsets
+    size_t buf_bytes = 0;
+    int64_t max_wgs = 1024;   // workgroups of the append kernel the device holds at once
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bpe_append_stats st{};
+};
+
+void append_free(bpe_ctx *c) {
+    AppendState *A = c->app;
+    if (!A) return;
+    dfree(A->d_hist);
+    dfree(A->d_st);
+    dfree(A->d_buf);
+    for (hipEvent_t ev : A->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    delete A;
+    c->app = nullptr;
+}
+
+namespace {
+
+static_assert(APP_TILE == BPE_APPEND_TILE, "include/bpe.h append tile");
+
+int append_state(bpe_ctx *c, AppendState **out) {
+    if (!c->app) c->app = new AppendState();
+    AppendState *A = *out = c->app;
+    if (A->d_st) return BPE_OK;
+    int rc;
+    if ((rc = dev_alloc(&A->d_hist, BPE_MAX_VOCAB))) return rc;
+    // one resident round of persistent workgroups: a second, partly filled round would idle CUs
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_smp_append, APP_WG, 0) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && per_cu > 0 &&
+        cus > 0)
+        A->max_wgs = (int64_t)per_cu * cus;
+    for (hipEvent_t &ev : A->ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    if ((rc = dev_alloc(&A->d_st, APP_WORDS))) return rc;   // (last: marks the state complete)
+    return BPE_OK;
+}
+
+// Room for `bytes` in the scratch buffer (nothing in it is kept between calls).
+int append_scratch(bpe_ctx *c, AppendState *A, size_t bytes) {
+    if (bytes <= A->buf_bytes) return BPE_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(A->d_buf);
+    A->d_buf = nullptr;
+    A->buf_bytes = 0;
+    int rc = dev_alloc(&A->d_buf, bytes + bytes / 4);
+    if (rc) return rc;
+    A->buf_bytes = bytes + bytes / 4;
+    return BPE_OK;
+}
+
+size_t app_align(size_t n) { return (n + 15) & ~(size_t)15; }
+
+int check_offsets(const int64_t *h_off, int64_t n, const char *what) {
+    if (n && h_off[0] < 0) return fail(BPE_ERR_ARG, std::string("bpe native: negative ") + what + " offset");
+    for (int64_t k = 0; k < n; ++k)
+        if (h_off[k + 1] < h_off[k])
+            return fail(BPE_ERR_ARG, std::string("bpe native: ") + what + " offsets must not decrease");
+    return BPE_OK;
+}
+
+// The append: n samples, sample k = d_vals[h_off[k] .. h_off[k+1]) (device values and offsets; h_off
+// the host's checked copy of d_off).  The kernel writes past live_slots before the host knows that
+// every id is good, over the sealed tail of the last chunk (which the passes read): a failed call
+// does not advance and seals the tail again, so nothing observable has changed.
+int append_samples(bpe_ctx *c, AppendState *A, const int32_t *d_vals, const int64_t *d_off, const int64_t *h_off,
+                   int64_t n) {
+    if (n == 0) return BPE_OK;
+    const int64_t base = h_off[0], total = h_off[n] - base, S = total + n;
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = append_begin(c, S))) return rc;
+    const int64_t nt0 = (int64_t)c->h_len16.size();
+    const int dmis = (int)(c->live_slots & 3);
+    const int64_t n_tiles = (S + dmis + APP_TILE - 1) / APP_TILE;
+    int64_t per_wg = (n_tiles + A->max_wgs - 1) / A->max_wgs;
+    if (per_wg > APP_MAX_TILES_PER_WG) per_wg = APP_MAX_TILES_PER_WG;
+    const int64_t grid = (n_tiles + per_wg - 1) / per_wg;
+    if (grid > 0x7FFFFFFF) return fail(BPE_ERR_ARG, "bpe native: sample batch too large");
+    HIP_TRY(hipMemsetAsync(A->d_hist, 0, (size_t)BPE_MAX_VOCAB * 8, s));
+    HIP_TRY(hipMemsetAsync(A->d_st, 0, APP_WORDS * 8, s));
+    HIP_TRY(hipEventRecord(A->ev[0], s));
+    k_smp_append<<<(unsigned)grid, APP_WG, 0, s>>>(d_vals + base, d_off, n, base, total, dmis, n_tiles, per_wg, SEP,
+                                                   c->d_ids + c->live_slots, A->d_hist, A->d_st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(A->ev[1], s));
+    // one sync: the status words and the counts of the ids the context knows already
+    unsigned long long h_st[APP_WORDS] = {0, 0};
+    std::vector<unsigned long long> hist((size_t)nt0, 0);
+    HIP_TRY(hipMemcpyAsync(h_st, A->d_st, sizeof h_st, hipMemcpyDeviceToHost, s));
+    if (nt0) HIP_TRY(hipMemcpyAsync(hist.data(), A->d_hist, (size_t)nt0 * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, A->ev[0], A->ev[1]));
+    A->st.kernel_ms += ms;
+    const int64_t nt1 = std::max<int64_t>(nt0, (int64_t)h_st[APP_MAX]);
+    rc = BPE_OK;
+    if (h_st[APP_BAD] || nt1 > BPE_MAX_VOCAB) rc = fail(BPE_ERR_ARG, "bpe native: token id out of range in sample");
+    if (!rc && nt1 > nt0) {   // (ids the call registers, as bpe_add_sample does: their counts too)
+        hist.resize((size_t)nt1, 0);
+        hipError_t e = hipMemcpyAsync(hist.data() + nt0, A->d_hist + nt0, (size_t)(nt1 - nt0) * 8,
+                                      hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = fail(BPE_ERR_HIP, std::string("bpe native: append counts: ") + hipGetErrorString(e));
+        if (!rc) rc = ensure_vocab(c, nt1);
+    }
+    if (rc) {
+        const std::string msg = g_err;
+        const int rc2 = seal_tail(c);
+        if (rc2) return rc2;
+        HIP_TRY(hipStreamSynchronize(s));
+        return fail(rc, msg);
+    }
+    for (int64_t id = 0; id < nt1; ++id) c->h_count[id] += (int64_t)hist[id];
+    c->live_slots += S;
+    c->n_samples += n;
+    c->n_live += total;
+    if ((rc = seal_packed(c))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    A->st.samples += n;
+    A->st.tokens += total;
+    return BPE_OK;
+}
+
+int add_sample_batch(bpe_ctx *c, const int32_t *ids, const int64_t *off, int64_t n, bool dev) {
+    if (!c || n < 0 || n >= 0x7FFFFFFF || (n && !off)) return fail(BPE_ERR_ARG, "bpe native: bad add_sample_batch arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    AppendState *A;
+    if ((rc = append_state(c, &A))) return rc;
+    A->st.calls++;
+    if (n == 0) return BPE_OK;
+    hipStream_t s = c->stream;
+    std::vector<int64_t> off_copy;
+    const int64_t *h_off = off;
+    if (dev) {
+        off_copy.resize((size_t)n + 1);
+        HIP_TRY(hipMemcpyAsync(off_copy.data(), off, off_copy.size() * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        h_off = off_copy.data();
+    }
+    if ((rc = check_offsets(h_off, n, "sample"))) return rc;
+    const int64_t base = h_off[0], total = h_off[n] - base;
+    if (total && !ids) return fail(BPE_ERR_ARG, "bpe native: null id buffer");
+    if (dev) return append_samples(c, A, ids, off, h_off, n);
+    // the host form: ids and offsets staged, the offsets rebased to the staged ids
+    const size_t b_ids = app_align((size_t)total * 4);
+    if ((rc = append_scratch(c, A, b_ids + (size_t)(n + 1) * 8))) return rc;
+    int32_t *d_ids = reinterpret_cast<int32_t *>(A->d_buf);
+    int64_t *d_off = reinterpret_cast<int64_t *>(A->d_buf + b_ids);
+    if (total) HIP_TRY(hipMemcpyAsync(d_ids, ids + base, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+    // (the kernel subtracts off[0] itself: d_ids - base is never dereferenced below d_ids)
+    return append_samples(c, A, d_ids - base, d_off, h_off, n);
+}
+
+int restore_text(bpe_ctx *c, bpe_encoder *E, const uint16_t *units, const int64_t *off, int64_t n, bool dev) {
+    if (!c || n < 0 || n >= 0x7FFFFFFF || (n && !off))
+        return fail(BPE_ERR_ARG, "bpe native: bad restore_text_batch arguments");
+    if (!E) return fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int enc_device = -1;
+    int rc = encoder_device(E, &enc_device);
+    if (rc) return rc;
+    if (enc_device != c->device) return fail(BPE_ERR_ARG, "bpe native: the encoder is on another device than the context");
+    if ((rc = set_device(c))) return rc;
+    AppendState *A;
+    if ((rc = append_state(c, &A))) return rc;
+    A->st.calls++;
+    hipStream_t s = c->stream;
+    std::vector<int64_t> h_off((size_t)n + 1, 0);
+    if (n) {
+        if (dev) {
+            HIP_TRY(hipMemcpyAsync(h_off.data(), off, h_off.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        } else {
+            std::copy(off, off + n + 1, h_off.begin());
+        }
+    }
+    if ((rc = check_offsets(h_off.data(), n, "text"))) return rc;
+    const int64_t base = n ? h_off[0] : 0, total = n ? h_off[n] - base : 0;
+    if (total && !units) return fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+    // scratch: [encoded values: 4 B per unit (a text never grows) | their n + 1 offsets |
+    //           the host form's units and offsets]
+    const size_t b_vals = app_align((size_t)std::max<int64_t>(total, 1) * 4), b_ooff = app_align((size_t)(n + 1) * 8);
+    const size_t b_units = dev ? 0 : app_align((size_t)total * 2), b_uoff = dev ? 0 : (size_t)(n + 1) * 8;
+    if ((rc = append_scratch(c, A, b_vals + b_ooff + b_units + b_uoff))) return rc;
+    int32_t *d_vals = reinterpret_cast<int32_t *>(A->d_buf);
+    int64_t *d_ooff = reinterpret_cast<int64_t *>(A->d_buf + b_vals);
+    const uint16_t *d_units = units;
+    const int64_t *d_uoff = off;
+    if (!dev) {
+        uint16_t *su = reinterpret_cast<uint16_t *>(A->d_buf + b_vals + b_ooff);
+        int64_t *so = reinterpret_cast<int64_t *>(A->d_buf + b_vals + b_ooff + b_units);
+        if (total) HIP_TRY(hipMemcpyAsync(su, units + base, (size_t)total * 2, hipMemcpyHostToDevice, s));
+        for (int64_t k = 0; k <= n; ++k) h_off[k] -= base;
+        HIP_TRY(hipMemcpyAsync(so, h_off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        d_units = su;
+        d_uoff = so;
+    }
+    // Two streams, no events: the staging above is complete before the encoder starts (this sync),
+    // and the encoder's device form synchronises its own stream before it returns, so its values
+    // and offsets are complete before the append kernel is enqueued on the context's stream.
+    HIP_TRY(hipStreamSynchronize(s));
+    int64_t needed = 0;
+    if ((rc = bpe_encode_text_batch_device(E, BPE_ENCODE_IDS, d_units, d_uoff, n, d_vals, total, d_ooff, &needed)))
+        return rc;   // (the encoder's own code and message)
+    if ((rc = set_device(c))) return rc;
+    if (n == 0) return BPE_OK;
+    std::vector<int64_t> h_ooff((size_t)n + 1);
+    HIP_TRY(hipMemcpyAsync(h_ooff.data(), d_ooff, h_ooff.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = check_offsets(h_ooff.data(), n, "sample"))) return rc;
+    if (h_ooff[n] - h_ooff[0] != needed || needed > total)
+        return fail(BPE_ERR_STATE, "bpe native: the encoder's offsets do not match its value count");
+    return append_samples(c, A, d_vals, d_ooff, h_ooff.data(), n);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpe_add_sample_batch(bpe_ctx *c, const int32_t *ids, const int64_t *off, int64_t n) {
+    if (n >= 0 && (n == 0 || off)) MULTI(add_sample_batch(c->multi, ids, off, n, false));
+    return add_sample_batch(c, ids, off, n, false);
+}
+
+int bpe_add_sample_batch_device(bpe_ctx *c, const int32_t *d_ids, const int64_t *d_off, int64_t n) {
+    if (n >= 0 && (n == 0 || d_off)) MULTI(add_sample_batch(c->multi, d_ids, d_off, n, true));
+    return add_sample_batch(c, d_ids, d_off, n, true);
+}
+
+int bpe_restore_text_batch(bpe_ctx *c, bpe_encoder *enc, const uint16_t *units, const int64_t *off, int64_t n_texts) {
+    if (enc && n_texts >= 0 && (n_texts == 0 || off)) MULTI(restore_text_batch(c->multi, enc, units, off, n_texts, false));
+    return restore_text(c, enc, units, off, n_texts, false);
+}
+
+int bpe_restore_text_batch_device(bpe_ctx *c, bpe_encoder *enc, const uint16_t *d_units, const int64_t *d_off,
+                                  int64_t n_texts) {
+    if (enc && n_texts >= 0 && (n_texts == 0 || d_off))
+        MULTI(restore_text_batch(c->multi, enc, d_units, d_off, n_texts, true));
+    return restore_text(c, enc, d_units, d_off, n_texts, true);
+}
+
+int bpe_token_counts(bpe_ctx *c, int64_t *counts, int64_t cap) {
+    if (counts && cap >= 0) MULTI(token_counts(c->multi, counts, cap));
+    if (!c || cap < 0 || (cap && !counts)) return fail(BPE_ERR_ARG, "bpe native: bad token_counts arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = settle(c))) return rc;
+    const int64_t nt = (int64_t)c->h_count.size();
+    if (cap < nt) return fail(BPE_ERR_ARG, "bpe native: token_counts buffer below the token count");
+    std::copy(c->h_count.begin(), c->h_count.end(), counts);
+    return BPE_OK;
+}
+
+int bpe_get_append_stats(bpe_ctx *c, bpe_append_stats *out) {
+    if (out) MULTI(get_append_stats(c->multi, out));
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = c->app ? c->app->st : bpe_append_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_append_stats(bpe_ctx *c) {
+    MULTI(reset_append_stats(c->multi));
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    if (c->app) c->app->st = bpe_append_stats{};
     return BPE_OK;
 }
 

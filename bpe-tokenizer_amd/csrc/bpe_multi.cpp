@@ -70,6 +70,7 @@ struct bpe_multi {
     unsigned long long *h_buf = nullptr, *h_sum = nullptr;   // pinned, BPE_XCHG_WORDS each
     std::vector<std::vector<int32_t>> staged;            // samples not yet on a device
     bpe_ingest_stats ing{};                              // text ingest calls (kernel_ms: the shards')
+    bpe_append_stats app{};                              // sample-batch and restore calls (kernel_ms: the shards')
     bool distributed = false;
     // the maintained state (every shard holds the global tables, bpe_set_global_counts), and the
     // host-protocol iterations in a row that needed exact cold counts (two: enter that state)
@@ -638,6 +639,131 @@ int multi_reset_ingest_stats(bpe_multi *m) {
         double ms = 0;
         MTRY(ingest_kernel_ms(s, &ms, true));
     }
+    return BPE_OK;
+}
+
+// ---- corpus from encoded samples / restore (bpe_add_sample_batch, bpe_restore_text_batch) ----------
+int multi_add_sample_batch(bpe_multi *m, const int32_t *ids, const int64_t *off, int64_t n, bool dev) {
+    m->app.calls++;
+    if (n == 0) return BPE_OK;
+    // the device form: the shards may sit on other devices, so the batch comes to the host
+    std::vector<int64_t> h_off;
+    std::vector<int32_t> h_ids;
+    if (dev) {
+        h_off.resize((size_t)n + 1);
+        MHIP(hipSetDevice(m->dev[0]));
+        MHIP(hipMemcpy(h_off.data(), off, h_off.size() * 8, hipMemcpyDeviceToHost));
+        off = h_off.data();
+    }
+    if (off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative sample offset");
+    for (int64_t k = 0; k < n; ++k)
+        if (off[k + 1] < off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: sample offsets must not decrease");
+    const int64_t base = off[0], total = off[n] - base;
+    if (total && !ids) return bpe_fail(BPE_ERR_ARG, "bpe native: null id buffer");
+    if (dev) {
+        h_ids.resize((size_t)std::max<int64_t>(total, 1));
+        if (total) MHIP(hipMemcpy(h_ids.data(), ids + base, (size_t)total * 4, hipMemcpyDeviceToHost));
+        for (auto &o : h_off) o -= base;
+        ids = h_ids.data();
+    }
+    // checked before any shard changes; every shard knows every token before any shard sees it
+    // (multi_add_sample)
+    int32_t mx = -1;
+    for (int64_t i = off[0]; i < off[n]; ++i) {
+        if (ids[i] < 0 || ids[i] >= BPE_MAX_VOCAB)
+            return bpe_fail(BPE_ERR_ARG, "bpe native: token id out of range in sample");
+        mx = std::max(mx, ids[i]);
+    }
+    int32_t nt = 0;
+    MTRY(check_vocab(m, &nt));
+    for (int32_t id = nt; id <= mx; ++id) MTRY(multi_set_token_len16(m, id, 1));
+    if (m->distributed || !m->staged.empty()) {
+        // after other samples: all of it to the end of the corpus
+        MTRY(distribute(m));
+        MTRY(bpe_add_sample_batch(m->sh.back(), ids, off, n));
+    } else {
+        // a fresh corpus: whole samples cut into n contiguous runs of about equal tokens, in order
+        int64_t k0 = 0;
+        for (int r = 0; r < m->n; ++r) {
+            int64_t k1 = k0;
+            while (k1 < n) {
+                const int64_t acc = off[k1] - off[0], len = off[k1 + 1] - off[k1];
+                const int at = total ? (int)std::min<int64_t>(m->n - 1, (acc + len / 2) * m->n / total) : 0;
+                if (at > r) break;
+                ++k1;
+            }
+            if (r == m->n - 1) k1 = n;
+            if (k1 > k0) MTRY(bpe_add_sample_batch(m->sh[r], ids, off + k0, k1 - k0));
+            k0 = k1;
+        }
+        m->distributed = true;
+    }
+    m->app.samples += n;
+    m->app.tokens += total;
+    return drop_global(m);
+}
+
+// The texts are encoded through the encoder's host form (it may sit on any device), then every
+// shard takes its run of samples as above.
+int multi_restore_text_batch(bpe_multi *m, bpe_encoder *enc, const uint16_t *units, const int64_t *off,
+                             int64_t n_texts, bool dev) {
+    std::vector<int64_t> h_off;
+    std::vector<uint16_t> h_units;
+    if (dev && n_texts) {
+        h_off.resize((size_t)n_texts + 1);
+        MHIP(hipSetDevice(m->dev[0]));
+        MHIP(hipMemcpy(h_off.data(), off, h_off.size() * 8, hipMemcpyDeviceToHost));
+        if (h_off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+        for (int64_t k = 0; k < n_texts; ++k)
+            if (h_off[k + 1] < h_off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+        const int64_t b = h_off[0], t = h_off[n_texts] - b;
+        if (t && !units) return bpe_fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+        h_units.resize((size_t)std::max<int64_t>(t, 1));
+        if (t) MHIP(hipMemcpy(h_units.data(), units + b, (size_t)t * 2, hipMemcpyDeviceToHost));
+        for (auto &o : h_off) o -= b;
+        units = h_units.data();
+        off = h_off.data();
+    }
+    if (n_texts == 0) {
+        m->app.calls++;
+        return BPE_OK;
+    }
+    if (off[0] < 0 || off[n_texts] < off[0]) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+    const int64_t cap = off[n_texts] - off[0];
+    std::vector<int32_t> vals((size_t)std::max<int64_t>(cap, 1));
+    std::vector<int64_t> out_off((size_t)n_texts + 1, 0);
+    MTRY(bpe_encode_text_batch(enc, BPE_ENCODE_IDS, units, off, n_texts, vals.data(), cap, out_off.data()));
+    return multi_add_sample_batch(m, vals.data(), out_off.data(), n_texts, false);
+}
+
+int multi_token_counts(bpe_multi *m, int64_t *counts, int64_t cap) {
+    int32_t nt = 0;
+    MTRY(check_vocab(m, &nt));
+    if (cap < nt) return bpe_fail(BPE_ERR_ARG, "bpe native: token_counts buffer below the token count");
+    std::fill(counts, counts + nt, (int64_t)0);
+    std::vector<int64_t> part((size_t)std::max<int32_t>(nt, 1));
+    for (auto s : m->sh) {
+        MTRY(bpe_token_counts(s, part.data(), nt));
+        for (int32_t i = 0; i < nt; ++i) counts[i] += part[i];
+    }
+    for (auto &s : m->staged)   // (samples not yet on a device)
+        for (int32_t id : s) counts[id] += 1;
+    return BPE_OK;
+}
+
+int multi_get_append_stats(bpe_multi *m, bpe_append_stats *out) {
+    *out = m->app;
+    for (auto s : m->sh) {
+        bpe_append_stats t{};
+        MTRY(bpe_get_append_stats(s, &t));
+        out->kernel_ms += t.kernel_ms;
+    }
+    return BPE_OK;
+}
+
+int multi_reset_append_stats(bpe_multi *m) {
+    m->app = bpe_append_stats{};
+    for (auto s : m->sh) MTRY(bpe_reset_append_stats(s));
     return BPE_OK;
 }
 

@@ -22,6 +22,12 @@ int multi_add_text_batch(bpe_multi *m, const uint16_t *units, const int64_t *off
                          int64_t hist_cap);
 int multi_get_ingest_stats(bpe_multi *m, bpe_ingest_stats *out);
 int multi_reset_ingest_stats(bpe_multi *m);
+int multi_add_sample_batch(bpe_multi *m, const int32_t *ids, const int64_t *off, int64_t n, bool dev);
+int multi_restore_text_batch(bpe_multi *m, bpe_encoder *enc, const uint16_t *units, const int64_t *off,
+                             int64_t n_texts, bool dev);
+int multi_token_counts(bpe_multi *m, int64_t *counts, int64_t cap);
+int multi_get_append_stats(bpe_multi *m, bpe_append_stats *out);
+int multi_reset_append_stats(bpe_multi *m);
 int multi_clear_corpus(bpe_multi *m);
 int multi_corpus_size(bpe_multi *m, int64_t *n_samples, int64_t *n_tokens);
 int multi_read_corpus(bpe_multi *m, int32_t *ids_out, int64_t ids_cap, int64_t *sample_off,
@@ -64,6 +70,10 @@ int ingest_text(bpe_ctx *c, const uint16_t *units, const int64_t *off, int64_t n
                 uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap);
 int ingest_learn(bpe_ctx *c, const uint32_t *code_points, int64_t n);
 int ingest_kernel_ms(bpe_ctx *c, double *ms, bool reset);
+
+// (bpe_encode.hip) the device an encoder lives on (the restore checks it against the context's; the
+// encoder's struct stays private)
+int encoder_device(bpe_encoder *enc, int *device);
 
 // error reporting shared with bpe_engine.hip
 int bpe_fail(int code, const char *msg);

@@ -70,6 +70,13 @@ export declare class BPETokenizer {
    * `for (let c of contents) this.addToCorpus(c)` would.  Needs a HIP device.
    */
   addToCorpusBatch(contents: string[]): void
+  /**
+   * restoreToCorpus for many contents at once on the GPU: leaves the corpus as
+   * `for (let c of contents) this.restoreToCorpus(c)` would, except that the batch is atomic (an
+   * unknown char throws `unknown token, char: ...` and adds no content).  Without a HIP device (or
+   * with BPE_ENCODE_DEVICE=0) that loop runs in JS.
+   */
+  restoreToCorpusBatch(contents: string[]): void
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

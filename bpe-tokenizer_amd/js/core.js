@@ -26,6 +26,7 @@ const {
   encodeIdsMaybeOnDevice,
   decodeVectorsOnDevice,
   encodeTextsMaybeOnDevice,
+  restoreTextsMaybeOnDevice,
   textsToUnits,
   syncEngineChars,
   idsToCode,
@@ -316,6 +317,27 @@ class BPETokenizer {
     for (let code of content_in_code) ids.push(code.codePointAt(0) - 1)
     let engine = this.engine()
     loadNative().addSample(engine, Int32Array.from(ids))
+  }
+
+  /**
+   * @description restoreToCorpus for many contents at once on the GPU (bpe_restore_text_batch: the
+   * texts are encoded by the device text encoder with this tokenizer's chars and merges, and appended
+   * as samples on the device): leaves the corpus, toJSON() and the training that follows exactly as
+   * `for (let c of contents) this.restoreToCorpus(c)` would.  Token weights are not updated.  An
+   * addition to the reference's surface, like addToCorpusBatch; restoreToCorpus itself stays as it
+   * is.  The batch is atomic: when a content holds an unknown char the reference's
+   * `unknown token, char: "x"` is thrown and no content has been added (the loop would have added
+   * the ones before it).  It follows encodeToVectorBatch's routing: without the addon or a HIP
+   * device for it, with BPE_ENCODE_DEVICE=0, or with an entry that is not a string, the loop runs.
+   */
+  restoreToCorpusBatch(contents) {
+    if (contents.length === 0) return
+    if (contents.every(c => typeof c === 'string')) {
+      // (pending merges are flushed and pending tokens registered first)
+      let engine = this.engine()
+      if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, contents)) return
+    }
+    for (let content of contents) this.restoreToCorpus(content)
   }
 
   /**

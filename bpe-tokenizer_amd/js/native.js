@@ -25,6 +25,13 @@ function loadNativeIngest() {
   return nativeIngest
 }
 
+// the restore's addon (addon/bpe_restore_napi.node: addSampleBatch, restoreTextBatch on an engine handle)
+let nativeRestore = null
+function loadNativeRestore() {
+  if (!nativeRestore) nativeRestore = require(path.join(__dirname, '..', 'addon', 'bpe_restore_napi.node'))
+  return nativeRestore
+}
+
 // the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
 let nativeText = null
 function loadNativeText() {
@@ -333,6 +340,50 @@ function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
 }
 
 /**
+ * A batch of texts through the owner's device text encoder straight into the engine's corpus
+ * (bpe_restore_text_batch: encodeToCode on the device, then every text one sample) -> true, or false
+ * when the device cannot take the call (the caller then loops restoreToCorpus), under
+ * encodeTextsMaybeOnDevice's rules: BPE_ENCODE_DEVICE=0, no addon or no HIP device, a token id the
+ * device does not hold; with BPE_ENCODE_DEVICE=1 the device's errors go through.  The reference's
+ * `unknown token, char: "x"` is thrown with its string either way; the batch is atomic, so no text has
+ * been added then (the reference's loop would have added the texts before the failing one).
+ */
+function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts) {
+  if (ENCODE_DEVICE === '0') return false
+  if (
+    ENCODE_DEVICE !== '1' &&
+    (owner._tenc_failed === true || (owner._tenc_failed && owner._tenc_failed === list))
+  )
+    return false
+  try {
+    let enc = syncTextEncoder(owner, list, tripleOf)
+    let [units, off] = textsToUnits(texts)
+    loadNativeRestore().restoreTextBatch(engine, enc, units, off)
+  } catch (e) {
+    let msg = String((e && e.message) || e)
+    let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
+    if (m) throw new Error('unknown token, char: ' + JSON.stringify(String.fromCodePoint(parseInt(m[1], 16))))
+    if (ENCODE_DEVICE === '1') throw e
+    if (!Object.prototype.hasOwnProperty.call(owner, '_tenc_failed'))
+      Object.defineProperty(owner, '_tenc_failed', { value: null, writable: true, enumerable: false })
+    if (!owner._tenc) {
+      owner._tenc_failed = true
+    } else {
+      // (the encoder may hold part of the tables: the next call loads them again from the start)
+      owner._tenc_list = null
+      owner._tenc_chars = null
+      if (CAPABILITY_TEXT_TABLE.test(msg)) owner._tenc_failed = list
+      else if (!warned) {
+        warned = true
+        process.emitWarning('bpe device restore failed, this call restores text by text in JS: ' + msg)
+      }
+    }
+    return false
+  }
+  return true
+}
+
+/**
  * The engine's char table (bpe_set_chars) follows `owner.char_to_token`: sent whole when the object
  * was replaced (fromJSON), when the engine is new, or when it has gained keys the engine did not make
  * itself (addToCorpus maps chars on the host and does not feed the table).  addToCorpusBatch counts
@@ -398,6 +449,7 @@ module.exports = {
   loadNativeDecode,
   loadNativeText,
   loadNativeIngest,
+  loadNativeRestore,
   maxLengthArg,
   minWeightArg,
   encodeOnDevice,
@@ -407,6 +459,7 @@ module.exports = {
   decodeVectorsOnDevice,
   syncTextEncoder,
   encodeTextsMaybeOnDevice,
+  restoreTextsMaybeOnDevice,
   textsToUnits,
   syncEngineChars,
   idsToCode,

@@ -560,6 +560,65 @@ int bpe_add_text_batch_device(bpe_ctx *ctx, const uint16_t *d_units, const int64
 int bpe_get_ingest_stats(bpe_ctx *ctx, bpe_ingest_stats *out);
 int bpe_reset_ingest_stats(bpe_ctx *ctx);
 
+/* ---- corpus from encoded samples / restore -----------------------------------------------------
+ * bpe_add_sample for a batch, and on top of it restoreToCorpus (core.ts:213-216:
+ * `corpus_in_code.push(encodeToCode(content))`) for a batch of UTF-16 texts, on the device.
+ *
+ * bpe_add_sample_batch: sample k is ids[off[k] .. off[k+1]) (host buffers); off[0] need not be 0 and
+ * ids before it are never read; offsets must not decrease or be negative (BPE_ERR_ARG); n == 0 and
+ * empty samples are fine.  The call leaves the context exactly as
+ * `for k: bpe_add_sample(ids + off[k], off[k+1] - off[k])` would: corpus, sample count, live count,
+ * the engine's per-token counts, and the vocabulary (ids at or past bpe_num_tokens() are registered
+ * with len16 1).  An id outside [0, BPE_MAX_VOCAB) gives BPE_ERR_ARG with bpe_add_sample's message.
+ * A failed call changes nothing (the loop would have kept the samples before the bad one; the batch
+ * is atomic) and the context stays usable.
+ * bpe_add_sample_batch_device is the same with ids and offsets already on the context's device (any
+ * 4-byte aligned id pointer); it reads the n + 1 offsets back (8 B per sample) for validation and
+ * sizing, runs on the context's stream and synchronises before returning.
+ *
+ * bpe_restore_text_batch: text k is units[off[k] .. off[k+1]), with bpe_encode_text_batch's offset
+ * rules.  The texts go through `enc` (its char table, its merges, its long-text mode and all its
+ * routes: bpe_encode_text_batch_device with BPE_ENCODE_IDS, into scratch on the device) and the
+ * result is appended as samples, one per text, by the code above: no id comes to the host unless the
+ * encoder itself assembles there (a replayed long text).  enc must be on the context's device
+ * (BPE_ERR_ARG).  No token weight, char table or vocabulary entry changes beyond what bpe_add_sample
+ * does for those ids ("Token weights are not updated when restoring content").
+ * The encoder's errors come back as they are: `unknown token, char: U+XXXX (text K, unit I)` with
+ * BPE_ERR_VOCAB, texts with at least one unit and no char table BPE_ERR_STATE, offset errors
+ * BPE_ERR_ARG.  The batch is atomic: on any error no text has been added, where the reference's
+ * `for (t of texts) restoreToCorpus(t)` would have added the texts before the failing one.
+ * Scratch beside the corpus: 4 B per unit and 8 B per text (the host form: 2 B per unit and 8 B per
+ * text more), kept by the context and only ever grown; BPE_ERR_OOM changes nothing.
+ * bpe_restore_text_batch_device is the same with units and offsets already on the context's device;
+ * it runs on the encoder's stream, then the context's, and synchronises before returning.
+ *
+ * A multi-device context takes both as it takes bpe_add_text_batch: on a fresh corpus the samples are
+ * cut into contiguous runs of whole samples of about equal tokens, one per shard; otherwise all go to
+ * the last shard.  Its restore encodes through the encoder's host form (any device), and its device
+ * forms copy to the host.  Corpus, counts and merges equal a single context's.
+ *
+ * bpe_token_counts: the occurrences of every token id in the corpus (the engine's own exact counts,
+ * after any pending merge is settled); cap >= bpe_num_tokens(), else BPE_ERR_ARG.  A multi-device
+ * context sums its shards.
+ * The append kernel works on tiles of BPE_APPEND_TILE corpus slots (csrc/bpe_append.hip.h; exported
+ * for the tests, which place sample ends around the tile edges). */
+#define BPE_APPEND_TILE 2048   /* corpus slots per tile of the append kernel */
+typedef struct {
+    int64_t calls;            /* sample-batch and restore calls */
+    int64_t samples;          /* samples of the calls that succeeded */
+    int64_t tokens;           /* ... their tokens */
+    double kernel_ms;         /* HIP-event time of the append kernel only */
+} bpe_append_stats;
+int bpe_add_sample_batch(bpe_ctx *ctx, const int32_t *ids, const int64_t *off, int64_t n);
+int bpe_add_sample_batch_device(bpe_ctx *ctx, const int32_t *d_ids, const int64_t *d_off, int64_t n);
+int bpe_restore_text_batch(bpe_ctx *ctx, bpe_encoder *enc, const uint16_t *units, const int64_t *off,
+                           int64_t n_texts);
+int bpe_restore_text_batch_device(bpe_ctx *ctx, bpe_encoder *enc, const uint16_t *d_units, const int64_t *d_off,
+                                  int64_t n_texts);
+int bpe_token_counts(bpe_ctx *ctx, int64_t *counts, int64_t cap);
+int bpe_get_append_stats(bpe_ctx *ctx, bpe_append_stats *out);
+int bpe_reset_append_stats(bpe_ctx *ctx);
+
 /* ---- decoding ----------------------------------------------------------------------------------
  * decodeVector / decodeTokens (core.ts:447-471) for a batch of texts: `content += token.chars` for
  * every value of a text (core.ts:462-468), the values being vector indices (mapped through
