@@ -51,6 +51,8 @@ C_API = [
     'bpe_encoder_set_long_texts', 'bpe_encoder_get_split_stats', 'bpe_encoder_reset_split_stats',
     'bpe_add_sample_batch', 'bpe_add_sample_batch_device', 'bpe_restore_text_batch',
     'bpe_restore_text_batch_device', 'bpe_token_counts', 'bpe_get_append_stats', 'bpe_reset_append_stats',
+    'bpe_export_samples', 'bpe_export_samples_device', 'bpe_export_text_batch', 'bpe_export_text_batch_device',
+    'bpe_get_export_stats', 'bpe_reset_export_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -81,6 +83,11 @@ TEXT_SCAN_ROUND = 2048   # BPE_TEXT_SCAN_ROUND: tile counts per round of the fro
 ENCODE_IDS = 0      # BPE_ENCODE_IDS: text -> token ids
 ENCODE_VECTORS = 1  # BPE_ENCODE_VECTORS: text -> vector indices (encodeToVector)
 APPEND_TILE = 2048  # BPE_APPEND_TILE: corpus slots per tile of the append kernel
+EXPORT_TILE = 256   # BPE_EXPORT_TILE: corpus slots per wave step of the export kernels
+EXPORT_SCAN_THREADS = 1024   # BPE_EXPORT_SCAN_THREADS: threads of the one-block scan of the export's prefixes
+EXPORT_IDS = 0      # BPE_EXPORT_IDS: samples out as token ids
+EXPORT_VECTORS = 1  # BPE_EXPORT_VECTORS: ... as vector indices (encodeToVector of every sample)
+EXPORT_CODE = 2     # BPE_EXPORT_CODE: ... as uint16 code units id + 1 (corpus_in_code)
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -181,6 +188,15 @@ class IngestStats(ctypes.Structure):
 class AppendStats(ctypes.Structure):
     """bpe_append_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('samples', ctypes.c_int64), ('tokens', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ExportStats(ctypes.Structure):
+    """bpe_export_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('samples', ctypes.c_int64), ('values', ctypes.c_int64),
                 ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
@@ -306,6 +322,15 @@ def lib():
         'bpe_token_counts': ([vp, i64p, ctypes.c_int64], ctypes.c_int),
         'bpe_get_append_stats': ([vp, ctypes.POINTER(AppendStats)], ctypes.c_int),
         'bpe_reset_append_stats': ([vp], ctypes.c_int),
+        'bpe_export_samples': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32, vp, ctypes.c_int64,
+                                i64p], ctypes.c_int),
+        'bpe_export_samples_device': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32, vp,
+                                       ctypes.c_int64, vp, i64p], ctypes.c_int),
+        'bpe_export_text_batch': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_export_text_batch_device': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p],
+                                         ctypes.c_int),
+        'bpe_get_export_stats': ([vp, ctypes.POINTER(ExportStats)], ctypes.c_int),
+        'bpe_reset_export_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -376,6 +401,7 @@ class Engine:
 
     def __init__(self, device=0, devices=None, reduce='rccl'):
         self._ctx = ctypes.c_void_p()
+        self.device = int(device if devices is None else devices[0])
         if devices is None:
             _check(lib().bpe_create(ctypes.byref(self._ctx), device), 'bpe_create')
         else:
@@ -580,6 +606,136 @@ class Engine:
 
     def reset_append_stats(self):
         _check(lib().bpe_reset_append_stats(self._ctx), 'bpe_reset_append_stats')
+
+    # corpus out (bpe_export_*, include/bpe.h) ---------------------------------------------------------
+    _EXPORT_KINDS = {'ids': EXPORT_IDS, 'vectors': EXPORT_VECTORS, 'code': EXPORT_CODE, 'codes': EXPORT_CODE,
+                     EXPORT_IDS: EXPORT_IDS, EXPORT_VECTORS: EXPORT_VECTORS, EXPORT_CODE: EXPORT_CODE}
+
+    def _export_args(self, idx, kind, to_vector_index):
+        """(kind, idx array or None, its pointer, n, index array or None, its pointer, its length)."""
+        i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        kind = self._EXPORT_KINDS[kind]
+        if idx is None:
+            idx_a, idx_p, n = None, None, self.corpus_size()[0]
+        else:
+            idx_a = np.ascontiguousarray(idx, np.int64).ravel()
+            n = idx_a.size
+            idx_p = (idx_a if n else np.zeros(1, np.int64)).ctypes.data_as(i64p)
+        if to_vector_index is None:
+            tvi_a, tvi_p, n_index = None, None, 0
+        else:
+            tvi_a = _i32(to_vector_index).ravel()
+            n_index = tvi_a.size
+            tvi_a = tvi_a if n_index else np.zeros(1, np.int32)
+            tvi_p = tvi_a.ctypes.data_as(i32p)
+        return kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index
+
+    def export_samples(self, idx=None, kind='ids', to_vector_index=None):
+        """Samples out of the corpus (bpe_export_samples): idx a list of sample indices (any order,
+        repeats allowed), None for every sample in corpus order; kind 'ids' (int32 token ids),
+        'vectors' (int32 to_vector_index[id], encodeToVector of the sample) or 'code' (uint16 units
+        id + 1, the sample's corpus_in_code string).  Returns (values, offsets int64) as numpy
+        arrays.  A list of samples takes the sizing call first, then the real one."""
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        dtype = np.uint16 if kind == EXPORT_CODE else np.int32
+        off = np.zeros(n + 1, np.int64)
+        if idx is None:   # (every sample: one value per live token, no sizing call)
+            off[n] = self.corpus_size()[1]
+        else:
+            rc = lib().bpe_export_samples(self._ctx, kind, idx_p, n, tvi_p, n_index, None, 0,
+                                          off.ctypes.data_as(i64p))
+            if rc == BPE_OK:   # (nothing to write)
+                return np.zeros(0, dtype), off
+            if rc != ERR_ARG or off[n] <= 0:
+                _check(rc, 'bpe_export_samples')
+        vals = np.empty(max(int(off[n]), 1), dtype)[:int(off[n])]
+        _check(lib().bpe_export_samples(self._ctx, kind, idx_p, n, tvi_p, n_index, vals.ctypes.data, vals.size,
+                                        off.ctypes.data_as(i64p)), 'bpe_export_samples')
+        return vals, off
+
+    def export_samples_tensors(self, idx=None, kind='ids', to_vector_index=None, out=None):
+        """Device form (bpe_export_samples_device): (values, offsets) as torch tensors on the context's
+        device, int32 values (int16 for 'code') and int64 offsets; no value touches the host.  out: a
+        tensor of that dtype on the device to write the values into (any element offset), else one
+        is made after the sizing call."""
+        import torch
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        dev = torch.device('cuda', self.device)
+        dtype = torch.int16 if kind == EXPORT_CODE else torch.int32
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        need = ctypes.c_int64()
+        if out is None and idx is None:   # (every sample: one value per live token, no sizing call)
+            out = torch.empty(self.corpus_size()[1], dtype=dtype, device=dev)
+        if out is None:
+            torch.cuda.synchronize(dev)   # (the context runs on a stream of its own)
+            rc = lib().bpe_export_samples_device(self._ctx, kind, idx_p, n, tvi_p, n_index, None, 0, off.data_ptr(),
+                                                 ctypes.byref(need))
+            if rc == BPE_OK:
+                return torch.zeros(0, dtype=dtype, device=dev), off
+            if rc != ERR_ARG or need.value <= 0:
+                _check(rc, 'bpe_export_samples_device')
+            out = torch.empty(need.value, dtype=dtype, device=dev)
+        elif out.dtype != dtype or not out.is_cuda or out.device.index != self.device or not out.is_contiguous():
+            raise BpeError('export_samples_tensors takes a contiguous %s tensor on the context\'s device' % dtype,
+                           ERR_ARG)
+        torch.cuda.synchronize(dev)
+        _check(lib().bpe_export_samples_device(self._ctx, kind, idx_p, n, tvi_p, n_index,
+                                               out.data_ptr() if out.numel() else None, out.numel(),
+                                               off.data_ptr(), ctypes.byref(need)), 'bpe_export_samples_device')
+        return out[:need.value], off
+
+    def export_text_flat(self, dec, idx=None):
+        """Samples out as UTF-16 text through `dec` (a Decoder on the context's device;
+        bpe_export_text_batch): (units uint16, offsets int64).  The sizing call, then the real one."""
+        _, idx_a, idx_p, n, _, _, _ = self._export_args(idx, 'ids', None)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        d = dec._dec if dec is not None else None
+        off = np.zeros(n + 1, np.int64)
+        rc = lib().bpe_export_text_batch(self._ctx, d, idx_p, n, None, 0, off.ctypes.data_as(i64p))
+        if rc == BPE_OK:
+            return np.zeros(0, np.uint16), off
+        if rc != ERR_ARG or off[n] <= 0:
+            _check(rc, 'bpe_export_text_batch')
+        units = np.empty(int(off[n]), np.uint16)
+        _check(lib().bpe_export_text_batch(self._ctx, d, idx_p, n, units.ctypes.data, units.size,
+                                           off.ctypes.data_as(i64p)), 'bpe_export_text_batch')
+        return units, off
+
+    def export_text(self, dec, idx=None):
+        """The samples' texts as a list of str (lone surrogates kept)."""
+        units, oo = self.export_text_flat(dec, idx)
+        raw = units.astype('<u2', copy=False).tobytes()
+        return [raw[2 * oo[k]:2 * oo[k + 1]].decode('utf-16-le', 'surrogatepass') for k in range(len(oo) - 1)]
+
+    def export_text_tensors(self, dec, idx=None):
+        """Device form (bpe_export_text_batch_device): (int16 tensor of the units, int64 offsets
+        tensor) on the context's device; no id and no unit touches the host."""
+        import torch
+        _, idx_a, idx_p, n, _, _, _ = self._export_args(idx, 'ids', None)
+        dev = torch.device('cuda', self.device)
+        d = dec._dec if dec is not None else None
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        need = ctypes.c_int64()
+        torch.cuda.synchronize(dev)
+        rc = lib().bpe_export_text_batch_device(self._ctx, d, idx_p, n, None, 0, off.data_ptr(), ctypes.byref(need))
+        if rc == BPE_OK:
+            return torch.zeros(0, dtype=torch.int16, device=dev), off
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, 'bpe_export_text_batch_device')
+        units = torch.empty(need.value, dtype=torch.int16, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().bpe_export_text_batch_device(self._ctx, d, idx_p, n, units.data_ptr(), units.numel(),
+                                                  off.data_ptr(), ctypes.byref(need)), 'bpe_export_text_batch_device')
+        return units, off
+
+    def export_stats(self):
+        s = ExportStats()
+        _check(lib().bpe_get_export_stats(self._ctx, ctypes.byref(s)), 'bpe_get_export_stats')
+        return s.as_dict()
+
+    def reset_export_stats(self):
+        _check(lib().bpe_reset_export_stats(self._ctx), 'bpe_reset_export_stats')
 
     def clear_corpus(self):
         _check(lib().bpe_clear_corpus(self._ctx), 'bpe_clear_corpus')

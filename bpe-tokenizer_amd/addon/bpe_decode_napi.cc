@@ -16,10 +16,7 @@ namespace {
 
 // A decoder handle (bpe_decoder_*: the vocabulary's chars on the device, decodeVector /
 // decodeTokens core.ts:447-471 for batches) behind a JS external.  destroyDecoder() frees it at
-// once; the holder goes with the external's finalizer.
-struct DecoderHolder {
-    bpe_decoder *d = nullptr;
-};
+// once; the holder goes with the external's finalizer (napi_util.h DecoderHolder).
 
 void finalize_decoder(napi_env, void *data, void *) {
     DecoderHolder *h = static_cast<DecoderHolder *>(data);

@@ -1,6 +1,6 @@
 // napi_util.h — what the N-API modules (bpe_napi.cc, bpe_decode_napi.cc, bpe_text_napi.cc,
-// bpe_ingest_napi.cc, bpe_restore_napi.cc) share: errors as JS exceptions carrying bpe_last_error(),
-// argument access, and the engine and text encoder handles.
+// bpe_ingest_napi.cc, bpe_restore_napi.cc, bpe_export_napi.cc) share: errors as JS exceptions carrying
+// bpe_last_error(), argument access, and the engine, text encoder and decoder handles.
 #pragma once
 #include <node_api.h>
 
@@ -21,6 +21,12 @@ struct EngineHolder {
 // destroyTextEncoder() frees the encoder at once; the holder goes with the external's finalizer.
 struct TextEncoderHolder {
     bpe_encoder *e = nullptr;
+};
+
+// What a decoder handle (bpe_decode_napi.node createDecoder's JS external) points to.
+// destroyDecoder() frees the decoder at once; the holder goes with the external's finalizer.
+struct DecoderHolder {
+    bpe_decoder *d = nullptr;
 };
 
 napi_value throw_native(napi_env env, const char *what) {

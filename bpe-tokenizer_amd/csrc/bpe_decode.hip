@@ -502,6 +502,12 @@ size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
 
+int decoder_device(bpe_decoder *D, int *device) {
+    if (!D || !device) return bpe_fail(BPE_ERR_ARG, "bpe native: null decoder");
+    *device = D->device;
+    return BPE_OK;
+}
+
 extern "C" {
 
 int bpe_decoder_create(bpe_decoder **out, int device) {

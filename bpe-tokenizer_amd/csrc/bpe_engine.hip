@@ -13,6 +13,7 @@
 #include "bpe.h"
 #include "bpe_ingest.hip.h"   // the corpus ingest from text (with bpe_text_front.hip.h, the encoder's front end)
 #include "bpe_append.hip.h"   // the corpus append from encoded samples (bpe_add_sample_batch, the restore)
+#include "bpe_export.hip.h"   // the corpus export (bpe_export_samples, bpe_export_text_batch)
 #include "bpe_multi.h"
 #include "bpe_tools.h"
 
@@ -242,10 +243,13 @@ struct bpe_ctx {
     struct IngestState *ing = nullptr;
     // the corpus append from encoded samples: scratch and counters (made by its first call)
     struct AppendState *app = nullptr;
+    // the corpus export: scratch and counters (made by its first call)
+    struct ExportState *exp = nullptr;
 };
 
 void ingest_free(bpe_ctx *c);
 void append_free(bpe_ctx *c);
+void export_free(bpe_ctx *c);
 
 namespace {
 
@@ -2824,6 +2828,7 @@ int bpe_destroy(bpe_ctx *c) {
     pix_free(c);
     ingest_free(c);
     append_free(c);
+    export_free(c);
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -4122,6 +4127,362 @@ int bpe_reset_append_stats(bpe_ctx *c) {
     MULTI(reset_append_stats(c->multi));
     if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
     if (c->app) c->app->st = bpe_append_stats{};
+    return BPE_OK;
+}
+
+}  // extern "C"
+
+// ---- corpus out (bpe_export_samples, bpe_export_text_batch, include/bpe.h): bpe_export.hip.h's
+// kernels after k_census and k_scan_pair; nothing here writes the corpus or any state of the passes --
+struct ExportState {
+    char *d_buf = nullptr;    // grow-only: region prefixes, sample index, chunk prefixes, plan, vector index
+    size_t buf_bytes = 0;
+    char *d_vals = nullptr;   // grow-only: the host forms' values; the text export's ids, offsets and units
+    size_t vals_bytes = 0;
+    unsigned long long *d_st = nullptr;   // EXP_CHECK's first failing value
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // the index / check span, the emit span
+    bpe_export_stats st{};
+    // the call in flight, between export_prepare and export_emit (pointers into d_buf)
+    bool all = false, le_done = false, emit_timed = false;
+    int64_t n = 0, needed = 0, n_items = 0;
+    int64_t *d_live = nullptr, *d_seps = nullptr, *d_le = nullptr, *d_se = nullptr, *d_cpre = nullptr;
+    int64_t *d_idx = nullptr, *d_soff = nullptr, *d_ipre = nullptr;
+    int32_t *d_map = nullptr;
+    int32_t n_index = 0;
+    const int64_t *d_off = nullptr;   // the call's n + 1 offsets
+};
+
+void export_free(bpe_ctx *c) {
+    ExportState *X = c->exp;
+    if (!X) return;
+    dfree(X->d_buf);
+    dfree(X->d_vals);
+    dfree(X->d_st);
+    for (hipEvent_t ev : X->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    delete X;
+    c->exp = nullptr;
+}
+
+namespace {
+
+static_assert(EXP_TILE == BPE_EXPORT_TILE && BPE_EXPORT_SCAN_THREADS == 1024, "include/bpe.h export constants");
+
+int export_state(bpe_ctx *c, ExportState **out) {
+    if (!c->exp) c->exp = new ExportState();
+    ExportState *X = *out = c->exp;
+    if (X->d_st) return BPE_OK;
+    for (hipEvent_t &ev : X->ev)
+        if (!ev) HIP_TRY(hipEventCreate(&ev));
+    return dev_alloc(&X->d_st, 1);   // (last: marks the state complete)
+}
+
+// Room for `bytes` in one of the scratch buffers (nothing in them is kept between calls).
+int export_grow(bpe_ctx *c, char **buf, size_t *have, size_t bytes) {
+    if (bytes <= *have) return BPE_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    dfree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    int rc = dev_alloc(buf, bytes + bytes / 4);
+    if (rc) return rc;
+    *have = bytes + bytes / 4;
+    return BPE_OK;
+}
+
+// Every way out of an export call waits for the copies it enqueued from and to the caller's buffers.
+struct ExportSync {
+    hipStream_t s;
+    ~ExportSync() { (void)hipStreamSynchronize(s); }
+};
+
+template <int KIND>
+void export_walk(bpe_ctx *c, ExportState *X, void *d_out, int64_t *off, int64_t *se, int64_t *cpre) {
+    k_exp_walk<KIND><<<(c->R + EXP_WAVES - 1) / EXP_WAVES, EXP_WG, 0, c->stream>>>(
+        c->d_ids, c->n_chunks, c->cpr, c->R, X->d_live, X->d_seps, c->n_samples, c->n_live, X->d_map, X->n_index,
+        d_out, off, se, cpre, X->d_st);
+}
+
+template <int KIND>
+void export_sel(bpe_ctx *c, ExportState *X, void *d_out) {
+    const int64_t grid = std::min<int64_t>((X->n_items + EXP_WAVES - 1) / EXP_WAVES, 1 << 16);
+    k_exp_sel<KIND><<<(unsigned)grid, EXP_WG, 0, c->stream>>>(c->d_ids, X->d_idx, X->n, X->d_le, X->d_se, X->d_cpre,
+                                                              X->d_soff, X->d_ipre, X->n_items, X->d_map, X->n_index,
+                                                              d_out, X->d_st);
+}
+
+// The values (kind: BPE_EXPORT_*, or EXP_NONE for the offsets alone) of the prepared call into d_out;
+// X->d_off holds the call's offsets afterwards.
+int export_emit(bpe_ctx *c, ExportState *X, int kind, void *d_out) {
+    hipStream_t s = c->stream;
+    X->emit_timed = false;
+    if (X->all ? (kind == EXP_NONE && X->le_done) : (kind == EXP_NONE || X->n_items == 0)) return BPE_OK;
+    HIP_TRY(hipEventRecord(X->ev[2], s));
+    if (X->all) {
+        if (kind == EXP_IDS) export_walk<EXP_IDS>(c, X, d_out, X->d_le, nullptr, nullptr);
+        else if (kind == EXP_VEC) export_walk<EXP_VEC>(c, X, d_out, X->d_le, nullptr, nullptr);
+        else if (kind == EXP_CODE) export_walk<EXP_CODE>(c, X, d_out, X->d_le, nullptr, nullptr);
+        else export_walk<EXP_NONE>(c, X, nullptr, X->d_le, nullptr, nullptr);
+        X->le_done = true;
+    } else {
+        if (kind == EXP_IDS) export_sel<EXP_IDS>(c, X, d_out);
+        else if (kind == EXP_VEC) export_sel<EXP_VEC>(c, X, d_out);
+        else export_sel<EXP_CODE>(c, X, d_out);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(X->ev[3], s));
+    X->emit_timed = true;
+    return BPE_OK;
+}
+
+// The kernels' time of a call, after its last sync.
+int export_timing(ExportState *X) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, X->ev[0], X->ev[1]));
+    X->st.kernel_ms += ms;
+    if (X->emit_timed) {
+        HIP_TRY(hipEventElapsedTime(&ms, X->ev[2], X->ev[3]));
+        X->st.kernel_ms += ms;
+    }
+    return BPE_OK;
+}
+
+size_t exp_align(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// Everything of a call before its values: the arguments, the region prefixes, for the selected
+// form the sample index, the chunk prefixes and the plan (the call's offsets and wave items), and
+// the hole check of the vectors where the host's counts cannot rule a hole out.  Sets X->needed.
+int export_prepare(bpe_ctx *c, ExportState *X, int kind, const int64_t *idx, int64_t n, const int32_t *tvi,
+                   int32_t n_index) {
+    if (kind != EXP_IDS && kind != EXP_VEC && kind != EXP_CODE) return fail(BPE_ERR_ARG, "bpe native: unknown export kind");
+    if (n < 0 || n >= 0x7FFFFFFE) return fail(BPE_ERR_ARG, "bpe native: bad export arguments");
+    if (kind == EXP_VEC && !tvi) return fail(BPE_ERR_STATE, "bpe native: no vector index (compactVectorIndex first)");
+    if (kind == EXP_VEC && n_index < 0) return fail(BPE_ERR_ARG, "bpe native: bad export arguments");
+    int rc;
+    if ((rc = settle(c))) return rc;
+    const int64_t ns = c->n_samples;
+    if (!idx && n != ns)
+        return fail(BPE_ERR_ARG, "bpe native: an export of every sample (idx NULL) takes n = the sample count");
+    for (int64_t k = 0; idx && k < n; ++k)
+        if (idx[k] < 0 || idx[k] >= ns) return fail(BPE_ERR_ARG, "bpe native: sample index out of range");
+    hipStream_t s = c->stream;
+    const bool all = !idx, vec = kind == EXP_VEC;
+    X->all = all;
+    X->le_done = false;
+    X->n = n;
+    X->n_items = 0;
+    X->n_index = vec ? n_index : 0;
+    // the engine's per-token counts are exact: a hole no present id maps to cannot be met
+    bool check = false;
+    for (size_t id = 0; vec && id < c->h_count.size() && !check; ++id)
+        check = c->h_count[id] > 0 && ((int64_t)id >= n_index || tvi[id] < 0);
+    geometry(c);
+    const size_t b_reg = exp_align((size_t)c->R * 8), b_le = exp_align((size_t)(ns + 1) * 8);
+    const size_t b_se = all ? 0 : exp_align((size_t)std::max<int64_t>(ns, 1) * 8);
+    const size_t b_cpre = all ? 0 : exp_align((size_t)std::max<int64_t>(c->n_chunks, 1) * 8);
+    const size_t b_n = all ? 0 : exp_align((size_t)(n + 1) * 8);
+    const size_t b_map = vec ? exp_align((size_t)std::max<int32_t>(n_index, 1) * 4) : 0;
+    if ((rc = export_grow(c, &X->d_buf, &X->buf_bytes, 2 * b_reg + b_le + b_se + b_cpre + 3 * b_n + b_map))) return rc;
+    char *p = X->d_buf;
+    auto take = [&p](size_t bytes) {
+        char *q = p;
+        p += bytes;
+        return q;
+    };
+    X->d_live = reinterpret_cast<int64_t *>(take(b_reg));
+    X->d_seps = reinterpret_cast<int64_t *>(take(b_reg));
+    X->d_le = reinterpret_cast<int64_t *>(take(b_le));
+    X->d_se = reinterpret_cast<int64_t *>(take(b_se));
+    X->d_cpre = reinterpret_cast<int64_t *>(take(b_cpre));
+    X->d_idx = reinterpret_cast<int64_t *>(take(b_n));
+    X->d_soff = reinterpret_cast<int64_t *>(take(b_n));
+    X->d_ipre = reinterpret_cast<int64_t *>(take(b_n));
+    X->d_map = vec ? reinterpret_cast<int32_t *>(take(b_map)) : nullptr;
+    X->d_off = all ? X->d_le : X->d_soff;
+    if (vec && n_index) HIP_TRY(hipMemcpyAsync(X->d_map, tvi, (size_t)n_index * 4, hipMemcpyHostToDevice, s));
+    if (!all && n) HIP_TRY(hipMemcpyAsync(X->d_idx, idx, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(X->d_le, 0, 8, s));
+    HIP_TRY(hipMemsetAsync(X->d_st, 0xFF, 8, s));
+    HIP_TRY(hipEventRecord(X->ev[0], s));
+    const bool empty = !all && n == 0;   // (nothing selected: off[0] = 0 is the whole answer)
+    if (empty) HIP_TRY(hipMemsetAsync(X->d_soff, 0, 8, s));
+    if (!empty) {
+        k_census<<<(c->R + 3) / 4, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, X->d_live, X->d_seps);
+        k_scan_pair<<<1, 1024, 0, s>>>(c->R, X->d_live, X->d_seps);
+    }
+    X->needed = all ? c->n_live : 0;
+    if (!all && n) {
+        export_walk<EXP_NONE>(c, X, nullptr, X->d_le, X->d_se, X->d_cpre);
+        k_exp_plan<<<(unsigned)((n + 1 + 255) / 256), 256, 0, s>>>(X->d_idx, n, X->d_le, X->d_se, X->d_soff, X->d_ipre);
+        k_scan_pair<<<1, 1024, 0, s>>>((int)(n + 1), X->d_soff, X->d_ipre);
+        HIP_TRY(hipGetLastError());
+        int64_t tot[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(&tot[0], X->d_soff + n, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&tot[1], X->d_ipre + n, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        X->needed = tot[0];
+        X->n_items = tot[1];
+    }
+    if (check && !empty) {
+        if (all) {
+            export_walk<EXP_CHECK>(c, X, nullptr, X->d_le, nullptr, nullptr);
+            X->le_done = true;
+        } else if (X->n_items) {
+            export_sel<EXP_CHECK>(c, X, nullptr);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(X->ev[1], s));
+    if (check && !empty) {
+        unsigned long long key = ~0ull;
+        HIP_TRY(hipMemcpyAsync(&key, X->d_st, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (key != ~0ull) {
+            const int64_t pos = (int64_t)(key >> 16);
+            std::vector<int64_t> off((size_t)n + 1);
+            HIP_TRY(hipMemcpyAsync(off.data(), X->d_off, off.size() * 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const int64_t k = (int64_t)(std::upper_bound(off.begin(), off.end(), pos) - off.begin()) - 1;
+            char msg[128];
+            std::snprintf(msg, sizeof msg, "unknown token index: %lld (sample %lld, position %lld)",
+                          (long long)(key & 0xFFFF), (long long)k, (long long)(pos - off[(size_t)std::max<int64_t>(k, 0)]));
+            return fail(BPE_ERR_VOCAB, msg);
+        }
+    }
+    return BPE_OK;
+}
+
+int export_samples(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                   void *out, int64_t cap, int64_t *off_out, int64_t *needed_out, bool dev) {
+    if (!c || cap < 0 || !off_out || (cap && !out) || (dev && !needed_out))
+        return fail(BPE_ERR_ARG, "bpe native: bad export_samples arguments");
+    const size_t esize = kind == EXP_CODE ? 2 : 4;
+    if (dev && (((uintptr_t)out & (esize - 1)) || ((uintptr_t)off_out & 7)))
+        return fail(BPE_ERR_ARG, "bpe native: misaligned export buffer");
+    int rc = set_device(c);
+    if (rc) return rc;
+    ExportState *X;
+    if ((rc = export_state(c, &X))) return rc;
+    X->st.calls++;
+    hipStream_t s = c->stream;
+    ExportSync guard{s};
+    if ((rc = export_prepare(c, X, kind, idx, n, tvi, n_index))) return rc;
+    const int64_t needed = X->needed;
+    const bool fits = needed <= cap;
+    void *d_out = out;
+    if (!dev && fits && needed) {
+        if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, (size_t)needed * esize))) return rc;
+        d_out = X->d_vals;
+    }
+    if ((rc = export_emit(c, X, fits ? kind : EXP_NONE, d_out))) return rc;
+    HIP_TRY(hipMemcpyAsync(off_out, X->d_off, (size_t)(n + 1) * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (!dev && fits && needed)
+        HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)needed * esize, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = export_timing(X))) return rc;
+    if (needed_out) *needed_out = needed;
+    if (!fits) {
+        char msg[128];
+        std::snprintf(msg, sizeof msg, "bpe native: export needs %lld values, the buffer holds %lld",
+                      (long long)needed, (long long)cap);
+        return fail(BPE_ERR_ARG, msg);
+    }
+    X->st.samples += n;
+    X->st.values += needed;
+    return BPE_OK;
+}
+
+int export_text(bpe_ctx *c, bpe_decoder *D, const int64_t *idx, int64_t n, uint16_t *units, int64_t cap,
+                int64_t *off_out, int64_t *needed_out, bool dev) {
+    if (!c || cap < 0 || !off_out || (cap && !units) || (dev && !needed_out))
+        return fail(BPE_ERR_ARG, "bpe native: bad export_text_batch arguments");
+    if (!D) return fail(BPE_ERR_ARG, "bpe native: null decoder");
+    int dec_device = -1;
+    int rc = decoder_device(D, &dec_device);
+    if (rc) return rc;
+    if (dec_device != c->device) return fail(BPE_ERR_ARG, "bpe native: the decoder is on another device than the context");
+    if ((rc = set_device(c))) return rc;
+    ExportState *X;
+    if ((rc = export_state(c, &X))) return rc;
+    X->st.calls++;
+    hipStream_t s = c->stream;
+    ExportSync guard{s};
+    if ((rc = export_prepare(c, X, EXP_IDS, idx, n, nullptr, 0))) return rc;
+    const int64_t n_ids = X->needed;
+    // scratch: [ids: 4 B per token | the host form's n + 1 unit offsets and units_cap units]
+    const size_t b_ids = exp_align((size_t)std::max<int64_t>(n_ids, 1) * 4), b_ooff = dev ? 0 : exp_align((size_t)(n + 1) * 8);
+    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, b_ids + b_ooff + (dev ? 0 : (size_t)cap * 2)))) return rc;
+    int32_t *d_ids = reinterpret_cast<int32_t *>(X->d_vals);
+    int64_t *d_ooff = dev ? off_out : reinterpret_cast<int64_t *>(X->d_vals + b_ids);
+    uint16_t *d_units = dev ? units : (cap ? reinterpret_cast<uint16_t *>(X->d_vals + b_ids + b_ooff) : nullptr);
+    if ((rc = export_emit(c, X, EXP_IDS, d_ids))) return rc;
+    // Two streams, no events: the ids and their offsets are complete before the decoder starts (this
+    // sync), and the decoder's device form synchronises its own stream before it returns.
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = export_timing(X))) return rc;
+    int64_t dneed = -1;   // (set by the decoder once its offsets are written)
+    const int drc = bpe_decode_batch_device(D, BPE_DECODE_IDS, d_ids, X->d_off, n, d_units, cap, d_ooff, &dneed);
+    const std::string dmsg = g_err;
+    if ((rc = set_device(c))) return rc;
+    if (!dev && dneed >= 0) {
+        HIP_TRY(hipMemcpyAsync(off_out, d_ooff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (drc == BPE_OK && dneed)
+            HIP_TRY(hipMemcpyAsync(units, d_units, (size_t)dneed * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (needed_out && dneed >= 0) *needed_out = dneed;
+    if (drc) return drc < 0 ? fail(drc, dmsg) : drc;   // (the decoder's own code and message)
+    X->st.samples += n;
+    X->st.values += n_ids;
+    return BPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpe_export_samples(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                       int32_t n_index, void *vals_out, int64_t vals_cap, int64_t *out_off) {
+    if (n >= 0 && vals_cap >= 0 && out_off && (!vals_cap || vals_out))
+        MULTI(export_samples(c->multi, kind, idx, n, to_vector_index, n_index, vals_out, vals_cap, out_off));
+    return export_samples(c, kind, idx, n, to_vector_index, n_index, vals_out, vals_cap, out_off, nullptr, false);
+}
+
+int bpe_export_samples_device(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                              int32_t n_index, void *d_vals_out, int64_t vals_cap, int64_t *d_out_off,
+                              int64_t *needed) {
+    if (c && c->multi)
+        return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
+                                 "(its shards sit on different devices: take the host form)");
+    return export_samples(c, kind, idx, n, to_vector_index, n_index, d_vals_out, vals_cap, d_out_off, needed, true);
+}
+
+int bpe_export_text_batch(bpe_ctx *c, bpe_decoder *dec, const int64_t *idx, int64_t n, uint16_t *units_out,
+                          int64_t units_cap, int64_t *out_off) {
+    if (dec && n >= 0 && units_cap >= 0 && out_off && (!units_cap || units_out))
+        MULTI(export_text_batch(c->multi, dec, idx, n, units_out, units_cap, out_off));
+    return export_text(c, dec, idx, n, units_out, units_cap, out_off, nullptr, false);
+}
+
+int bpe_export_text_batch_device(bpe_ctx *c, bpe_decoder *dec, const int64_t *idx, int64_t n, uint16_t *d_units_out,
+                                 int64_t units_cap, int64_t *d_out_off, int64_t *needed) {
+    if (c && c->multi)
+        return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
+                                 "(its shards sit on different devices: take the host form)");
+    return export_text(c, dec, idx, n, d_units_out, units_cap, d_out_off, needed, true);
+}
+
+int bpe_get_export_stats(bpe_ctx *c, bpe_export_stats *out) {
+    if (out) MULTI(get_export_stats(c->multi, out));
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = c->exp ? c->exp->st : bpe_export_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_export_stats(bpe_ctx *c) {
+    MULTI(reset_export_stats(c->multi));
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    if (c->exp) c->exp->st = bpe_export_stats{};
     return BPE_OK;
 }
 

@@ -71,6 +71,7 @@ struct bpe_multi {
     std::vector<std::vector<int32_t>> staged;            // samples not yet on a device
     bpe_ingest_stats ing{};                              // text ingest calls (kernel_ms: the shards')
     bpe_append_stats app{};                              // sample-batch and restore calls (kernel_ms: the shards')
+    bpe_export_stats exp{};                              // export calls (kernel_ms: the shards')
     bool distributed = false;
     // the maintained state (every shard holds the global tables, bpe_set_global_counts), and the
     // host-protocol iterations in a row that needed exact cold counts (two: enter that state)
@@ -873,6 +874,133 @@ int multi_read_samples(bpe_multi *m, const int64_t *idx, int64_t n, int32_t *ids
             const int64_t k = slot[r][j];
             std::copy(ids[r].begin() + offs[r][j], ids[r].begin() + offs[r][j + 1], ids_out + off[k]);
         }
+    return BPE_OK;
+}
+
+// ---- corpus out ---------------------------------------------------------------------------------------
+// The host forms of the export, shard by shard.  Every shard is asked twice: for its offsets first
+// (the sizing call, which also makes every check: a hole of the vector index fails here, before
+// anything is written), then, once the whole answer is known to fit, for its values.
+namespace {
+
+// The shard's failure `unknown token index: N (sample K, position I)` with K the place among the
+// samples asked of that shard: K in the caller's list comes from `place`.
+bool parse_hole(long long *id, long long *k, long long *pos) {
+    char buf[256];
+    bpe_last_error(buf, sizeof buf);
+    return std::sscanf(buf, "unknown token index: %lld (sample %lld, position %lld)", id, k, pos) == 3;
+}
+
+}  // namespace
+
+int multi_export_samples(bpe_multi *m, int kind, const int64_t *idx, int64_t n, const int32_t *tvi,
+                         int32_t n_index, void *vals_out, int64_t cap, int64_t *out_off) {
+    MTRY(distribute(m));
+    m->exp.calls++;
+    if (kind != BPE_EXPORT_IDS && kind != BPE_EXPORT_VECTORS && kind != BPE_EXPORT_CODE)
+        return bpe_fail(BPE_ERR_ARG, "bpe native: unknown export kind");
+    if (kind == BPE_EXPORT_VECTORS && !tvi)
+        return bpe_fail(BPE_ERR_STATE, "bpe native: no vector index (compactVectorIndex first)");
+    std::vector<int64_t> first(m->n + 1, 0);
+    for (int r = 0; r < m->n; ++r) {
+        int64_t a = 0;
+        MTRY(bpe_corpus_size(m->sh[r], &a, nullptr));
+        first[r + 1] = first[r] + a;
+    }
+    if (!idx && n != first[m->n])
+        return bpe_fail(BPE_ERR_ARG, "bpe native: an export of every sample (idx NULL) takes n = the sample count");
+    // per shard: its requested samples (local indices) and where each goes in the answer
+    std::vector<std::vector<int64_t>> local(m->n), place(m->n);
+    for (int64_t k = 0; idx && k < n; ++k) {
+        if (idx[k] < 0 || idx[k] >= first[m->n])
+            return bpe_fail(BPE_ERR_ARG, "bpe native: sample index out of range");
+        const int r = (int)(std::upper_bound(first.begin(), first.end(), idx[k]) - first.begin()) - 1;
+        local[r].push_back(idx[k] - first[r]);
+        place[r].push_back(k);
+    }
+    const size_t esize = kind == BPE_EXPORT_CODE ? 2 : 4;
+    std::vector<std::vector<int64_t>> offs(m->n);
+    long long bad_id = 0, bad_k = -1, bad_pos = 0;
+    for (int r = 0; r < m->n; ++r) {
+        const int64_t q = idx ? (int64_t)local[r].size() : first[r + 1] - first[r];
+        offs[r].assign((size_t)q + 1, 0);
+        if (idx && !q) continue;
+        const int rc = bpe_export_samples(m->sh[r], kind, idx ? local[r].data() : nullptr, q, tvi, n_index, nullptr, 0,
+                                          offs[r].data());
+        if (rc == BPE_ERR_VOCAB) {
+            long long id, k, pos;
+            if (!parse_hole(&id, &k, &pos)) return rc;
+            const long long kk = idx ? place[r][(size_t)k] : first[r] + k;
+            if (bad_k < 0 || kk < bad_k) bad_id = id, bad_k = kk, bad_pos = pos;
+            if (!idx) break;   // (corpus order: the first shard that fails holds the first failure)
+        } else if (rc < 0 && !(rc == BPE_ERR_ARG && offs[r][(size_t)q] > 0)) {
+            return rc;   // (BPE_ERR_ARG with offsets: the sizing call's answer)
+        }
+    }
+    if (bad_k >= 0) {
+        char msg[128];
+        std::snprintf(msg, sizeof msg, "unknown token index: %lld (sample %lld, position %lld)", bad_id, bad_k, bad_pos);
+        return bpe_fail(BPE_ERR_VOCAB, msg);
+    }
+    std::vector<int64_t> len((size_t)n, 0);
+    for (int r = 0; r < m->n; ++r)
+        for (size_t j = 0; j + 1 < offs[r].size(); ++j)
+            len[(size_t)(idx ? place[r][j] : first[r] + (int64_t)j)] = offs[r][j + 1] - offs[r][j];
+    out_off[0] = 0;
+    for (int64_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + len[(size_t)k];
+    if (cap < out_off[n]) {
+        char msg[128];
+        std::snprintf(msg, sizeof msg, "bpe native: export needs %lld values, the buffer holds %lld",
+                      (long long)out_off[n], (long long)cap);
+        return bpe_fail(BPE_ERR_ARG, msg);
+    }
+    char *out = static_cast<char *>(vals_out);
+    std::vector<char> tmp;
+    for (int r = 0; r < m->n; ++r) {
+        const int64_t q = (int64_t)offs[r].size() - 1, need = offs[r][(size_t)q];
+        if (!need) continue;
+        if (!idx) {   // (the shard's samples are one run of the answer)
+            MTRY(bpe_export_samples(m->sh[r], kind, nullptr, q, tvi, n_index, out + (size_t)out_off[first[r]] * esize, need,
+                                    offs[r].data()));
+            continue;
+        }
+        tmp.resize((size_t)need * esize);
+        MTRY(bpe_export_samples(m->sh[r], kind, local[r].data(), q, tvi, n_index, tmp.data(), need, offs[r].data()));
+        for (int64_t j = 0; j < q; ++j)
+            std::memcpy(out + (size_t)out_off[place[r][(size_t)j]] * esize, tmp.data() + (size_t)offs[r][(size_t)j] * esize,
+                        (size_t)(offs[r][(size_t)j + 1] - offs[r][(size_t)j]) * esize);
+    }
+    m->exp.samples += n;
+    m->exp.values += out_off[n];
+    return BPE_OK;
+}
+
+int multi_export_text_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint16_t *units_out,
+                            int64_t units_cap, int64_t *out_off) {
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    int rc = multi_export_samples(m, BPE_EXPORT_IDS, idx, n, nullptr, 0, nullptr, 0, off.data());
+    if (rc < 0 && !(rc == BPE_ERR_ARG && off[(size_t)n] > 0)) return rc;
+    std::vector<int32_t> ids((size_t)std::max<int64_t>(off[(size_t)n], 1));
+    if (off[(size_t)n]) {
+        m->exp.calls--;   // (one call, asked twice)
+        MTRY(multi_export_samples(m, BPE_EXPORT_IDS, idx, n, nullptr, 0, ids.data(), off[(size_t)n], off.data()));
+    }
+    return bpe_decode_batch(dec, BPE_DECODE_IDS, ids.data(), off.data(), n, units_out, units_cap, out_off);
+}
+
+int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out) {
+    *out = m->exp;
+    for (auto s : m->sh) {
+        bpe_export_stats t{};
+        MTRY(bpe_get_export_stats(s, &t));
+        out->kernel_ms += t.kernel_ms;
+    }
+    return BPE_OK;
+}
+
+int multi_reset_export_stats(bpe_multi *m) {
+    m->exp = bpe_export_stats{};
+    for (auto s : m->sh) MTRY(bpe_reset_export_stats(s));
     return BPE_OK;
 }
 

@@ -28,6 +28,12 @@ int multi_restore_text_batch(bpe_multi *m, bpe_encoder *enc, const uint16_t *uni
 int multi_token_counts(bpe_multi *m, int64_t *counts, int64_t cap);
 int multi_get_append_stats(bpe_multi *m, bpe_append_stats *out);
 int multi_reset_append_stats(bpe_multi *m);
+int multi_export_samples(bpe_multi *m, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                         int32_t n_index, void *vals_out, int64_t vals_cap, int64_t *out_off);
+int multi_export_text_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint16_t *units_out,
+                            int64_t units_cap, int64_t *out_off);
+int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out);
+int multi_reset_export_stats(bpe_multi *m);
 int multi_clear_corpus(bpe_multi *m);
 int multi_corpus_size(bpe_multi *m, int64_t *n_samples, int64_t *n_tokens);
 int multi_read_corpus(bpe_multi *m, int32_t *ids_out, int64_t ids_cap, int64_t *sample_off,
@@ -74,6 +80,8 @@ int ingest_kernel_ms(bpe_ctx *c, double *ms, bool reset);
 // (bpe_encode.hip) the device an encoder lives on (the restore checks it against the context's; the
 // encoder's struct stays private)
 int encoder_device(bpe_encoder *enc, int *device);
+// (bpe_decode.hip) the same for a decoder (the text export checks it)
+int decoder_device(bpe_decoder *dec, int *device);
 
 // error reporting shared with bpe_engine.hip
 int bpe_fail(int code, const char *msg);

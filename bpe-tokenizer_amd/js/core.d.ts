@@ -77,6 +77,17 @@ export declare class BPETokenizer {
    * with BPE_ENCODE_DEVICE=0) that loop runs in JS.
    */
   restoreToCorpusBatch(contents: string[]): void
+  /**
+   * the trained corpus as vectors on the GPU: `encodeToVector` of every training sample (of the samples
+   * `indices`, in that order, when given) without encoding the raw text again; throws
+   * `unknown token index: N`.  Without the addon (or with BPE_ENCODE_DEVICE=0) the map runs in JS.
+   */
+  corpusToVectorBatch(indices?: number[]): Int32Array[]
+  /**
+   * the trained corpus back as text on the GPU: the contents of the samples (`indices` when given).
+   * Without the addon (or with BPE_ENCODE_DEVICE=0) the chars are joined in JS.
+   */
+  corpusToTextBatch(indices?: number[]): string[]
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

@@ -30,6 +30,9 @@ const {
   textsToUnits,
   syncEngineChars,
   idsToCode,
+  corpusCodesOnDevice,
+  corpusVectorsOnDevice,
+  corpusTextsOnDevice,
 } = require('./native')
 
 /** @description file separator (core.ts:36) */
@@ -72,6 +75,13 @@ function replaceAll(s, from, to) {
 /** a merge_tokens entry [a, b, c] -> its token indices (the encoder's (a, b, c) triple) */
 function tokenTriple(merge) {
   return [merge[0].index, merge[1].index, merge[2].index]
+}
+
+/** the samples `indices` (every sample without them) as token ids: [Int32Array, offsets] */
+function corpusIds(engine, indices) {
+  let n = loadNative()
+  if (indices === undefined || indices === null) return n.readCorpus(engine)
+  return n.readSamples(engine, Float64Array.from(indices))
 }
 
 class BPETokenizer {
@@ -151,19 +161,63 @@ class BPETokenizer {
    */
   get corpus_in_code() {
     if (!this._engine) return []
-    let [ids, offsets] = loadNative().readCorpus(this.engine())
+    let engine = this.engine()
+    // the device's code form (bpe_export_samples, BPE_EXPORT_CODE): a string per sample from its units
+    let codes = corpusCodesOnDevice(engine, null)
+    if (codes) return codes
+    let [ids, offsets] = loadNative().readCorpus(engine)
     let samples = []
-    for (let s = 0; s + 1 < offsets.length; s++) {
-      let code = ''
-      for (let i = offsets[s]; i < offsets[s + 1]; i += 8192) {
-        let end = Math.min(offsets[s + 1], i + 8192)
-        let part = []
-        for (let j = i; j < end; j++) part.push(ids[j] + 1)
-        code += String.fromCodePoint.apply(null, part)
-      }
-      samples.push(code)
-    }
+    for (let s = 0; s + 1 < offsets.length; s++) samples.push(idsToCode(ids, offsets[s], offsets[s + 1]))
     return samples
+  }
+
+  /**
+   * @description the trained corpus as vectors, on the GPU (bpe_export_samples, BPE_EXPORT_VECTORS):
+   * `encodeToVector` of every training sample (of the samples `indices`, in that order, when given)
+   * without encoding the raw text again: the corpus holds exactly those tokens.  Throws the
+   * reference's `unknown token index: N` for a token the vector index skips.  Without the addon
+   * (or with BPE_ENCODE_DEVICE=0) the ids are read back and mapped in JS, with the same results.
+   */
+  corpusToVectorBatch(indices) {
+    if (!this._engine) return []
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let engine = this.engine()
+    let out = corpusVectorsOnDevice(this, engine, indices)
+    if (out) return out
+    let { to_vector_index } = this
+    let [ids, offsets] = corpusIds(engine, indices)
+    out = []
+    for (let s = 0; s + 1 < offsets.length; s++) {
+      let vector = new Int32Array(offsets[s + 1] - offsets[s])
+      for (let i = offsets[s], p = 0; i < offsets[s + 1]; i++) {
+        if (!(ids[i] in to_vector_index)) throw new Error(`unknown token index: ${ids[i]}`)
+        vector[p++] = to_vector_index[ids[i]]
+      }
+      out.push(vector)
+    }
+    return out
+  }
+
+  /**
+   * @description the trained corpus back as text, on the GPU (bpe_export_text_batch): the chars of
+   * every sample's tokens (of the samples `indices` when given), i.e. the contents added, through the
+   * device decoder that follows the token table.  Without the addon (or with BPE_ENCODE_DEVICE=0) the
+   * ids are read back and the chars joined in JS, with the same results.
+   */
+  corpusToTextBatch(indices) {
+    if (!this._engine) return []
+    let engine = this.engine()
+    let out = corpusTextsOnDevice(this, engine, indices)
+    if (out) return out
+    let { token_table } = this
+    let [ids, offsets] = corpusIds(engine, indices)
+    out = []
+    for (let s = 0; s + 1 < offsets.length; s++) {
+      let parts = []
+      for (let i = offsets[s]; i < offsets[s + 1]; i++) parts.push(token_table[ids[i]].chars)
+      out.push(parts.join(''))
+    }
+    return out
   }
 
   set corpus_in_code(samples) {

@@ -34,6 +34,7 @@ const {
   minWeightArg,
   encodeIdsMaybeOnDevice,
   idsToCode,
+  corpusCodesOnDevice,
 } = require('./native')
 const { EOF } = require('./core')
 
@@ -419,10 +420,15 @@ class BPETokenizerDB {
     let changed = []
     for (let i = 0; i < lens.length; i++) if (lens[i] !== this._lens[i]) changed.push(i)
     if (changed.length === 0) return
-    let [ids, off] = n.readSamples(this._engine, Float64Array.from(changed))
+    // the changed rows in the device's code form (bpe_export_samples, BPE_EXPORT_CODE): a string per
+    // row from its units; without the addon (or with BPE_ENCODE_DEVICE=0) from the ids, token by token
+    let codes = corpusCodesOnDevice(this._engine, changed)
+    let ids, off
+    if (!codes) [ids, off] = n.readSamples(this._engine, Float64Array.from(changed))
     for (let k = 0; k < changed.length; k++) {
       let i = changed[k]
-      this.update_corpus.run({ id: this._rows[i], content_code: idsToCode(ids, off[k], off[k + 1]) })
+      let content_code = codes ? codes[k] : idsToCode(ids, off[k], off[k + 1])
+      this.update_corpus.run({ id: this._rows[i], content_code })
       this._lens[i] = lens[i]
     }
   }

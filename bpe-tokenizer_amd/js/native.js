@@ -33,6 +33,14 @@ function loadNativeRestore() {
 }
 
 // the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
+// the export's addon (addon/bpe_export_napi.node: exportSamples, exportText on an engine handle)
+let nativeExport = null
+let nativeExportMissing = false
+function loadNativeExport() {
+  if (!nativeExport) nativeExport = require(path.join(__dirname, '..', 'addon', 'bpe_export_napi.node'))
+  return nativeExport
+}
+
 let nativeText = null
 function loadNativeText() {
   if (!nativeText) nativeText = require(path.join(__dirname, '..', 'addon', 'bpe_text_napi.node'))
@@ -413,6 +421,78 @@ function syncEngineChars(owner, engine) {
   owner._eng_nchars = keys.length
 }
 
+/**
+ * The export's addon, or null when the callers are to take their JS route: BPE_ENCODE_DEVICE=0, or the
+ * addon is not built (with BPE_ENCODE_DEVICE=1 that is an error).
+ */
+function exportAddon() {
+  if (ENCODE_DEVICE === '0' || nativeExportMissing) return null
+  try {
+    return loadNativeExport()
+  } catch (e) {
+    if (ENCODE_DEVICE === '1') throw e
+    nativeExportMissing = true
+    return null
+  }
+}
+
+/** BPE_EXPORT_* (include/bpe.h) */
+const EXPORT_IDS = 0
+const EXPORT_VECTORS = 1
+const EXPORT_CODE = 2
+
+/** sample indices for the export's addon: null (every sample) or a Float64Array */
+function exportIndices(indices) {
+  return indices === undefined || indices === null ? null : Float64Array.from(indices)
+}
+
+/**
+ * The code strings (`corpus_in_code` / `content_code`: unit = token index + 1) of the samples
+ * `indices` (null: every sample) from the device's code form, each string made from its UTF-16 units
+ * in one call -> string[], or null when there is no addon to ask (exportAddon).
+ */
+function corpusCodesOnDevice(engine, indices) {
+  let addon = exportAddon()
+  if (!addon) return null
+  let [units, off] = addon.exportSamples(engine, EXPORT_CODE, exportIndices(indices), null)
+  let buf = Buffer.from(units.buffer, units.byteOffset, units.byteLength)
+  let out = new Array(off.length - 1)
+  for (let s = 0; s + 1 < off.length; s++) out[s] = buf.toString('utf16le', 2 * off[s], 2 * off[s + 1])
+  return out
+}
+
+/**
+ * The samples `indices` (null: every sample) as vectors through `owner.to_vector_index` (holes go as
+ * -1) -> Int32Array[], or null when there is no addon to ask.  The device's `unknown token index: N
+ * (sample K, position I)` is thrown as the reference's `unknown token index: N`.
+ */
+function corpusVectorsOnDevice(owner, engine, indices) {
+  let addon = exportAddon()
+  if (!addon) return null
+  let index = new Int32Array(owner.to_vector_index.length).fill(-1)
+  owner.to_vector_index.forEach((v, i) => {
+    index[i] = v
+  })
+  let vals, off
+  try {
+    ;[vals, off] = addon.exportSamples(engine, EXPORT_VECTORS, exportIndices(indices), index)
+  } catch (e) {
+    let m = /^unknown token index: (\d+) \(sample \d+, position \d+\)$/.exec(String(e && e.message))
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    throw e
+  }
+  let out = new Array(off.length - 1)
+  for (let s = 0; s + 1 < off.length; s++) out[s] = vals.slice(off[s], off[s + 1])
+  return out
+}
+
+/** the samples `indices` (null: every sample) as text through the owner's device decoder, or null */
+function corpusTextsOnDevice(owner, engine, indices) {
+  let addon = exportAddon()
+  if (!addon) return null
+  return addon.exportText(engine, syncDecoder(owner), exportIndices(indices))
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -463,4 +543,8 @@ module.exports = {
   textsToUnits,
   syncEngineChars,
   idsToCode,
+  loadNativeExport,
+  corpusCodesOnDevice,
+  corpusVectorsOnDevice,
+  corpusTextsOnDevice,
 }

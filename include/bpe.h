@@ -688,6 +688,74 @@ int bpe_decode_batch_device(bpe_decoder *dec, int kind, const int32_t *d_vals, c
 int bpe_decoder_get_stats(bpe_decoder *dec, bpe_decoder_stats *out);
 int bpe_decoder_reset_stats(bpe_decoder *dec);
 
+/* ---- corpus out ----------------------------------------------------------------------------------
+ * The trained corpus back out of the device layout: samples as token ids (`corpus_in_code` as ids,
+ * core.ts:106), as vector indices (encodeToVector of every sample, core.ts:434-444, without encoding
+ * the raw text again: what example/skip-gram.ts consumes), as code units (the `corpus_in_code` /
+ * `content_code` strings themselves: unit = id + 1, at most BPE_MAX_VOCAB, so 16 bits hold it), or,
+ * through a decoder, as UTF-16 text (the opposite of bpe_restore_text_batch).
+ *
+ * bpe_export_samples: idx is a host array of n sample indices, in any order, repeats allowed,
+ * n == 0 fine; idx == NULL means every sample in corpus order, and n must then be the context's
+ * sample count (BPE_ERR_ARG).  An index outside [0, n_samples) gives BPE_ERR_ARG with nothing
+ * written.  The samples' values go back to back into vals_out (int32_t, or uint16_t for
+ * BPE_EXPORT_CODE; vals_cap counts values) and n + 1 offsets into out_off (out_off[0] = 0).
+ * Capacity follows bpe_decode_batch: when out_off[n] exceeds vals_cap the offsets are written, no
+ * value is, and BPE_ERR_ARG comes back (vals_out == NULL with vals_cap 0 is the sizing call).
+ * BPE_EXPORT_VECTORS takes to_vector_index of compactVectorIndex (core.ts:222-241) as a host array
+ * with bpe_encoder_set_vector_index's rules: n_index entries, -1 for a hole, ids at or past n_index
+ * are holes; NULL gives BPE_ERR_STATE (the other kinds ignore both arguments).  A token that maps to
+ * a hole fails the whole call with BPE_ERR_VOCAB, nothing written to either output, and the message
+ *   unknown token index: N (sample K, position I)     (K: the place in idx; I: the place in the sample)
+ * for the first failing value in output order.  The engine's exact per-token counts rule that out on
+ * the host when no id with a nonzero count is a hole; only otherwise does a check pass over the
+ * samples run before anything is written.
+ * An export only reads: it settles a pending merge as bpe_sample_lengths does and leaves the corpus,
+ * the counts, the mode, the digest plane, the hit lists and every other stat as they were, so a
+ * bpe_merge_until after it gives the merges it would have given without it.
+ * bpe_export_samples_device is the same with the outputs on the context's device (any 4-byte aligned
+ * value pointer, 2-byte for BPE_EXPORT_CODE; idx and to_vector_index stay host arrays): no value
+ * touches the host.  *needed (a host int64) receives the number of values.  It runs on the context's
+ * stream and synchronises before returning.
+ *
+ * bpe_export_text_batch: the samples' ids go into scratch on the context (4 B per token and 8 B per
+ * sample, grow-only) and through `dec` (bpe_decode_batch_device with BPE_DECODE_IDS): units_out and
+ * out_off as bpe_decode_batch fills them, the decoder's errors, messages and sizing behaviour as
+ * they are (a decoder that knows fewer tokens than the corpus holds: `unknown token index: V (text K,
+ * position I)`).  dec must be on the context's device (BPE_ERR_ARG; NULL too).  In the device form no
+ * id and no unit touches the host; it runs on the context's stream, then the decoder's.
+ *
+ * A multi-device context takes the host forms shard by shard into the caller's buffer (the indices
+ * routed to the shards that hold them, as bpe_read_samples routes them; its text export decodes
+ * through the decoder's host form); the device forms refuse it with BPE_ERR_ARG, since the shards
+ * sit on different devices.
+ * The kernels stage one chunk of BPE_EXPORT_TILE corpus slots per wave (csrc/bpe_export.hip.h;
+ * exported for the tests); the prefixes come from the scan of bpe_sample_lengths, one block of
+ * BPE_EXPORT_SCAN_THREADS threads, each owning a run of consecutive entries. */
+#define BPE_EXPORT_TILE 256           /* corpus slots per wave step of the export kernels */
+#define BPE_EXPORT_SCAN_THREADS 1024  /* threads of the one-block scan of the prefixes */
+#define BPE_EXPORT_IDS     0   /* int32 token ids (what bpe_read_samples returns) */
+#define BPE_EXPORT_VECTORS 1   /* int32 to_vector_index[id]: encodeToVector of the sample, core.ts:434-444 */
+#define BPE_EXPORT_CODE    2   /* uint16 units id + 1: the sample's corpus_in_code / content_code string */
+typedef struct {
+    int64_t calls;            /* export calls (sizing calls and failed calls count) */
+    int64_t samples;          /* samples of the calls that wrote their values */
+    int64_t values;           /* ... the values they wrote (tokens; for the text export too) */
+    double kernel_ms;         /* HIP-event time of the export's kernels (index, check and emit spans) */
+} bpe_export_stats;
+int bpe_export_samples(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n,
+                       const int32_t *to_vector_index, int32_t n_index,
+                       void *vals_out, int64_t vals_cap, int64_t *out_off);
+int bpe_export_samples_device(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n,
+                              const int32_t *to_vector_index, int32_t n_index,
+                              void *d_vals_out, int64_t vals_cap, int64_t *d_out_off, int64_t *needed);
+int bpe_export_text_batch(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *idx, int64_t n,
+                          uint16_t *units_out, int64_t units_cap, int64_t *out_off);
+int bpe_export_text_batch_device(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *idx, int64_t n,
+                                 uint16_t *d_units_out, int64_t units_cap, int64_t *d_out_off, int64_t *needed);
+int bpe_get_export_stats(bpe_ctx *ctx, bpe_export_stats *out);
+int bpe_reset_export_stats(bpe_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
