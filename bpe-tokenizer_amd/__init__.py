@@ -53,6 +53,10 @@ C_API = [
     'bpe_restore_text_batch_device', 'bpe_token_counts', 'bpe_get_append_stats', 'bpe_reset_append_stats',
     'bpe_export_samples', 'bpe_export_samples_device', 'bpe_export_text_batch', 'bpe_export_text_batch_device',
     'bpe_get_export_stats', 'bpe_reset_export_stats',
+    'bpe_encoder_utf8_to_utf16', 'bpe_encoder_utf8_to_utf16_device', 'bpe_encode_utf8_batch',
+    'bpe_encode_utf8_batch_device', 'bpe_add_utf8_batch', 'bpe_add_utf8_batch_device', 'bpe_restore_utf8_batch',
+    'bpe_restore_utf8_batch_device', 'bpe_encoder_get_utf8_stats', 'bpe_encoder_reset_utf8_stats',
+    'bpe_get_utf8_stats', 'bpe_reset_utf8_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -88,6 +92,7 @@ EXPORT_SCAN_THREADS = 1024   # BPE_EXPORT_SCAN_THREADS: threads of the one-block
 EXPORT_IDS = 0      # BPE_EXPORT_IDS: samples out as token ids
 EXPORT_VECTORS = 1  # BPE_EXPORT_VECTORS: ... as vector indices (encodeToVector of every sample)
 EXPORT_CODE = 2     # BPE_EXPORT_CODE: ... as uint16 code units id + 1 (corpus_in_code)
+UTF8_TILE = 4096    # BPE_UTF8_TILE: bytes per workgroup of the UTF-8 transcode (its scan round: TEXT_SCAN_ROUND)
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -198,6 +203,15 @@ class ExportStats(ctypes.Structure):
     """bpe_export_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('samples', ctypes.c_int64), ('values', ctypes.c_int64),
                 ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Utf8Stats(ctypes.Structure):
+    """bpe_utf8_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('bytes', ctypes.c_int64),
+                ('units', ctypes.c_int64), ('replaced', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -331,6 +345,23 @@ def lib():
                                          ctypes.c_int),
         'bpe_get_export_stats': ([vp, ctypes.POINTER(ExportStats)], ctypes.c_int),
         'bpe_reset_export_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_utf8_to_utf16': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_encoder_utf8_to_utf16_device': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p],
+                                             ctypes.c_int),
+        'bpe_encode_utf8_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p],
+                                  ctypes.c_int),
+        'bpe_encode_utf8_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                          i64p], ctypes.c_int),
+        'bpe_add_utf8_batch': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p, ctypes.c_int64],
+                               ctypes.c_int),
+        'bpe_add_utf8_batch_device': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p,
+                                       ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_utf8_batch': ([vp, vp, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_utf8_batch_device': ([vp, vp, vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_encoder_get_utf8_stats': ([vp, ctypes.POINTER(Utf8Stats)], ctypes.c_int),
+        'bpe_encoder_reset_utf8_stats': ([vp], ctypes.c_int),
+        'bpe_get_utf8_stats': ([vp, ctypes.POINTER(Utf8Stats)], ctypes.c_int),
+        'bpe_reset_utf8_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -591,6 +622,47 @@ class Engine:
                                                    units.data_ptr() if units.numel() else None,
                                                    off.data_ptr(), off.numel() - 1),
                'bpe_restore_text_batch_device')
+
+    # text as UTF-8 (include/bpe.h "text as UTF-8"): bytes in, transcoded on the device -----------------
+    def add_utf8_batch(self, texts, off=None, new_cap=1024):
+        """add_text for UTF-8: texts a list of bytes, or the flat form (uint8 array, int64 offsets).
+        Each text decodes as bytes.decode('utf-8', 'replace') does -> (new_chars, hist)."""
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        return self._add_text(lib().bpe_add_utf8_batch, 'bpe_add_utf8_batch', src.ctypes.data,
+                              off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1, new_cap)
+
+    def add_utf8_tensors(self, data, off, new_cap=1024):
+        """Device form (bpe_add_utf8_batch_device): data a torch uint8 tensor (any byte offset) and
+        off a torch int64 tensor on the context's device -> (new_chars, hist) as numpy arrays."""
+        data, off = _utf8_tensors(data, off, 'add_utf8_tensors')
+        return self._add_text(lib().bpe_add_utf8_batch_device, 'bpe_add_utf8_batch_device',
+                              data.data_ptr() if data.numel() else None, off.data_ptr(), off.numel() - 1, new_cap)
+
+    def restore_utf8_batch(self, enc, texts, off=None):
+        """restore_text for UTF-8: texts a list of bytes, or the flat form (uint8 array, int64 offsets)."""
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        _check(lib().bpe_restore_utf8_batch(self._ctx, enc._enc if enc is not None else None, src.ctypes.data,
+                                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1),
+               'bpe_restore_utf8_batch')
+
+    def restore_utf8_tensors(self, enc, data, off):
+        """Device form (bpe_restore_utf8_batch_device): torch uint8 bytes and int64 offsets on the
+        context's device; neither a unit nor an id comes to the host."""
+        data, off = _utf8_tensors(data, off, 'restore_utf8_tensors')
+        _check(lib().bpe_restore_utf8_batch_device(self._ctx, enc._enc if enc is not None else None,
+                                                   data.data_ptr() if data.numel() else None,
+                                                   off.data_ptr(), off.numel() - 1),
+               'bpe_restore_utf8_batch_device')
+
+    def utf8_stats(self):
+        s = Utf8Stats()
+        _check(lib().bpe_get_utf8_stats(self._ctx, ctypes.byref(s)), 'bpe_get_utf8_stats')
+        return s.as_dict()
+
+    def reset_utf8_stats(self):
+        _check(lib().bpe_reset_utf8_stats(self._ctx), 'bpe_reset_utf8_stats')
 
     def token_counts(self):
         """Occurrences of every token id in the corpus (int64; the engine's own exact counts)."""
@@ -1138,6 +1210,109 @@ class Encoder:
 
     def reset_text_stats(self):
         _check(lib().bpe_encoder_reset_text_stats(self._enc), 'bpe_encoder_reset_text_stats')
+
+
+    # text as UTF-8 (include/bpe.h "text as UTF-8"): bytes in, transcoded on the device -----------------
+    def utf8_to_utf16(self, texts, off=None):
+        """The transcode alone: texts a list of bytes, or the flat form (uint8 array, int64 offsets)
+        -> (units uint16, out_off int64).  Each text decodes as bytes.decode('utf-8', 'replace')."""
+        data, off = _utf8_flat(texts, off)
+        n = len(off) - 1
+        total = max(int(off[-1] - off[0]), 0) if n > 0 else 0
+        units = np.zeros(max(total, 1), dtype=np.uint16)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        src = data if data.size else np.zeros(1, np.uint8)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(lib().bpe_encoder_utf8_to_utf16(self._enc, src.ctypes.data, off.ctypes.data_as(i64p), n,
+                                               units.ctypes.data, units.size, out_off.ctypes.data_as(i64p)),
+               'bpe_encoder_utf8_to_utf16')
+        return units[:out_off[n]], out_off
+
+    def utf8_to_utf16_tensors(self, data, off):
+        """Device form (bpe_encoder_utf8_to_utf16_device): data a torch uint8 tensor (any byte offset)
+        and off a torch int64 tensor on the encoder's device -> (int16 tensor of the units, int64
+        offsets tensor), both on that device."""
+        import torch
+        data, off = _utf8_tensors(data, off, 'utf8_to_utf16_tensors', self.device)
+        n = off.numel() - 1
+        units = torch.empty(max(data.numel(), 1), dtype=torch.int16, device=data.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+        torch.cuda.synchronize(data.device)
+        need = ctypes.c_int64()
+        _check(lib().bpe_encoder_utf8_to_utf16_device(self._enc, data.data_ptr() if data.numel() else None,
+                                                      off.data_ptr(), n, units.data_ptr(), units.numel(),
+                                                      out_off.data_ptr(), ctypes.byref(need)),
+               'bpe_encoder_utf8_to_utf16_device')
+        return units[:need.value], out_off
+
+    def encode_utf8(self, texts, off=None, kind='vectors'):
+        """encode_text for UTF-8.  texts a list of bytes -> list of int32 arrays; the flat form
+        (uint8 array, int64 offsets) -> (values int32, out_off int64)."""
+        kind = self._KINDS[kind]
+        flat = off is not None
+        data, off = _utf8_flat(texts, off)
+        n = len(off) - 1
+        total = max(int(off[-1] - off[0]), 0) if n > 0 else 0
+        out = np.zeros(max(total, 1), dtype=np.int32)
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        src = data if data.size else np.zeros(1, np.uint8)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        _check(lib().bpe_encode_utf8_batch(self._enc, kind, src.ctypes.data, off.ctypes.data_as(i64p), n,
+                                           out.ctypes.data, out.size, out_off.ctypes.data_as(i64p)),
+               'bpe_encode_utf8_batch')
+        if flat:
+            return out[:out_off[n]], out_off
+        return [out[out_off[k]:out_off[k + 1]].copy() for k in range(n)]
+
+    def encode_utf8_tensors(self, data, off, kind='vectors'):
+        """Device form (bpe_encode_utf8_batch_device): torch uint8 bytes and int64 offsets on the
+        encoder's device -> (int32 tensor of the values, int64 offsets tensor), both on that device."""
+        import torch
+        kind = self._KINDS[kind]
+        data, off = _utf8_tensors(data, off, 'encode_utf8_tensors', self.device)
+        n = off.numel() - 1
+        vals = torch.empty(max(data.numel(), 1), dtype=torch.int32, device=data.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=data.device)
+        torch.cuda.synchronize(data.device)   # (the encoder runs on a stream of its own)
+        need = ctypes.c_int64()
+        _check(lib().bpe_encode_utf8_batch_device(self._enc, kind, data.data_ptr() if data.numel() else None,
+                                                  off.data_ptr(), n, vals.data_ptr(), data.numel(),
+                                                  out_off.data_ptr(), ctypes.byref(need)),
+               'bpe_encode_utf8_batch_device')
+        return vals[:need.value], out_off
+
+    def utf8_stats(self):
+        s = Utf8Stats()
+        _check(lib().bpe_encoder_get_utf8_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_utf8_stats')
+        return s.as_dict()
+
+    def reset_utf8_stats(self):
+        _check(lib().bpe_encoder_reset_utf8_stats(self._enc), 'bpe_encoder_reset_utf8_stats')
+
+
+def _utf8_flat(texts, off):
+    """A batch of UTF-8 texts as (uint8 array, int64 offsets): a list of bytes-like objects
+    (off None), or the flat form as it is."""
+    if off is not None:
+        return np.ascontiguousarray(texts, dtype=np.uint8).ravel(), np.ascontiguousarray(off, dtype=np.int64)
+    parts = [bytes(t) for t in texts]
+    off = np.zeros(len(parts) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in parts], out=off[1:])
+    return np.frombuffer(b''.join(parts), dtype=np.uint8), off
+
+
+def _utf8_tensors(data, off, what, device=None):
+    """Checks a device batch: a torch uint8 tensor (a view at any byte offset is fine) and int64
+    offsets on one device (`device`: which one)."""
+    import torch
+    if data.dtype != torch.uint8 or off.dtype != torch.int64:
+        raise BpeError('%s takes uint8 bytes and int64 offsets' % what, ERR_ARG)
+    if not (data.is_cuda and off.is_cuda and data.device == off.device) or \
+            (device is not None and data.device.index != device):
+        raise BpeError('%s takes tensors on the device of the call' % what, ERR_ARG)
+    data, off = data.contiguous(), off.contiguous()
+    torch.cuda.synchronize(data.device)   # (contexts and encoders run on streams of their own)
+    return data, off
 
 
 def _units(x):

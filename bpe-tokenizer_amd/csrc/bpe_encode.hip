@@ -471,6 +471,7 @@ k_text_ooff(const int64_t *__restrict__ ooff, const int64_t *__restrict__ seg_of
 }  // namespace
 
 #include "bpe_text.hip.h"   // the text front end and the vector back end (bpe_encode_text_batch)
+#include "bpe_utf8.hip.h"   // text as UTF-8: bytes -> units in front of it (bpe_encode_utf8_batch)
 
 struct bpe_encoder {
     int device = 0;
@@ -503,6 +504,8 @@ struct bpe_encoder {
     int32_t scratch_known = 0;
     bpe_encoder_stats st{};
     bpe_text_state txt;                       // the text form (bpe_encode_text_batch)
+    Utf8State u8;                             // text as UTF-8 (bpe_encoder_utf8_to_utf16 and what builds on it)
+    Utf8Call u8_pending;                      // a restore's transcode, counted when the restore is done
     // long texts in segments (BPE_LONG_SPLIT): first and last base id of every id (identity until
     // a merge makes it), the ids made so far, and the tables k_cuts reads (built and uploaded
     // with the rank table when dirty)
@@ -1640,6 +1643,28 @@ int encoder_device(bpe_encoder *E, int *device) {
     return BPE_OK;
 }
 
+// The restore from UTF-8 (bpe_engine.hip): the texts' units and offsets in the encoder's scratch,
+// on its device (units == NULL: on the host instead, for a multi-device context); the call's
+// numbers are counted by encoder_utf8_done once the restore has succeeded.
+int encoder_utf8_units(bpe_encoder *E, const uint8_t *bytes, const int64_t *off, int64_t n_texts, bool dev,
+                       const uint16_t **d_units, const int64_t **d_uoff, int64_t *n_units) {
+    if (!E || !d_units || !d_uoff || !n_units) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    ENC_TRY(hipSetDevice(E->device));
+    E->u8.st.calls++;
+    Utf8Call J;
+    J.bytes = bytes, J.off = off, J.n_texts = n_texts, J.dev = dev;
+    const int rc = u8_transcode(E->u8, E->stream, J);
+    if (rc) return rc;
+    *d_units = J.d_units;
+    *d_uoff = J.d_uoff;
+    *n_units = J.units;
+    J.h_off.clear();
+    E->u8_pending = J;
+    return BPE_OK;
+}
+
+void encoder_utf8_done(bpe_encoder *E) { u8_commit(E->u8, E->u8_pending); }
+
 extern "C" {
 
 int bpe_encoder_create(bpe_encoder **out, int device) {
@@ -1695,6 +1720,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     if (E->d_buf) (void)hipFree(E->d_buf);
     if (E->h_buf) (void)hipHostFree(E->h_buf);
     text_free(E);
+    u8_free(E->u8);
     if (E->ev0) (void)hipEventDestroy(E->ev0);
     if (E->ev1) (void)hipEventDestroy(E->ev1);
     for (int i = 0; i < 2; ++i)
@@ -1885,6 +1911,107 @@ int bpe_encode_text_batch_device(bpe_encoder *E, int kind, const uint16_t *d_uni
                                  int64_t *needed) {
     if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
     return text_run(E, kind, d_units, d_off, n_texts, d_vals_out, vals_cap, d_out_off, true, needed);
+}
+
+int bpe_encoder_utf8_to_utf16(bpe_encoder *E, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                              uint16_t *units_out, int64_t units_cap, int64_t *out_off) {
+    if (!E || units_cap < 0 || !out_off || (units_cap && !units_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad utf8_to_utf16 arguments");
+    ENC_TRY(hipSetDevice(E->device));
+    E->u8.st.calls++;
+    Utf8Call J;
+    J.bytes = bytes, J.off = off, J.n_texts = n_texts, J.dev = false, J.cap = units_cap;
+    int rc = u8_transcode(E->u8, E->stream, J);
+    if (rc) return rc;
+    ENC_TRY(hipMemcpyAsync(out_off, J.d_uoff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToHost, E->stream));
+    if (J.fits && J.units)
+        ENC_TRY(hipMemcpyAsync(units_out, J.d_units, (size_t)J.units * 2, hipMemcpyDeviceToHost, E->stream));
+    ENC_TRY(hipStreamSynchronize(E->stream));
+    if (!J.fits) return u8_cap_error(J);
+    u8_commit(E->u8, J);
+    return BPE_OK;
+}
+
+int bpe_encoder_utf8_to_utf16_device(bpe_encoder *E, const uint8_t *d_bytes, const int64_t *d_off, int64_t n_texts,
+                                     uint16_t *d_units_out, int64_t units_cap, int64_t *d_out_off, int64_t *needed) {
+    if (!E || !needed || units_cap < 0 || !d_out_off || (units_cap && !d_units_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad utf8_to_utf16 arguments");
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->u8.st.calls++;
+    Utf8Call J;
+    J.bytes = d_bytes, J.off = d_off, J.n_texts = n_texts, J.dev = true, J.cap = units_cap;
+    J.d_units = units_cap ? d_units_out : nullptr, J.d_uoff = d_out_off;
+    int rc = u8_transcode(E->u8, E->stream, J);
+    if (rc) return rc;
+    *needed = J.units;
+    if (!J.fits) return u8_cap_error(J);
+    u8_commit(E->u8, J);
+    return BPE_OK;
+}
+
+namespace {
+
+// transcode, then the UTF-16 device form on the units; the host form's values and offsets come
+// back from scratch
+int utf8_encode(bpe_encoder *E, int kind, const uint8_t *bytes, const int64_t *off, int64_t n_texts, int32_t *vals_out,
+                int64_t cap, int64_t *out_off, bool dev, int64_t *needed) {
+    *needed = 0;
+    // (the UTF-16 form's own checks, made before any work here as they are made there)
+    if (kind != BPE_ENCODE_IDS && kind != BPE_ENCODE_VECTORS) return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode kind");
+    if (n_texts < 0 || n_texts >= 0x7FFFFFFF || cap < 0 || !out_off || (n_texts && !off) || (cap && !vals_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_text_batch arguments");
+    if (kind == BPE_ENCODE_VECTORS && !E->txt.has_tvi)
+        return bpe_fail(BPE_ERR_STATE, "bpe native: encode to vectors without a vector index "
+                                       "(bpe_encoder_set_vector_index)");
+    ENC_TRY(hipSetDevice(E->device));
+    E->u8.st.calls++;
+    Utf8Call J;
+    J.bytes = bytes, J.off = off, J.n_texts = n_texts, J.dev = dev;
+    // the host form's values go through scratch: at most min(cap, bytes) of them (a text never grows)
+    if (!dev) J.vals_cap = cap;
+    int rc = u8_transcode(E->u8, E->stream, J);
+    if (rc) return rc;
+    if (dev) {
+        rc = text_run(E, kind, J.d_units, J.d_uoff, n_texts, vals_out, cap, out_off, true, needed);
+    } else {
+        rc = text_run(E, kind, J.d_units, J.d_uoff, n_texts, J.d_vals, J.s_cap, J.d_ooff, true, needed);
+        if (rc) return rc;
+        ENC_TRY(hipMemcpyAsync(out_off, J.d_ooff, (size_t)(n_texts + 1) * 8, hipMemcpyDeviceToHost, E->stream));
+        if (*needed) ENC_TRY(hipMemcpyAsync(vals_out, J.d_vals, (size_t)*needed * 4, hipMemcpyDeviceToHost, E->stream));
+        ENC_TRY(hipStreamSynchronize(E->stream));
+    }
+    if (rc) return rc;
+    u8_commit(E->u8, J);
+    return BPE_OK;
+}
+
+}  // namespace
+
+int bpe_encode_utf8_batch(bpe_encoder *E, int kind, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                          int32_t *vals_out, int64_t vals_cap, int64_t *out_off) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int64_t needed = 0;
+    return utf8_encode(E, kind, bytes, off, n_texts, vals_out, vals_cap, out_off, false, &needed);
+}
+
+int bpe_encode_utf8_batch_device(bpe_encoder *E, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                 int64_t n_texts, int32_t *d_vals_out, int64_t vals_cap, int64_t *d_out_off,
+                                 int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    return utf8_encode(E, kind, d_bytes, d_off, n_texts, d_vals_out, vals_cap, d_out_off, true, needed);
+}
+
+int bpe_encoder_get_utf8_stats(bpe_encoder *E, bpe_utf8_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->u8.st;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_utf8_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->u8.st = bpe_utf8_stats{};
+    return BPE_OK;
 }
 
 int bpe_encoder_get_text_stats(bpe_encoder *E, bpe_text_stats *out) {

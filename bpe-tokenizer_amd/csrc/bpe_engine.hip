@@ -15,6 +15,7 @@
 #include "bpe_append.hip.h"   // the corpus append from encoded samples (bpe_add_sample_batch, the restore)
 #include "bpe_export.hip.h"   // the corpus export (bpe_export_samples, bpe_export_text_batch)
 #include "bpe_multi.h"
+#include "bpe_utf8.hip.h"     // text as UTF-8: bytes -> units in front of the ingest (bpe_add_utf8_batch)
 #include "bpe_tools.h"
 
 namespace bpe_step {
@@ -245,6 +246,8 @@ struct bpe_ctx {
     struct AppendState *app = nullptr;
     // the corpus export: scratch and counters (made by its first call)
     struct ExportState *exp = nullptr;
+    // text as UTF-8: the transcode's scratch and counters (made by its first call)
+    Utf8State *u8 = nullptr;
 };
 
 void ingest_free(bpe_ctx *c);
@@ -2829,6 +2832,10 @@ int bpe_destroy(bpe_ctx *c) {
     ingest_free(c);
     append_free(c);
     export_free(c);
+    if (c->u8) {
+        u8_free(*c->u8);
+        delete c->u8;
+    }
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -4103,6 +4110,123 @@ int bpe_restore_text_batch_device(bpe_ctx *c, bpe_encoder *enc, const uint16_t *
         MULTI(restore_text_batch(c->multi, enc, d_units, d_off, n_texts, true));
     return restore_text(c, enc, d_units, d_off, n_texts, true);
 }
+
+}  // extern "C"
+
+// ---- text as UTF-8 (include/bpe.h): the transcode of bpe_utf8.hip.h, then the UTF-16 device forms ----
+
+namespace {
+
+// the units of a transcode on the host (a multi-device context takes its UTF-16 host forms)
+int utf8_units_to_host(hipStream_t s, const uint16_t *d_units, const int64_t *d_uoff, int64_t n, int64_t n_units,
+                       std::vector<uint16_t> &units, std::vector<int64_t> &uoff) {
+    units.resize((size_t)std::max<int64_t>(n_units, 1));
+    uoff.resize((size_t)n + 1);
+    if (n_units) HIP_TRY(hipMemcpyAsync(units.data(), d_units, (size_t)n_units * 2, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(uoff.data(), d_uoff, uoff.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return BPE_OK;
+}
+
+int add_utf8(bpe_ctx *c, const uint8_t *bytes, const int64_t *off, int64_t n_texts, bool dev, uint32_t *new_chars,
+             int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    // (the UTF-16 form's own argument check, made before any work here as it is made there)
+    if (!c || !n_new || n_texts < 0 || n_texts >= 0x7FFFFFFF || new_cap < 0 || hist_cap < 0 || (n_texts && !off) ||
+        (new_cap && !new_chars) || (hist_cap && !id_hist))
+        return fail(BPE_ERR_ARG, "bpe native: bad add_text_batch arguments");
+    *n_new = 0;
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;   // the context that transcodes
+    int rc = set_device(t);
+    if (rc) return rc;
+    if (!t->u8) t->u8 = new Utf8State();
+    t->u8->st.calls++;
+    Utf8Call J;
+    J.bytes = bytes, J.off = off, J.n_texts = n_texts, J.dev = dev;
+    if ((rc = u8_transcode(*t->u8, t->stream, J))) return rc;
+    if (c->multi) {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> uoff;
+        if ((rc = utf8_units_to_host(t->stream, J.d_units, J.d_uoff, n_texts, J.units, units, uoff))) return rc;
+        rc = multi_add_text_batch(c->multi, units.data(), uoff.data(), n_texts, false, new_chars, new_cap, n_new,
+                                  id_hist, hist_cap);
+    } else {
+        rc = ingest_text(c, J.d_units, J.d_uoff, n_texts, true, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+    }
+    if (rc) return rc;
+    u8_commit(*t->u8, J);
+    return BPE_OK;
+}
+
+int restore_utf8(bpe_ctx *c, bpe_encoder *E, const uint8_t *bytes, const int64_t *off, int64_t n, bool dev) {
+    // (the UTF-16 form's own checks, made before any work here as they are made there)
+    if (!c || n < 0 || n >= 0x7FFFFFFF || (n && !off))
+        return fail(BPE_ERR_ARG, "bpe native: bad restore_text_batch arguments");
+    if (!E) return fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int enc_device = -1;
+    int rc = encoder_device(E, &enc_device);
+    if (rc) return rc;
+    if (!c->multi && enc_device != c->device)
+        return fail(BPE_ERR_ARG, "bpe native: the encoder is on another device than the context");
+    const uint16_t *d_units = nullptr;
+    const int64_t *d_uoff = nullptr;
+    int64_t n_units = 0;
+    if ((rc = encoder_utf8_units(E, bytes, off, n, dev, &d_units, &d_uoff, &n_units))) return rc;
+    if (c->multi) {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> uoff;
+        HIP_TRY(hipSetDevice(enc_device));
+        // (the encoder's transcode has synchronised its stream: a plain copy follows it)
+        if ((rc = utf8_units_to_host(nullptr, d_units, d_uoff, n, n_units, units, uoff))) return rc;
+        rc = multi_restore_text_batch(c->multi, E, units.data(), uoff.data(), n, false);
+    } else {
+        rc = restore_text(c, E, d_units, d_uoff, n, true);
+    }
+    if (rc) return rc;
+    encoder_utf8_done(E);
+    return BPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpe_add_utf8_batch(bpe_ctx *c, const uint8_t *bytes, const int64_t *off, int64_t n_texts, uint32_t *new_chars,
+                       int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    return add_utf8(c, bytes, off, n_texts, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_add_utf8_batch_device(bpe_ctx *c, const uint8_t *d_bytes, const int64_t *d_off, int64_t n_texts,
+                              uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                              int64_t hist_cap) {
+    return add_utf8(c, d_bytes, d_off, n_texts, true, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_restore_utf8_batch(bpe_ctx *c, bpe_encoder *enc, const uint8_t *bytes, const int64_t *off, int64_t n_texts) {
+    return restore_utf8(c, enc, bytes, off, n_texts, false);
+}
+
+int bpe_restore_utf8_batch_device(bpe_ctx *c, bpe_encoder *enc, const uint8_t *d_bytes, const int64_t *d_off,
+                                  int64_t n_texts) {
+    return restore_utf8(c, enc, d_bytes, d_off, n_texts, true);
+}
+
+int bpe_get_utf8_stats(bpe_ctx *c, bpe_utf8_stats *out) {
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    const bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    *out = t->u8 ? t->u8->st : bpe_utf8_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_utf8_stats(bpe_ctx *c) {
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    if (t->u8) t->u8->st = bpe_utf8_stats{};
+    return BPE_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int bpe_token_counts(bpe_ctx *c, int64_t *counts, int64_t cap) {
     if (counts && cap >= 0) MULTI(token_counts(c->multi, counts, cap));

@@ -446,6 +446,8 @@ int multi_shard_count(bpe_multi *m, int *n) {
     return BPE_OK;
 }
 
+bpe_ctx *multi_first_shard(bpe_multi *m) { return m->sh[0]; }
+
 int multi_set_mode(bpe_multi *m, int mode, bool explicit_choice) {
     for (auto s : m->sh) MTRY(bpe_set_mode(s, mode));
     if (explicit_choice) m->mode_explicit = true;

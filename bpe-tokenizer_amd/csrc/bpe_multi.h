@@ -53,6 +53,8 @@ int multi_get_stats(bpe_multi *m, bpe_stats *out);
 int multi_reset_stats(bpe_multi *m);
 int multi_get_stream(bpe_multi *m, void **stream);
 int multi_shard_count(bpe_multi *m, int *n);
+// the shard whose device and stream a multi-device context's UTF-8 ingest transcodes on
+bpe_ctx *multi_first_shard(bpe_multi *m);
 // explicit_choice: the caller's bpe_set_mode (false: the automatic switch past AUTO_PIX_VOCAB ids)
 int multi_set_mode(bpe_multi *m, int mode, bool explicit_choice = true);
 
@@ -80,6 +82,12 @@ int ingest_kernel_ms(bpe_ctx *c, double *ms, bool reset);
 // (bpe_encode.hip) the device an encoder lives on (the restore checks it against the context's; the
 // encoder's struct stays private)
 int encoder_device(bpe_encoder *enc, int *device);
+// (bpe_encode.hip) the restore from UTF-8: the texts transcoded on the encoder, their units and
+// offsets left in its scratch on its device; encoder_utf8_done counts that transcode in the
+// encoder's bpe_utf8_stats once the restore has succeeded
+int encoder_utf8_units(bpe_encoder *enc, const uint8_t *bytes, const int64_t *off, int64_t n_texts, bool dev,
+                       const uint16_t **d_units, const int64_t **d_uoff, int64_t *n_units);
+void encoder_utf8_done(bpe_encoder *enc);
 // (bpe_decode.hip) the same for a decoder (the text export checks it)
 int decoder_device(bpe_decoder *dec, int *device);
 

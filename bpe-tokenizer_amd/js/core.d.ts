@@ -78,6 +78,16 @@ export declare class BPETokenizer {
    */
   restoreToCorpusBatch(contents: string[]): void
   /**
+   * the three batch methods for UTF-8 bytes (files, datasets), decoded on the GPU exactly as
+   * `buffer.toString()` decodes them: ill-formed bytes become U+FFFD, a char like any other.  Each
+   * leaves the tokenizer as the method above does on `buffers.map(b => b.toString())`: weights,
+   * char_to_token, token_table order and error strings.  addToCorpusBatchUtf8 needs a HIP device;
+   * the other two run that map in JS without one.
+   */
+  addToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>): void
+  restoreToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>): void
+  encodeToVectorBatchUtf8(buffers: Array<Buffer | Uint8Array>): number[][]
+  /**
    * the trained corpus as vectors on the GPU: `encodeToVector` of every training sample (of the samples
    * `indices`, in that order, when given) without encoding the raw text again; throws
    * `unknown token index: N`.  Without the addon (or with BPE_ENCODE_DEVICE=0) the map runs in JS.

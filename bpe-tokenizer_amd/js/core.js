@@ -33,6 +33,8 @@ const {
   corpusCodesOnDevice,
   corpusVectorsOnDevice,
   corpusTextsOnDevice,
+  loadNativeUtf8,
+  buffersToBytes,
 } = require('./native')
 
 /** @description file separator (core.ts:36) */
@@ -338,7 +340,25 @@ class BPETokenizer {
     let engine = this.engine()
     syncEngineChars(this, engine)
     let [units, off] = textsToUnits(contents)
-    let [new_chars, hist] = loadNativeIngest().addTextBatch(engine, units, off)
+    this._addedOnDevice(loadNativeIngest().addTextBatch(engine, units, off))
+  }
+
+  /**
+   * @description addToCorpusBatch for UTF-8 bytes: an array of Buffer / Uint8Array, decoded on the
+   * device exactly as `buffer.toString()` decodes them (ill-formed bytes become U+FFFD, which is then
+   * a char like any other; bpe_add_utf8_batch).  Leaves the tokenizer exactly as
+   * `this.addToCorpusBatch(buffers.map(b => b.toString()))` does.  Needs a HIP device.
+   */
+  addToCorpusBatchUtf8(buffers) {
+    if (buffers.length === 0) return
+    let engine = this.engine()
+    syncEngineChars(this, engine)
+    let [bytes, off] = buffersToBytes(buffers)
+    this._addedOnDevice(loadNativeUtf8().addUtf8Batch(engine, bytes, off))
+  }
+
+  /** the bookkeeping of core.ts:186-202 for a batch the engine ingested: [new_chars, hist] */
+  _addedOnDevice([new_chars, hist]) {
     let { char_to_token, code_to_token, token_table } = this
     let first = token_table.length
     for (let index = 0; index < first; index++) {
@@ -392,6 +412,19 @@ class BPETokenizer {
       if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, contents)) return
     }
     for (let content of contents) this.restoreToCorpus(content)
+  }
+
+  /**
+   * @description restoreToCorpusBatch for UTF-8 bytes: an array of Buffer / Uint8Array, decoded on
+   * the device as `buffer.toString()` decodes them (bpe_restore_utf8_batch).  Leaves the tokenizer
+   * exactly as `this.restoreToCorpusBatch(buffers.map(b => b.toString()))` does, the errors included;
+   * when the device cannot take the call, that is what runs.
+   */
+  restoreToCorpusBatchUtf8(buffers) {
+    if (buffers.length === 0) return
+    let engine = this.engine()
+    if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, buffers, true)) return
+    this.restoreToCorpusBatch(buffers.map(b => Buffer.from(b.buffer, b.byteOffset, b.length).toString()))
   }
 
   /**
@@ -596,6 +629,20 @@ class BPETokenizer {
       if (out) return out
     }
     return texts.map(t => this.encodeToVector(t))
+  }
+
+  /**
+   * @description encodeToVectorBatch for UTF-8 bytes: an array of Buffer / Uint8Array, decoded on the
+   * device as `buffer.toString()` decodes them (bpe_encode_utf8_batch).  Equals
+   * `this.encodeToVectorBatch(buffers.map(b => b.toString()))`, the errors included; when the device
+   * cannot take the call, that is what runs.
+   */
+  encodeToVectorBatchUtf8(buffers) {
+    if (buffers.length === 0) return []
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let out = encodeTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, buffers, true)
+    if (out) return out
+    return this.encodeToVectorBatch(buffers.map(b => Buffer.from(b.buffer, b.byteOffset, b.length).toString()))
   }
 
   /** core.ts:447-453 */

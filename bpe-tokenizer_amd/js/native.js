@@ -32,6 +32,14 @@ function loadNativeRestore() {
   return nativeRestore
 }
 
+// the UTF-8 addon (addon/bpe_utf8_napi.node: addUtf8Batch, restoreUtf8Batch on an engine handle,
+// encodeUtf8Batch on a text encoder handle)
+let nativeUtf8 = null
+function loadNativeUtf8() {
+  if (!nativeUtf8) nativeUtf8 = require(path.join(__dirname, '..', 'addon', 'bpe_utf8_napi.node'))
+  return nativeUtf8
+}
+
 // the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
 // the export's addon (addon/bpe_export_napi.node: exportSamples, exportText on an engine handle)
 let nativeExport = null
@@ -297,6 +305,15 @@ function textsToUnits(texts) {
   return [new Uint16Array(buf.buffer, buf.byteOffset, buf.length >> 1), off]
 }
 
+/** buffers (Buffer / Uint8Array, UTF-8) as one Uint8Array of bytes and a Float64Array of offsets */
+function buffersToBytes(buffers) {
+  let off = new Float64Array(buffers.length + 1)
+  for (let k = 0; k < buffers.length; k++) off[k + 1] = off[k] + buffers[k].length
+  let bytes = new Uint8Array(off[buffers.length])
+  for (let k = 0; k < buffers.length; k++) bytes.set(buffers[k], off[k])
+  return [bytes, off]
+}
+
 /**
  * A batch of texts through the owner's device text encoder -> array of vectors, or null when the
  * device cannot take the call (the caller then maps encodeToVector in JS): BPE_ENCODE_DEVICE=0, no
@@ -304,9 +321,10 @@ function textsToUnits(texts) {
  * hold (>= BPE_MAX_VOCAB: remembered while the owner keeps that merge list and char table).  With
  * BPE_ENCODE_DEVICE=1 the device's errors go through.  The reference's own errors (an unknown char,
  * an unknown token index) are thrown with its strings either way.
+ * utf8: `texts` are Buffers / Uint8Arrays of UTF-8 bytes, decoded on the device (bpe_encode_utf8_batch).
  */
 const CAPABILITY_TEXT_TABLE = /merge token id out of range|more merges than token ids|char token id out of range/
-function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
+function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts, utf8) {
   if (ENCODE_DEVICE === '0') return null
   if (
     ENCODE_DEVICE !== '1' &&
@@ -316,8 +334,13 @@ function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
   let res
   try {
     let enc = syncTextEncoder(owner, list, tripleOf)
-    let [units, off] = textsToUnits(texts)
-    res = loadNativeText().encodeTextBatch(enc, units, off, 1)
+    if (utf8) {
+      let [bytes, off] = buffersToBytes(texts)
+      res = loadNativeUtf8().encodeUtf8Batch(enc, bytes, off, 1)
+    } else {
+      let [units, off] = textsToUnits(texts)
+      res = loadNativeText().encodeTextBatch(enc, units, off, 1)
+    }
   } catch (e) {
     let msg = String((e && e.message) || e)
     let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
@@ -355,8 +378,9 @@ function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts) {
  * device does not hold; with BPE_ENCODE_DEVICE=1 the device's errors go through.  The reference's
  * `unknown token, char: "x"` is thrown with its string either way; the batch is atomic, so no text has
  * been added then (the reference's loop would have added the texts before the failing one).
+ * utf8: `texts` are Buffers / Uint8Arrays of UTF-8 bytes, decoded on the device (bpe_restore_utf8_batch).
  */
-function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts) {
+function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts, utf8) {
   if (ENCODE_DEVICE === '0') return false
   if (
     ENCODE_DEVICE !== '1' &&
@@ -365,8 +389,13 @@ function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts) {
     return false
   try {
     let enc = syncTextEncoder(owner, list, tripleOf)
-    let [units, off] = textsToUnits(texts)
-    loadNativeRestore().restoreTextBatch(engine, enc, units, off)
+    if (utf8) {
+      let [bytes, off] = buffersToBytes(texts)
+      loadNativeUtf8().restoreUtf8Batch(engine, enc, bytes, off)
+    } else {
+      let [units, off] = textsToUnits(texts)
+      loadNativeRestore().restoreTextBatch(engine, enc, units, off)
+    }
   } catch (e) {
     let msg = String((e && e.message) || e)
     let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
@@ -530,6 +559,8 @@ module.exports = {
   loadNativeText,
   loadNativeIngest,
   loadNativeRestore,
+  loadNativeUtf8,
+  buffersToBytes,
   maxLengthArg,
   minWeightArg,
   encodeOnDevice,

@@ -756,6 +756,80 @@ int bpe_export_text_batch_device(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *
 int bpe_get_export_stats(bpe_ctx *ctx, bpe_export_stats *out);
 int bpe_reset_export_stats(bpe_ctx *ctx);
 
+/* ---- text as UTF-8 -------------------------------------------------------------------------------
+ * The three text pipelines above from UTF-8 bytes (files, datasets, byte tensors) instead of UTF-16
+ * units: the bytes are transcoded to units on the device and the UTF-16 `_device` form takes them
+ * there, so a host form ships 1 B per byte and no char is touched on the host.
+ *
+ * Text k is bytes[off[k] .. off[k+1]) and decodes on its own, exactly as Node's
+ * Buffer.prototype.toString() and WHATWG TextDecoder('utf-8', {ignoreBOM: true}) decode it (what
+ * fileContentToCorpus does to a Buffer, core.ts:55-58; CPython's bytes.decode('utf-8', 'replace')
+ * gives the same): every maximal ill-formed subpart becomes one U+FFFD, a sequence cut by the end
+ * of its text is ill-formed, a BOM stays U+FEFF, a 4-byte sequence becomes a surrogate pair.
+ * Ill-formed input is not an error: U+FFFD is then a char like any other (new to the ingest; to the
+ * encoder unknown unless its table has it).
+ *
+ * bpe_encoder_utf8_to_utf16 is the transcode alone, on the encoder's device and stream and in its
+ * own grow-only scratch.  Offsets follow bpe_encode_text_batch's rules (off[0] need not be 0 and
+ * bytes before it are never read; decreasing or negative offsets give BPE_ERR_ARG; n_texts == 0 is
+ * fine), capacity follows bpe_decode_batch's: out_off receives n_texts + 1 offsets with
+ * out_off[0] = 0; when out_off[n_texts] exceeds units_cap the offsets are written, no unit is, and
+ * BPE_ERR_ARG comes back (units_out == NULL with units_cap 0 is the sizing call).  units_cap >=
+ * off[n_texts] - off[0] always suffices.  The `_device` form takes and fills buffers on the
+ * encoder's device (any byte pointer, any 2-byte aligned unit pointer), reads the offsets back
+ * (8 B per text) and synchronises before returning; *needed (a host int64) receives the units.
+ *
+ * bpe_encode_utf8_batch, bpe_add_utf8_batch and bpe_restore_utf8_batch are that transcode (on the
+ * encoder for the encode and the restore, on the context for the ingest) followed by
+ * bpe_encode_text_batch_device, bpe_add_text_batch_device and bpe_restore_text_batch_device on the
+ * units and their offsets: outputs, error codes, messages, atomicity and the long-text routes are
+ * those of the UTF-16 form given the decoded texts, and error places stay (text K, unit I) with I a
+ * unit of the decoded text.  The host forms copy the bytes in and only the existing outputs out;
+ * the `_device` forms change their arguments as the UTF-16 `_device` forms do.
+ * A multi-device context transcodes on its first shard's device, brings the units to the host and
+ * takes its UTF-16 host form (the restore: on the encoder's device); its device forms do the same
+ * from device buffers.
+ *
+ * bpe_utf8_stats counts the calls and, for those whose whole pipeline succeeded, their texts,
+ * bytes, units and `replaced`: the U+FFFD made from ill-formed input (a U+FFFD spelled EF BF BD is
+ * not counted), which is how a caller learns that a file was not clean.  The encoder's counters
+ * take the transcode, the encode and the restore, the context's the ingest (a multi-device
+ * context's: its first shard's).
+ * The kernels work on tiles of BPE_UTF8_TILE bytes and scan BPE_TEXT_SCAN_ROUND tile counts per
+ * round (csrc/bpe_utf8.hip.h; exported for the tests). */
+#define BPE_UTF8_TILE 4096
+typedef struct {
+    int64_t calls;            /* UTF-8 calls */
+    int64_t texts;            /* texts of the calls that succeeded */
+    int64_t bytes;            /* ... their bytes */
+    int64_t units;            /* ... the UTF-16 units they decoded to */
+    int64_t replaced;         /* ... the U+FFFD among them made from ill-formed input */
+    double kernel_ms;         /* HIP-event time of the transcode kernels */
+} bpe_utf8_stats;
+int bpe_encoder_utf8_to_utf16(bpe_encoder *enc, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                              uint16_t *units_out, int64_t units_cap, int64_t *out_off);
+int bpe_encoder_utf8_to_utf16_device(bpe_encoder *enc, const uint8_t *d_bytes, const int64_t *d_off,
+                                     int64_t n_texts, uint16_t *d_units_out, int64_t units_cap,
+                                     int64_t *d_out_off, int64_t *needed);
+int bpe_encode_utf8_batch(bpe_encoder *enc, int kind, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                          int32_t *vals_out, int64_t vals_cap, int64_t *out_off);
+int bpe_encode_utf8_batch_device(bpe_encoder *enc, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                 int64_t n_texts, int32_t *d_vals_out, int64_t vals_cap, int64_t *d_out_off,
+                                 int64_t *needed);
+int bpe_add_utf8_batch(bpe_ctx *ctx, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                       uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap);
+int bpe_add_utf8_batch_device(bpe_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_off, int64_t n_texts,
+                              uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                              int64_t hist_cap);
+int bpe_restore_utf8_batch(bpe_ctx *ctx, bpe_encoder *enc, const uint8_t *bytes, const int64_t *off,
+                           int64_t n_texts);
+int bpe_restore_utf8_batch_device(bpe_ctx *ctx, bpe_encoder *enc, const uint8_t *d_bytes, const int64_t *d_off,
+                                  int64_t n_texts);
+int bpe_encoder_get_utf8_stats(bpe_encoder *enc, bpe_utf8_stats *out);
+int bpe_encoder_reset_utf8_stats(bpe_encoder *enc);
+int bpe_get_utf8_stats(bpe_ctx *ctx, bpe_utf8_stats *out);
+int bpe_reset_utf8_stats(bpe_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
