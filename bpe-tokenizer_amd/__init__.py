@@ -57,6 +57,9 @@ C_API = [
     'bpe_encode_utf8_batch_device', 'bpe_add_utf8_batch', 'bpe_add_utf8_batch_device', 'bpe_restore_utf8_batch',
     'bpe_restore_utf8_batch_device', 'bpe_encoder_get_utf8_stats', 'bpe_encoder_reset_utf8_stats',
     'bpe_get_utf8_stats', 'bpe_reset_utf8_stats',
+    'bpe_decoder_utf16_to_utf8', 'bpe_decoder_utf16_to_utf8_device', 'bpe_decode_utf8_batch',
+    'bpe_decode_utf8_batch_device', 'bpe_export_utf8_batch', 'bpe_export_utf8_batch_device',
+    'bpe_decoder_get_utf8_stats', 'bpe_decoder_reset_utf8_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -93,6 +96,7 @@ EXPORT_IDS = 0      # BPE_EXPORT_IDS: samples out as token ids
 EXPORT_VECTORS = 1  # BPE_EXPORT_VECTORS: ... as vector indices (encodeToVector of every sample)
 EXPORT_CODE = 2     # BPE_EXPORT_CODE: ... as uint16 code units id + 1 (corpus_in_code)
 UTF8_TILE = 4096    # BPE_UTF8_TILE: bytes per workgroup of the UTF-8 transcode (its scan round: TEXT_SCAN_ROUND)
+UTF16_TILE = 2048   # BPE_UTF16_TILE: units per workgroup of the transcode to UTF-8 (the same scan round)
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -362,6 +366,18 @@ def lib():
         'bpe_encoder_reset_utf8_stats': ([vp], ctypes.c_int),
         'bpe_get_utf8_stats': ([vp, ctypes.POINTER(Utf8Stats)], ctypes.c_int),
         'bpe_reset_utf8_stats': ([vp], ctypes.c_int),
+        'bpe_decoder_utf16_to_utf8': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_decoder_utf16_to_utf8_device': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p],
+                                             ctypes.c_int),
+        'bpe_decode_utf8_batch': ([vp, ctypes.c_int, i32p, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p],
+                                  ctypes.c_int),
+        'bpe_decode_utf8_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                          i64p], ctypes.c_int),
+        'bpe_export_utf8_batch': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_export_utf8_batch_device': ([vp, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, vp, i64p],
+                                         ctypes.c_int),
+        'bpe_decoder_get_utf8_stats': ([vp, ctypes.POINTER(Utf8Stats)], ctypes.c_int),
+        'bpe_decoder_reset_utf8_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -800,6 +816,50 @@ class Engine:
         _check(lib().bpe_export_text_batch_device(self._ctx, d, idx_p, n, units.data_ptr(), units.numel(),
                                                   off.data_ptr(), ctypes.byref(need)), 'bpe_export_text_batch_device')
         return units, off
+
+    def export_utf8_flat(self, dec, idx=None):
+        """Samples out as UTF-8 through `dec` (bpe_export_utf8_batch): (bytes uint8, offsets int64),
+        encoded as Node's Buffer.from(text) encodes them.  The sizing call, then the real one."""
+        _, idx_a, idx_p, n, _, _, _ = self._export_args(idx, 'ids', None)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        d = dec._dec if dec is not None else None
+        off = np.zeros(n + 1, np.int64)
+        rc = lib().bpe_export_utf8_batch(self._ctx, d, idx_p, n, None, 0, off.ctypes.data_as(i64p))
+        if rc == BPE_OK:
+            return np.zeros(0, np.uint8), off
+        if rc != ERR_ARG or off[n] <= 0:
+            _check(rc, 'bpe_export_utf8_batch')
+        out = np.empty(int(off[n]), np.uint8)
+        _check(lib().bpe_export_utf8_batch(self._ctx, d, idx_p, n, out.ctypes.data, out.size,
+                                           off.ctypes.data_as(i64p)), 'bpe_export_utf8_batch')
+        return out, off
+
+    def export_utf8(self, dec, idx=None):
+        """The samples' texts as a list of bytes."""
+        out, oo = self.export_utf8_flat(dec, idx)
+        raw = out.tobytes()
+        return [raw[oo[k]:oo[k + 1]] for k in range(len(oo) - 1)]
+
+    def export_utf8_tensors(self, dec, idx=None):
+        """Device form (bpe_export_utf8_batch_device): (uint8 tensor of the bytes, int64 offsets
+        tensor) on the context's device; no id, unit or byte touches the host."""
+        import torch
+        _, idx_a, idx_p, n, _, _, _ = self._export_args(idx, 'ids', None)
+        dev = torch.device('cuda', self.device)
+        d = dec._dec if dec is not None else None
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        need = ctypes.c_int64()
+        torch.cuda.synchronize(dev)
+        rc = lib().bpe_export_utf8_batch_device(self._ctx, d, idx_p, n, None, 0, off.data_ptr(), ctypes.byref(need))
+        if rc == BPE_OK:
+            return torch.zeros(0, dtype=torch.uint8, device=dev), off
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, 'bpe_export_utf8_batch_device')
+        out = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().bpe_export_utf8_batch_device(self._ctx, d, idx_p, n, out.data_ptr(), out.numel(),
+                                                  off.data_ptr(), ctypes.byref(need)), 'bpe_export_utf8_batch_device')
+        return out, off
 
     def export_stats(self):
         s = ExportStats()
@@ -1454,6 +1514,128 @@ class Decoder:
                                              units.numel(), out_off.data_ptr(), ctypes.byref(need)),
                'bpe_decode_batch_device')
         return units, out_off
+
+    # ---- text out as UTF-8 (include/bpe.h "text out as UTF-8", csrc/bpe_utf8_out.hip.h) ----
+
+    def _sized_host(self, what, call, n):
+        """The sizing call, then the real one: call(out_ptr, cap, out_off_ptr) -> rc."""
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        rc = call(None, 0, out_off.ctypes.data_as(i64p))
+        if rc == BPE_OK:   # (nothing to write)
+            return np.zeros(0, np.uint8), out_off
+        if rc != ERR_ARG or out_off[-1] <= 0:
+            _check(rc, what)
+        out = np.empty(int(out_off[-1]), dtype=np.uint8)
+        _check(call(out.ctypes.data, out.size, out_off.ctypes.data_as(i64p)), what)
+        return out, out_off
+
+    def _sized_device(self, what, call, n, device):
+        """... on the device: call(out_ptr, cap, out_off_ptr, needed_ref) -> rc."""
+        import torch
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=device)
+        need = ctypes.c_int64()
+        torch.cuda.synchronize(device)   # (the decoder runs on a stream of its own)
+        rc = call(None, 0, out_off.data_ptr(), ctypes.byref(need))
+        if rc == BPE_OK:
+            return torch.zeros(0, dtype=torch.uint8, device=device), out_off
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, what)
+        out = torch.empty(need.value, dtype=torch.uint8, device=device)
+        torch.cuda.synchronize(device)
+        _check(call(out.data_ptr(), out.numel(), out_off.data_ptr(), ctypes.byref(need)), what)
+        return out, out_off
+
+    def utf16_to_utf8(self, texts_or_units, off=None):
+        """The transcode alone (bpe_decoder_utf16_to_utf8): a list of str or unit arrays (off None),
+        or the flat form (uint16 units, int64 offsets) -> (bytes uint8, out_off int64), each text
+        encoded as Node's Buffer.from(text) encodes it (lone surrogates: EF BF BD)."""
+        if off is None:
+            parts = [_units(t) for t in texts_or_units]
+            off = np.zeros(len(parts) + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in parts], out=off[1:])
+            units = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint16) if off[-1] else np.zeros(1, np.uint16)
+        else:
+            units = np.ascontiguousarray(texts_or_units, dtype=np.uint16).ravel()
+            off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        src = units if units.size else np.zeros(1, np.uint16)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+
+        def call(out, cap, oo):
+            return lib().bpe_decoder_utf16_to_utf8(self._dec, src.ctypes.data, off.ctypes.data_as(i64p), n, out, cap, oo)
+        return self._sized_host('bpe_decoder_utf16_to_utf8', call, n)
+
+    def utf16_to_utf8_tensors(self, units, off):
+        """Device form (bpe_decoder_utf16_to_utf8_device): units a torch int16 (or uint16) tensor, a
+        view at any unit offset is fine, and off a torch int64 tensor on the decoder's device ->
+        (uint8 tensor of the bytes, int64 offsets tensor) on that device."""
+        import torch
+        if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+            raise BpeError('utf16_to_utf8_tensors takes int16 units and int64 offsets', ERR_ARG)
+        if not (units.is_cuda and off.is_cuda and units.device.index == self.device
+                and off.device.index == self.device):
+            raise BpeError('utf16_to_utf8_tensors takes tensors on the decoder\'s device', ERR_ARG)
+        units, off = units.contiguous(), off.contiguous()
+        n = off.numel() - 1
+        up = units.data_ptr() if units.numel() else None
+
+        def call(out, cap, oo, need):
+            return lib().bpe_decoder_utf16_to_utf8_device(self._dec, up, off.data_ptr(), n, out, cap, oo, need)
+        return self._sized_device('bpe_decoder_utf16_to_utf8_device', call, n, units.device)
+
+    def decode_utf8_flat(self, vals, off, kind='vectors'):
+        """Flat form (bpe_decode_utf8_batch): texts vals[off[k]:off[k+1]] -> (bytes uint8, out_off
+        int64).  The sizing call, then the real one."""
+        kind = self._KINDS[kind]
+        vals = _i32(vals).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        src = vals if vals.size else np.zeros(1, np.int32)
+        i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+
+        def call(out, cap, oo):
+            return lib().bpe_decode_utf8_batch(self._dec, kind, src.ctypes.data_as(i32p), off.ctypes.data_as(i64p), n,
+                                               out, cap, oo)
+        return self._sized_host('bpe_decode_utf8_batch', call, n)
+
+    def decode_utf8(self, texts, kind='vectors'):
+        """texts: a list of vectors (or id sequences, kind='ids') -> list of bytes."""
+        lens = [len(t) for t in texts]
+        off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        vals = np.concatenate([np.asarray(t, dtype=np.int32) for t in texts]) if texts and off[-1] \
+            else np.zeros(0, np.int32)
+        out, oo = self.decode_utf8_flat(vals, off, kind)
+        raw = out.tobytes()
+        return [raw[oo[k]:oo[k + 1]] for k in range(len(texts))]
+
+    def decode_utf8_tensors(self, vals, off, kind='vectors'):
+        """Device form (bpe_decode_utf8_batch_device): vals a torch int32 tensor and off a torch int64
+        tensor on the decoder's device -> (uint8 tensor of the bytes, int64 offsets tensor), both on
+        that device."""
+        import torch
+        kind = self._KINDS[kind]
+        if vals.dtype != torch.int32 or off.dtype != torch.int64:
+            raise BpeError('decode_utf8_tensors takes int32 values and int64 offsets', ERR_ARG)
+        if not (vals.is_cuda and off.is_cuda and vals.device.index == self.device
+                and off.device.index == self.device):
+            raise BpeError('decode_utf8_tensors takes tensors on the decoder\'s device', ERR_ARG)
+        vals, off = vals.contiguous(), off.contiguous()
+        n = off.numel() - 1
+        vp = vals.data_ptr() if vals.numel() else None
+
+        def call(out, cap, oo, need):
+            return lib().bpe_decode_utf8_batch_device(self._dec, kind, vp, off.data_ptr(), n, out, cap, oo, need)
+        return self._sized_device('bpe_decode_utf8_batch_device', call, n, vals.device)
+
+    def utf8_stats(self):
+        s = Utf8Stats()
+        _check(lib().bpe_decoder_get_utf8_stats(self._dec, ctypes.byref(s)), 'bpe_decoder_get_utf8_stats')
+        return s.as_dict()
+
+    def reset_utf8_stats(self):
+        _check(lib().bpe_decoder_reset_utf8_stats(self._dec), 'bpe_decoder_reset_utf8_stats')
 
     def stats(self):
         s = DecoderStats()

@@ -41,6 +41,7 @@
 
 #include "bpe.h"
 #include "bpe_multi.h"   // bpe_fail
+#include "bpe_utf8_out.hip.h"   // text out as UTF-8: the transcode behind the decode (Utf8OutState)
 
 namespace {
 
@@ -349,6 +350,7 @@ struct bpe_decoder {
     char *d_buf = nullptr;                // staging of the host form
     size_t d_cap = 0;
     bpe_decoder_stats st{};
+    Utf8OutState o8;                      // text out as UTF-8 (bpe_utf8_out.hip.h)
 };
 
 namespace {
@@ -500,6 +502,67 @@ int decode_run(bpe_decoder *D, int kind, const int32_t *d_vals, const int64_t *d
 
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
+// ---- text out as UTF-8 (include/bpe.h; the kernels and the transcode: bpe_utf8_out.hip.h) ---------
+
+// The end of a transcode call: the capacity answer and the counters.  *needed: the bytes, once the
+// offsets are written.
+int utf8_out_result(bpe_decoder *D, const Utf8OutCall &J, int rc, int64_t *needed) {
+    if (rc) return rc;
+    *needed = J.bytes;
+    if (!J.fits) return u16_cap_error(J);
+    u16_commit(D->o8, J);
+    return BPE_OK;
+}
+
+// ... of a host form: the offsets and, when they fit, the bytes come back from the scratch.
+int utf8_out_to_host(bpe_decoder *D, const Utf8OutCall &J, int rc, uint8_t *bytes_out, int64_t *out_off) {
+    int64_t needed = -1;
+    rc = utf8_out_result(D, J, rc, &needed);
+    if (needed < 0) return rc;
+    DEC_TRY(hipMemcpyAsync(out_off, J.d_boff, (size_t)(J.n_texts + 1) * 8, hipMemcpyDeviceToHost, D->stream));
+    if (rc == BPE_OK && needed)
+        DEC_TRY(hipMemcpyAsync(bytes_out, J.d_bytes, (size_t)needed, hipMemcpyDeviceToHost, D->stream));
+    DEC_TRY(hipStreamSynchronize(D->stream));
+    return rc;   // (with the capacity message, when it did not fit)
+}
+
+// bpe_decode_batch_device into the decoder's scratch (a sizing pass, then the units), and the
+// transcode of those units.  J holds the byte outputs and their capacity.  The decoder's own errors
+// come back as they are, with J untouched and *transcoded false.
+// bpe_decoder_stats sees one decode per call: the sizing pass's counters are dropped when the units
+// pass follows (its kernel time stays); when nothing follows (a decoder error, or every text empty)
+// the first pass is the call.  They count the decode even when the bytes then miss their capacity:
+// what became of the bytes is in bpe_utf8_stats.
+int decode_utf8_run(bpe_decoder *D, int kind, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                    Utf8OutCall &J, bool *transcoded) {
+    Utf8OutState &U = D->o8;
+    *transcoded = false;
+    DEC_TRY(hipSetDevice(D->device));
+    const size_t b_off = align16((size_t)(n_texts + 1) * 8);
+    int rc;
+    if ((rc = u16_grow(D->stream, &U.d_dec, &U.d_dec_cap, b_off))) return rc;
+    const bpe_decoder_stats keep = D->st;
+    int64_t units = 0;
+    bool wrote = false;
+    rc = decode_run(D, kind, d_vals, d_off, n_texts, nullptr, 0, reinterpret_cast<int64_t *>(U.d_dec), &units, &wrote);
+    if (rc && !(rc == BPE_ERR_ARG && wrote && units > 0)) return rc;
+    if (units > 0) {
+        const double ms = D->st.kernel_ms;
+        D->st = keep;   // (one call, asked twice)
+        D->st.kernel_ms = ms;
+        if ((rc = u16_grow(D->stream, &U.d_dec, &U.d_dec_cap, b_off + (size_t)units * 2))) return rc;
+        rc = decode_run(D, kind, d_vals, d_off, n_texts, reinterpret_cast<uint16_t *>(U.d_dec + b_off), units,
+                        reinterpret_cast<int64_t *>(U.d_dec), &units, &wrote);
+        if (rc) return rc;
+    }
+    J.units = reinterpret_cast<const uint16_t *>(U.d_dec + b_off);
+    J.off = reinterpret_cast<const int64_t *>(U.d_dec);
+    J.n_texts = n_texts;
+    J.dev = true;
+    *transcoded = true;
+    return u16_transcode(U, D->stream, J);
+}
+
 }  // namespace
 
 int decoder_device(bpe_decoder *D, int *device) {
@@ -545,6 +608,7 @@ int bpe_decoder_destroy(bpe_decoder *D) {
     if (D->h_st) (void)hipHostFree(D->h_st);
     if (D->d_tiles) (void)hipFree(D->d_tiles);
     if (D->d_buf) (void)hipFree(D->d_buf);
+    u16_free(D->o8);
     if (D->ev0) (void)hipEventDestroy(D->ev0);
     if (D->ev1) (void)hipEventDestroy(D->ev1);
     if (D->stream) (void)hipStreamDestroy(D->stream);
@@ -698,6 +762,85 @@ int bpe_decoder_get_stats(bpe_decoder *D, bpe_decoder_stats *out) {
 int bpe_decoder_reset_stats(bpe_decoder *D) {
     if (!D) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
     D->st = bpe_decoder_stats{};
+    return BPE_OK;
+}
+
+int bpe_decoder_utf16_to_utf8_device(bpe_decoder *D, const uint16_t *d_units, const int64_t *d_off, int64_t n_texts,
+                                     uint8_t *d_bytes_out, int64_t bytes_cap, int64_t *d_out_off, int64_t *needed) {
+    if (!D || !needed || n_texts < 0 || bytes_cap < 0 || !d_out_off || (n_texts && !d_off) ||
+        (bytes_cap && !d_bytes_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad utf16_to_utf8 arguments");
+    DEC_TRY(hipSetDevice(D->device));
+    D->o8.st.calls++;
+    Utf8OutCall J;
+    J.units = d_units, J.off = d_off, J.n_texts = n_texts, J.dev = true;
+    J.d_bytes = d_bytes_out, J.d_boff = d_out_off, J.cap = bytes_cap;
+    return utf8_out_result(D, J, u16_transcode(D->o8, D->stream, J), needed);
+}
+
+int bpe_decoder_utf16_to_utf8(bpe_decoder *D, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                              uint8_t *bytes_out, int64_t bytes_cap, int64_t *out_off) {
+    if (!D || n_texts < 0 || bytes_cap < 0 || !out_off || (n_texts && !off) || (bytes_cap && !bytes_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad utf16_to_utf8 arguments");
+    DEC_TRY(hipSetDevice(D->device));
+    D->o8.st.calls++;
+    Utf8OutCall J;
+    J.units = units, J.off = off, J.n_texts = n_texts, J.cap = bytes_cap;
+    return utf8_out_to_host(D, J, u16_transcode(D->o8, D->stream, J), bytes_out, out_off);
+}
+
+int bpe_decode_utf8_batch_device(bpe_decoder *D, int kind, const int32_t *d_vals, const int64_t *d_off,
+                                 int64_t n_texts, uint8_t *d_bytes_out, int64_t bytes_cap, int64_t *d_out_off,
+                                 int64_t *needed) {
+    if (!D || !needed || n_texts < 0 || bytes_cap < 0 || !d_out_off || (n_texts && !d_off) ||
+        (bytes_cap && !d_bytes_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad decode_utf8_batch arguments");
+    D->o8.st.calls++;
+    Utf8OutCall J;
+    J.d_bytes = d_bytes_out, J.d_boff = d_out_off, J.cap = bytes_cap;
+    bool transcoded = false;
+    const int rc = decode_utf8_run(D, kind, d_vals, d_off, n_texts, J, &transcoded);
+    return transcoded ? utf8_out_result(D, J, rc, needed) : rc;
+}
+
+int bpe_decode_utf8_batch(bpe_decoder *D, int kind, const int32_t *vals, const int64_t *off, int64_t n_texts,
+                          uint8_t *bytes_out, int64_t bytes_cap, int64_t *out_off) {
+    if (!D || n_texts < 0 || bytes_cap < 0 || !out_off || (n_texts && !off) || (bytes_cap && !bytes_out))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad decode_utf8_batch arguments");
+    if (n_texts && off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+    for (int64_t k = 0; k < n_texts; ++k)
+        if (off[k + 1] < off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+    const int64_t base = n_texts ? off[0] : 0, total = n_texts ? off[n_texts] - base : 0;
+    if (total && !vals) return bpe_fail(BPE_ERR_ARG, "bpe native: null value buffer");
+    DEC_TRY(hipSetDevice(D->device));
+    D->o8.st.calls++;
+    // device staging: [vals | off (n+1)]
+    const size_t b_vals = align16((size_t)total * 4), b_off = align16((size_t)(n_texts + 1) * 8);
+    int rc;
+    if ((rc = grow_dev(&D->d_buf, &D->d_cap, b_vals + b_off))) return rc;
+    int32_t *d_vals = reinterpret_cast<int32_t *>(D->d_buf);
+    int64_t *d_off = reinterpret_cast<int64_t *>(D->d_buf + b_vals);
+    std::vector<int64_t> rel((size_t)n_texts + 1, 0);
+    for (int64_t k = 0; k <= n_texts && n_texts; ++k) rel[(size_t)k] = off[k] - base;
+    if (total) DEC_TRY(hipMemcpyAsync(d_vals, vals + base, (size_t)total * 4, hipMemcpyHostToDevice, D->stream));
+    DEC_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, D->stream));
+    DEC_TRY(hipStreamSynchronize(D->stream));   // (rel goes away with this frame)
+    Utf8OutCall J;
+    J.cap = bytes_cap;
+    bool transcoded = false;
+    rc = decode_utf8_run(D, kind, d_vals, d_off, n_texts, J, &transcoded);
+    return transcoded ? utf8_out_to_host(D, J, rc, bytes_out, out_off) : rc;
+}
+
+int bpe_decoder_get_utf8_stats(bpe_decoder *D, bpe_utf8_stats *out) {
+    if (!D || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = D->o8.st;
+    return BPE_OK;
+}
+
+int bpe_decoder_reset_utf8_stats(bpe_decoder *D) {
+    if (!D) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    D->o8.st = bpe_utf8_stats{};
     return BPE_OK;
 }
 

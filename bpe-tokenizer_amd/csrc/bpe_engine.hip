@@ -4516,10 +4516,13 @@ int export_samples(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const in
     return BPE_OK;
 }
 
-int export_text(bpe_ctx *c, bpe_decoder *D, const int64_t *idx, int64_t n, uint16_t *units, int64_t cap,
-                int64_t *off_out, int64_t *needed_out, bool dev) {
+// (utf8: bytes through bpe_decode_utf8_batch_device instead of units; `units` and cap count bytes then)
+int export_text(bpe_ctx *c, bpe_decoder *D, const int64_t *idx, int64_t n, void *units, int64_t cap,
+                int64_t *off_out, int64_t *needed_out, bool dev, bool utf8 = false) {
     if (!c || cap < 0 || !off_out || (cap && !units) || (dev && !needed_out))
-        return fail(BPE_ERR_ARG, "bpe native: bad export_text_batch arguments");
+        return fail(BPE_ERR_ARG, utf8 ? "bpe native: bad export_utf8_batch arguments"
+                                      : "bpe native: bad export_text_batch arguments");
+    const size_t esize = utf8 ? 1 : 2;
     if (!D) return fail(BPE_ERR_ARG, "bpe native: null decoder");
     int dec_device = -1;
     int rc = decoder_device(D, &dec_device);
@@ -4535,23 +4538,26 @@ int export_text(bpe_ctx *c, bpe_decoder *D, const int64_t *idx, int64_t n, uint1
     const int64_t n_ids = X->needed;
     // scratch: [ids: 4 B per token | the host form's n + 1 unit offsets and units_cap units]
     const size_t b_ids = exp_align((size_t)std::max<int64_t>(n_ids, 1) * 4), b_ooff = dev ? 0 : exp_align((size_t)(n + 1) * 8);
-    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, b_ids + b_ooff + (dev ? 0 : (size_t)cap * 2)))) return rc;
+    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, b_ids + b_ooff + (dev ? 0 : (size_t)cap * esize)))) return rc;
     int32_t *d_ids = reinterpret_cast<int32_t *>(X->d_vals);
     int64_t *d_ooff = dev ? off_out : reinterpret_cast<int64_t *>(X->d_vals + b_ids);
-    uint16_t *d_units = dev ? units : (cap ? reinterpret_cast<uint16_t *>(X->d_vals + b_ids + b_ooff) : nullptr);
+    void *d_units = dev ? units : (cap ? static_cast<void *>(X->d_vals + b_ids + b_ooff) : nullptr);
     if ((rc = export_emit(c, X, EXP_IDS, d_ids))) return rc;
     // Two streams, no events: the ids and their offsets are complete before the decoder starts (this
     // sync), and the decoder's device form synchronises its own stream before it returns.
     HIP_TRY(hipStreamSynchronize(s));
     if ((rc = export_timing(X))) return rc;
     int64_t dneed = -1;   // (set by the decoder once its offsets are written)
-    const int drc = bpe_decode_batch_device(D, BPE_DECODE_IDS, d_ids, X->d_off, n, d_units, cap, d_ooff, &dneed);
+    const int drc = utf8 ? bpe_decode_utf8_batch_device(D, BPE_DECODE_IDS, d_ids, X->d_off, n,
+                                                        static_cast<uint8_t *>(d_units), cap, d_ooff, &dneed)
+                         : bpe_decode_batch_device(D, BPE_DECODE_IDS, d_ids, X->d_off, n,
+                                                   static_cast<uint16_t *>(d_units), cap, d_ooff, &dneed);
     const std::string dmsg = g_err;
     if ((rc = set_device(c))) return rc;
     if (!dev && dneed >= 0) {
         HIP_TRY(hipMemcpyAsync(off_out, d_ooff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
         if (drc == BPE_OK && dneed)
-            HIP_TRY(hipMemcpyAsync(units, d_units, (size_t)dneed * 2, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(units, d_units, (size_t)dneed * esize, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     if (needed_out && dneed >= 0) *needed_out = dneed;
@@ -4594,6 +4600,21 @@ int bpe_export_text_batch_device(bpe_ctx *c, bpe_decoder *dec, const int64_t *id
         return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
                                  "(its shards sit on different devices: take the host form)");
     return export_text(c, dec, idx, n, d_units_out, units_cap, d_out_off, needed, true);
+}
+
+int bpe_export_utf8_batch(bpe_ctx *c, bpe_decoder *dec, const int64_t *idx, int64_t n, uint8_t *bytes_out,
+                          int64_t bytes_cap, int64_t *out_off) {
+    if (dec && n >= 0 && bytes_cap >= 0 && out_off && (!bytes_cap || bytes_out))
+        MULTI(export_utf8_batch(c->multi, dec, idx, n, bytes_out, bytes_cap, out_off));
+    return export_text(c, dec, idx, n, bytes_out, bytes_cap, out_off, nullptr, false, true);
+}
+
+int bpe_export_utf8_batch_device(bpe_ctx *c, bpe_decoder *dec, const int64_t *idx, int64_t n, uint8_t *d_bytes_out,
+                                 int64_t bytes_cap, int64_t *d_out_off, int64_t *needed) {
+    if (c && c->multi)
+        return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
+                                 "(its shards sit on different devices: take the host form)");
+    return export_text(c, dec, idx, n, d_bytes_out, bytes_cap, d_out_off, needed, true, true);
 }
 
 int bpe_get_export_stats(bpe_ctx *c, bpe_export_stats *out) {

@@ -990,6 +990,19 @@ int multi_export_text_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, 
     return bpe_decode_batch(dec, BPE_DECODE_IDS, ids.data(), off.data(), n, units_out, units_cap, out_off);
 }
 
+int multi_export_utf8_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint8_t *bytes_out,
+                            int64_t bytes_cap, int64_t *out_off) {
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    int rc = multi_export_samples(m, BPE_EXPORT_IDS, idx, n, nullptr, 0, nullptr, 0, off.data());
+    if (rc < 0 && !(rc == BPE_ERR_ARG && off[(size_t)n] > 0)) return rc;
+    std::vector<int32_t> ids((size_t)std::max<int64_t>(off[(size_t)n], 1));
+    if (off[(size_t)n]) {
+        m->exp.calls--;   // (one call, asked twice)
+        MTRY(multi_export_samples(m, BPE_EXPORT_IDS, idx, n, nullptr, 0, ids.data(), off[(size_t)n], off.data()));
+    }
+    return bpe_decode_utf8_batch(dec, BPE_DECODE_IDS, ids.data(), off.data(), n, bytes_out, bytes_cap, out_off);
+}
+
 int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out) {
     *out = m->exp;
     for (auto s : m->sh) {

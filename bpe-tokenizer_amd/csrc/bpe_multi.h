@@ -32,6 +32,8 @@ int multi_export_samples(bpe_multi *m, int kind, const int64_t *idx, int64_t n, 
                          int32_t n_index, void *vals_out, int64_t vals_cap, int64_t *out_off);
 int multi_export_text_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint16_t *units_out,
                             int64_t units_cap, int64_t *out_off);
+int multi_export_utf8_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint8_t *bytes_out,
+                            int64_t bytes_cap, int64_t *out_off);
 int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out);
 int multi_reset_export_stats(bpe_multi *m);
 int multi_clear_corpus(bpe_multi *m);

@@ -60,6 +60,12 @@ export declare class BPETokenizer {
    */
   decodeVectorBatch(vectors: number[][]): string[]
   /**
+   * decodeVectorBatch as UTF-8 bytes, encoded on the GPU as `Buffer.from(text)` encodes them (a lone
+   * surrogate becomes EF BF BD): equals `this.decodeVectorBatch(vectors).map(s => Buffer.from(s))`.
+   * The Buffers are slices of one allocation.  Without a HIP device the strings are encoded on the host.
+   */
+  decodeVectorBatchUtf8(vectors: number[][]): Buffer[]
+  /**
    * encodeToVector for many texts at once on the GPU: equals `texts.map(t => this.encodeToVector(t))`,
    * the `unknown token, char: ...` and `unknown token index: N` errors included.  Without a HIP
    * device (or with BPE_ENCODE_DEVICE=0) that map runs in JS.
@@ -98,6 +104,12 @@ export declare class BPETokenizer {
    * Without the addon (or with BPE_ENCODE_DEVICE=0) the chars are joined in JS.
    */
   corpusToTextBatch(indices?: number[]): string[]
+  /**
+   * corpusToTextBatch as UTF-8 bytes, encoded on the GPU: equals
+   * `this.corpusToTextBatch(indices).map(s => Buffer.from(s))`.  The Buffers are slices of one
+   * allocation.  Without the addon (or with BPE_ENCODE_DEVICE=0) the strings are encoded on the host.
+   */
+  corpusToTextBatchUtf8(indices?: number[]): Buffer[]
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

@@ -33,6 +33,8 @@ const {
   corpusCodesOnDevice,
   corpusVectorsOnDevice,
   corpusTextsOnDevice,
+  corpusTextsUtf8OnDevice,
+  decodeVectorsUtf8OnDevice,
   loadNativeUtf8,
   buffersToBytes,
 } = require('./native')
@@ -220,6 +222,19 @@ class BPETokenizer {
       out.push(parts.join(''))
     }
     return out
+  }
+
+  /**
+   * @description corpusToTextBatch as UTF-8 bytes, encoded on the GPU (bpe_export_utf8_batch): equals
+   * `this.corpusToTextBatch(indices).map(s => Buffer.from(s))`, what `fs.writeFileSync(path, s)` would
+   * write.  The Buffers are slices of one allocation.  Without the addon (or with
+   * BPE_ENCODE_DEVICE=0) that string route is taken, with the same results.
+   */
+  corpusToTextBatchUtf8(indices) {
+    if (!this._engine) return []
+    let out = corpusTextsUtf8OnDevice(this, this.engine(), indices)
+    if (out) return out
+    return this.corpusToTextBatch(indices).map(s => Buffer.from(s))
   }
 
   set corpus_in_code(samples) {
@@ -699,6 +714,38 @@ class BPETokenizer {
     } catch (e) {
       let m = /^unknown vector index: (-?\d+) \(text \d+, position \d+\)$/.exec(String(e && e.message))
       if (m) throw new Error(`unknown vector index: ${m[1]}`)
+      throw e
+    }
+  }
+
+  /**
+   * @description decodeVectorBatch as UTF-8 bytes, encoded on the GPU (bpe_decode_utf8_batch): equals
+   * `this.decodeVectorBatch(vectors).map(s => Buffer.from(s))`, the same error included; surrogates
+   * pair across tokens as they do in the joined string, a lone one becomes EF BF BD.  The Buffers are
+   * slices of one allocation.  A batch with an entry that is no int32, and a process without a HIP
+   * device or the addon, take the string route (decodeVector) plus Buffer.from, with the same results.
+   */
+  decodeVectorBatchUtf8(vectors) {
+    if (vectors.length === 0) return []
+    if (!this.from_vector_index) this.compactVectorIndex()
+    let host = () => vectors.map(v => Buffer.from(this.decodeVector(v)))
+    let off = new Float64Array(vectors.length + 1)
+    for (let k = 0; k < vectors.length; k++) off[k + 1] = off[k] + vectors[k].length
+    let vals = new Int32Array(off[vectors.length])
+    let p = 0
+    for (let vector of vectors) {
+      for (let x of vector) {
+        if (typeof x !== 'number' || (x | 0) !== x) return host()
+        vals[p++] = x
+      }
+    }
+    try {
+      return decodeVectorsUtf8OnDevice(this, vals, off)
+    } catch (e) {
+      let msg = String(e && e.message)
+      let m = /^unknown vector index: (-?\d+) \(text \d+, position \d+\)$/.exec(msg)
+      if (m) throw new Error(`unknown vector index: ${m[1]}`)
+      if (/no HIP device/.test(msg) || (e && e.code === 'MODULE_NOT_FOUND')) return host()
       throw e
     }
   }

@@ -40,6 +40,14 @@ function loadNativeUtf8() {
   return nativeUtf8
 }
 
+// the addon of the ways out as UTF-8 (addon/bpe_utf8_out_napi.node: decodeUtf8Batch on a decoder
+// handle, exportUtf8 on an engine handle and a decoder handle)
+let nativeUtf8Out = null
+function loadNativeUtf8Out() {
+  if (!nativeUtf8Out) nativeUtf8Out = require(path.join(__dirname, '..', 'addon', 'bpe_utf8_out_napi.node'))
+  return nativeUtf8Out
+}
+
 // the text encoder's addon (addon/bpe_text_napi.node: createTextEncoder ... encodeTextBatch)
 // the export's addon (addon/bpe_export_napi.node: exportSamples, exportText on an engine handle)
 let nativeExport = null
@@ -218,6 +226,11 @@ function syncDecoder(owner) {
 /** a batch of vectors (Int32Array values, Float64Array offsets) through the owner's decoder -> strings */
 function decodeVectorsOnDevice(owner, vals, off) {
   return loadNativeDecode().decodeBatch(syncDecoder(owner), vals, off, 1)
+}
+
+/** ... as UTF-8 bytes, encoded on the device as Buffer.from(text) encodes them -> Buffer[] */
+function decodeVectorsUtf8OnDevice(owner, vals, off) {
+  return loadNativeUtf8Out().decodeUtf8Batch(syncDecoder(owner), vals, off, 1)
 }
 
 /**
@@ -522,6 +535,19 @@ function corpusTextsOnDevice(owner, engine, indices) {
   return addon.exportText(engine, syncDecoder(owner), exportIndices(indices))
 }
 
+/** ... as UTF-8 bytes (bpe_export_utf8_batch) -> Buffer[], or null when there is no addon to ask */
+function corpusTextsUtf8OnDevice(owner, engine, indices) {
+  if (!exportAddon()) return null
+  let addon
+  try {
+    addon = loadNativeUtf8Out()
+  } catch (e) {
+    if (ENCODE_DEVICE === '1') throw e
+    return null
+  }
+  return addon.exportUtf8(engine, syncDecoder(owner), exportIndices(indices))
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -560,6 +586,7 @@ module.exports = {
   loadNativeIngest,
   loadNativeRestore,
   loadNativeUtf8,
+  loadNativeUtf8Out,
   buffersToBytes,
   maxLengthArg,
   minWeightArg,
@@ -568,6 +595,7 @@ module.exports = {
   encodeIdsMaybeOnDevice,
   syncDecoder,
   decodeVectorsOnDevice,
+  decodeVectorsUtf8OnDevice,
   syncTextEncoder,
   encodeTextsMaybeOnDevice,
   restoreTextsMaybeOnDevice,
@@ -578,4 +606,5 @@ module.exports = {
   corpusCodesOnDevice,
   corpusVectorsOnDevice,
   corpusTextsOnDevice,
+  corpusTextsUtf8OnDevice,
 }

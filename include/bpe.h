@@ -830,6 +830,70 @@ int bpe_encoder_reset_utf8_stats(bpe_encoder *enc);
 int bpe_get_utf8_stats(bpe_ctx *ctx, bpe_utf8_stats *out);
 int bpe_reset_utf8_stats(bpe_ctx *ctx);
 
+/* ---- text out as UTF-8 ---------------------------------------------------------------------------
+ * The ways out of the device that end in text (bpe_decode_batch, bpe_export_text_batch) as UTF-8
+ * bytes (files, dataset shards, sockets, byte tensors) instead of UTF-16 units: the units are
+ * transcoded to bytes on the device, so a host form brings back 1-3 B per unit already encoded, and
+ * with the forms of "text as UTF-8" above bytes -> corpus -> merges -> bytes and bytes -> vectors ->
+ * bytes cross PCIe as bytes and offsets only.  Everything here sits on a decoder, its device and
+ * stream, and keeps grow-only scratch there (2 B per decoded unit and 8 B per text, besides the
+ * transcode's tiles); BPE_ERR_OOM changes nothing.
+ *
+ * Text k is units[off[k] .. off[k+1]) and encodes on its own, exactly as Node's
+ * Buffer.from(str, 'utf8'), TextEncoder.encode(str) and fs.writeFileSync(path, str) encode a JS
+ * string (the WHATWG conversion to a USVString, then UTF-8): a high surrogate followed in its text by
+ * a low one becomes the four bytes of their code point, any other surrogate EF BF BD (U+FFFD), every
+ * other unit one, two or three bytes.  A high surrogate that ends text k and a low one that starts
+ * text k + 1 are both lone; U+FEFF is a char like any other (no BOM is added or dropped); a text
+ * never makes more than 3 bytes per unit.  On well-formed text this is the inverse of
+ * bpe_encoder_utf8_to_utf16.  Lone surrogates are not an error.
+ *
+ * bpe_decoder_utf16_to_utf8 is the transcode alone.  Offsets follow bpe_encode_text_batch's rules
+ * (off[0] need not be 0 and units before it are never read; decreasing or negative offsets give
+ * BPE_ERR_ARG with nothing written; n_texts == 0 is fine), capacity follows bpe_decode_batch's:
+ * out_off receives n_texts + 1 offsets with out_off[0] = 0; when out_off[n_texts] exceeds bytes_cap
+ * the offsets are written, no byte is, and BPE_ERR_ARG comes back (bytes_out == NULL with bytes_cap 0
+ * is the sizing call).  bytes_cap >= 3 * (off[n_texts] - off[0]) always suffices.  The `_device`
+ * form takes and fills buffers on the decoder's device (any 2-byte aligned unit pointer, any byte
+ * pointer), reads the offsets back (8 B per text) and synchronises before returning; *needed (a host
+ * int64) receives the bytes.
+ *
+ * bpe_decode_utf8_batch is bpe_decode_batch_device into the scratch, then that transcode: the
+ * decoder's errors and messages come back as they are, with nothing written (`unknown vector index:
+ * V (text K, position I)`, `unknown token index: ...`, BPE_ERR_STATE without a vector index).
+ * Surrogates pair on the decoded text, as in the reference's `content += token.chars` (core.ts:462-
+ * 468): a token that is a lone high surrogate followed by one that is a lone low surrogate becomes one
+ * 4-byte sequence.
+ *
+ * bpe_export_utf8_batch is bpe_export_text_batch's route with bpe_decode_utf8_batch_device in place
+ * of the UTF-16 decode: the same idx rules, the same "an export only reads" guarantee, the same
+ * decoder-device check.  A multi-device context takes the host form as bpe_export_text_batch does,
+ * shard by shard (through the decoder's host form); the device form refuses it with BPE_ERR_ARG.
+ *
+ * bpe_decoder_get_utf8_stats fills a bpe_utf8_stats read the other way round: calls, and for the
+ * calls whose whole pipeline succeeded and wrote its bytes their texts, `units` taken in, `bytes`
+ * written, `replaced` (lone surrogates turned into EF BF BD; a U+FFFD unit is not counted) and the
+ * HIP-event time of the transcode kernels alone (the decode's is in bpe_decoder_stats).
+ * The kernels work on tiles of BPE_UTF16_TILE units and scan BPE_TEXT_SCAN_ROUND tile counts per
+ * round (csrc/bpe_utf8_out.hip.h; exported for the tests). */
+#define BPE_UTF16_TILE 2048
+int bpe_decoder_utf16_to_utf8(bpe_decoder *dec, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                              uint8_t *bytes_out, int64_t bytes_cap, int64_t *out_off);
+int bpe_decoder_utf16_to_utf8_device(bpe_decoder *dec, const uint16_t *d_units, const int64_t *d_off,
+                                     int64_t n_texts, uint8_t *d_bytes_out, int64_t bytes_cap,
+                                     int64_t *d_out_off, int64_t *needed);
+int bpe_decode_utf8_batch(bpe_decoder *dec, int kind, const int32_t *vals, const int64_t *off, int64_t n_texts,
+                          uint8_t *bytes_out, int64_t bytes_cap, int64_t *out_off);
+int bpe_decode_utf8_batch_device(bpe_decoder *dec, int kind, const int32_t *d_vals, const int64_t *d_off,
+                                 int64_t n_texts, uint8_t *d_bytes_out, int64_t bytes_cap, int64_t *d_out_off,
+                                 int64_t *needed);
+int bpe_export_utf8_batch(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *idx, int64_t n,
+                          uint8_t *bytes_out, int64_t bytes_cap, int64_t *out_off);
+int bpe_export_utf8_batch_device(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *idx, int64_t n,
+                                 uint8_t *d_bytes_out, int64_t bytes_cap, int64_t *d_out_off, int64_t *needed);
+int bpe_decoder_get_utf8_stats(bpe_decoder *dec, bpe_utf8_stats *out);
+int bpe_decoder_reset_utf8_stats(bpe_decoder *dec);
+
 #ifdef __cplusplus
 }
 #endif
