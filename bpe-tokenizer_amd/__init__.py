@@ -60,6 +60,10 @@ C_API = [
     'bpe_decoder_utf16_to_utf8', 'bpe_decoder_utf16_to_utf8_device', 'bpe_decode_utf8_batch',
     'bpe_decode_utf8_batch_device', 'bpe_export_utf8_batch', 'bpe_export_utf8_batch_device',
     'bpe_decoder_get_utf8_stats', 'bpe_decoder_reset_utf8_stats',
+    'bpe_encoder_split_lines', 'bpe_encoder_split_lines_device', 'bpe_add_lines_batch', 'bpe_add_lines_batch_device',
+    'bpe_add_lines_utf8_batch', 'bpe_add_lines_utf8_batch_device', 'bpe_restore_lines_batch',
+    'bpe_restore_lines_batch_device', 'bpe_restore_lines_utf8_batch', 'bpe_restore_lines_utf8_batch_device',
+    'bpe_encoder_get_lines_stats', 'bpe_encoder_reset_lines_stats', 'bpe_get_lines_stats', 'bpe_reset_lines_stats',
 ]
 HOT_BINS = 65536
 TABLE_BINS = 81920
@@ -97,6 +101,11 @@ EXPORT_VECTORS = 1  # BPE_EXPORT_VECTORS: ... as vector indices (encodeToVector 
 EXPORT_CODE = 2     # BPE_EXPORT_CODE: ... as uint16 code units id + 1 (corpus_in_code)
 UTF8_TILE = 4096    # BPE_UTF8_TILE: bytes per workgroup of the UTF-8 transcode (its scan round: TEXT_SCAN_ROUND)
 UTF16_TILE = 2048   # BPE_UTF16_TILE: units per workgroup of the transcode to UTF-8 (the same scan round)
+LINES_TRIM = 0      # BPE_LINES_TRIM: linesToCorpus (cut at LF, trim(), wrapped in CR .. LF)
+LINES_KEEP = 1      # BPE_LINES_KEEP: linesTrimmedToCorpus (cut at LF, one trailing CR dropped, the same wrap)
+LINES_FILE = 2      # BPE_LINES_FILE: fileContentToCorpus (U+001C + text + U+0004)
+_LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
+                LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
 
 ERR_ARG, ERR_HIP, ERR_OOM, ERR_STATE, ERR_VOCAB = -1, -2, -3, -4, -5
@@ -216,6 +225,16 @@ class Utf8Stats(ctypes.Structure):
     """bpe_utf8_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('bytes', ctypes.c_int64),
                 ('units', ctypes.c_int64), ('replaced', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LinesStats(ctypes.Structure):
+    """bpe_lines_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units_in', ctypes.c_int64),
+                ('samples', ctypes.c_int64), ('units_out', ctypes.c_int64), ('trimmed', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -378,6 +397,26 @@ def lib():
                                          ctypes.c_int),
         'bpe_decoder_get_utf8_stats': ([vp, ctypes.POINTER(Utf8Stats)], ctypes.c_int),
         'bpe_decoder_reset_utf8_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_split_lines': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p,
+                                     ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_encoder_split_lines_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp,
+                                            ctypes.c_int64, i64p, i64p], ctypes.c_int),
+        'bpe_add_lines_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p,
+                                 ctypes.c_int64], ctypes.c_int),
+        'bpe_add_lines_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p,
+                                        ctypes.c_int64], ctypes.c_int),
+        'bpe_add_lines_utf8_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, vp, ctypes.c_int64, i64p, i64p,
+                                      ctypes.c_int64], ctypes.c_int),
+        'bpe_add_lines_utf8_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, i64p,
+                                             i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_lines_batch': ([vp, vp, ctypes.c_int, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_lines_batch_device': ([vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_lines_utf8_batch': ([vp, vp, ctypes.c_int, vp, i64p, ctypes.c_int64], ctypes.c_int),
+        'bpe_restore_lines_utf8_batch_device': ([vp, vp, ctypes.c_int, vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_encoder_get_lines_stats': ([vp, ctypes.POINTER(LinesStats)], ctypes.c_int),
+        'bpe_encoder_reset_lines_stats': ([vp], ctypes.c_int),
+        'bpe_get_lines_stats': ([vp, ctypes.POINTER(LinesStats)], ctypes.c_int),
+        'bpe_reset_lines_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -679,6 +718,99 @@ class Engine:
 
     def reset_utf8_stats(self):
         _check(lib().bpe_reset_utf8_stats(self._ctx), 'bpe_reset_utf8_stats')
+
+    # lines as samples (include/bpe.h "lines as samples"): the corpus helpers on the device ------------
+    def _add_lines(self, name, mode, ptr, off_ptr, n, new_cap):
+        mode, fn = lines_mode(mode), getattr(lib(), name)
+        return self._add_text(lambda ctx, *rest: fn(ctx, mode, *rest), name, ptr, off_ptr, n, new_cap)
+
+    def add_lines_flat(self, units, off, mode='trim', new_cap=1024):
+        """Flat form (bpe_add_lines_batch): texts units[off[k]:off[k+1]] (UTF-16 units) are split into
+        samples by the helper `mode` names ('trim': linesToCorpus, 'keep': linesTrimmedToCorpus,
+        'file': fileContentToCorpus) and ingested as add_text ingests them -> (new_chars, hist)."""
+        mode = lines_mode(mode)
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        return self._add_lines('bpe_add_lines_batch', mode, src.ctypes.data,
+                               off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1, new_cap)
+
+    def add_lines(self, texts, mode='trim', new_cap=1024):
+        """texts: a list of str (lone surrogates survive), each split into samples -> (new_chars, hist)."""
+        units, off = _units_flat(texts)
+        return self.add_lines_flat(units, off, mode, new_cap)
+
+    def add_lines_tensors(self, units, off, mode='trim', new_cap=1024):
+        """Device form (bpe_add_lines_batch_device): units a torch int16 or uint16 tensor and off a
+        torch int64 tensor on the context's device -> (new_chars, hist) as numpy arrays."""
+        mode = lines_mode(mode)
+        units, off = _units_tensors(units, off, 'add_lines_tensors')
+        return self._add_lines('bpe_add_lines_batch_device', mode, units.data_ptr() if units.numel() else None,
+                               off.data_ptr(), off.numel() - 1, new_cap)
+
+    def add_lines_utf8(self, texts, off=None, mode='trim', new_cap=1024):
+        """add_lines for UTF-8: texts a list of bytes (files), or the flat form (uint8 array, int64
+        offsets); transcoded and split on the device -> (new_chars, hist)."""
+        mode = lines_mode(mode)
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        return self._add_lines('bpe_add_lines_utf8_batch', mode, src.ctypes.data,
+                               off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1, new_cap)
+
+    def add_lines_utf8_tensors(self, data, off, mode='trim', new_cap=1024):
+        """Device form (bpe_add_lines_utf8_batch_device): torch uint8 bytes and int64 offsets on the
+        context's device -> (new_chars, hist) as numpy arrays."""
+        mode = lines_mode(mode)
+        data, off = _utf8_tensors(data, off, 'add_lines_utf8_tensors')
+        return self._add_lines('bpe_add_lines_utf8_batch_device', mode, data.data_ptr() if data.numel() else None,
+                               off.data_ptr(), off.numel() - 1, new_cap)
+
+    def _restore_lines(self, name, enc, mode, ptr, off_ptr, n):
+        _check(getattr(lib(), name)(self._ctx, enc._enc if enc is not None else None, mode, ptr, off_ptr, n), name)
+
+    def restore_lines_flat(self, enc, units, off, mode='trim'):
+        """Flat form (bpe_restore_lines_batch): the texts' samples are encoded by `enc` and appended,
+        as restore_text appends them.  The batch is atomic."""
+        mode = lines_mode(mode)
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        self._restore_lines('bpe_restore_lines_batch', enc, mode, src.ctypes.data,
+                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1)
+
+    def restore_lines(self, enc, texts, mode='trim'):
+        """texts: a list of str, each split into samples and restored."""
+        self.restore_lines_flat(enc, *_units_flat(texts), mode)
+
+    def restore_lines_tensors(self, enc, units, off, mode='trim'):
+        """Device form (bpe_restore_lines_batch_device)."""
+        mode = lines_mode(mode)
+        units, off = _units_tensors(units, off, 'restore_lines_tensors')
+        self._restore_lines('bpe_restore_lines_batch_device', enc, mode, units.data_ptr() if units.numel() else None,
+                            off.data_ptr(), off.numel() - 1)
+
+    def restore_lines_utf8(self, enc, texts, off=None, mode='trim'):
+        """restore_lines for UTF-8: texts a list of bytes, or the flat form (uint8 array, int64 offsets)."""
+        mode = lines_mode(mode)
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        self._restore_lines('bpe_restore_lines_utf8_batch', enc, mode, src.ctypes.data,
+                            off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(off) - 1)
+
+    def restore_lines_utf8_tensors(self, enc, data, off, mode='trim'):
+        """Device form (bpe_restore_lines_utf8_batch_device)."""
+        mode = lines_mode(mode)
+        data, off = _utf8_tensors(data, off, 'restore_lines_utf8_tensors')
+        self._restore_lines('bpe_restore_lines_utf8_batch_device', enc, mode, data.data_ptr() if data.numel() else None,
+                            off.data_ptr(), off.numel() - 1)
+
+    def lines_stats(self):
+        s = LinesStats()
+        _check(lib().bpe_get_lines_stats(self._ctx, ctypes.byref(s)), 'bpe_get_lines_stats')
+        return s.as_dict()
+
+    def reset_lines_stats(self):
+        _check(lib().bpe_reset_lines_stats(self._ctx), 'bpe_reset_lines_stats')
 
     def token_counts(self):
         """Occurrences of every token id in the corpus (int64; the engine's own exact counts)."""
@@ -1348,6 +1480,110 @@ class Encoder:
 
     def reset_utf8_stats(self):
         _check(lib().bpe_encoder_reset_utf8_stats(self._enc), 'bpe_encoder_reset_utf8_stats')
+
+    # lines as samples (include/bpe.h "lines as samples"): the corpus helpers on the device ------------
+    def split_lines_flat(self, units, off, mode='trim'):
+        """The split alone (bpe_encoder_split_lines): texts units[off[k]:off[k+1]] (UTF-16 units) ->
+        (units uint16, out_off int64) of the samples the helper `mode` names makes of them ('trim':
+        linesToCorpus, 'keep': linesTrimmedToCorpus, 'file': fileContentToCorpus)."""
+        mode = lines_mode(mode)
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        if n > 0 and (off[0] < 0 or np.any(np.diff(off) < 0)):
+            raise BpeError('split_lines: text offsets must not decrease', ERR_ARG)
+        total = int(off[-1] - off[0]) if n > 0 else 0
+        out = np.zeros(max(3 * total + 2 * n, 1), dtype=np.uint16)
+        out_off = np.zeros(total + n + 1, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        ns = ctypes.c_int64()
+        _check(lib().bpe_encoder_split_lines(self._enc, mode, src.ctypes.data, off.ctypes.data_as(i64p), n,
+                                             out.ctypes.data, out.size, out_off.ctypes.data_as(i64p), out_off.size,
+                                             ctypes.byref(ns)), 'bpe_encoder_split_lines')
+        out_off = out_off[:ns.value + 1].copy()
+        return out[:out_off[-1]].copy(), out_off
+
+    def split_lines(self, texts, mode='trim'):
+        """texts: a list of str (lone surrogates survive) -> the list of str texts.flatMap(helper) gives."""
+        units, off = _units_flat(texts)
+        out, oo = self.split_lines_flat(units, off, mode)
+        return [units_to_str(out[oo[k]:oo[k + 1]]) for k in range(len(oo) - 1)]
+
+    def split_lines_tensors(self, units, off, mode='trim', out=None, out_off=None):
+        """Device form (bpe_encoder_split_lines_device): units a torch int16 or uint16 tensor and off
+        a torch int64 tensor on the encoder's device -> (int16 tensor of the samples' units, int64
+        offsets tensor), both on that device.  With out and out_off (contiguous int16 and int64 tensors
+        on that device; 3 * units + 2 * texts and units + texts + 1 entries always suffice) the split
+        runs once into them and views of them come back; without, a sizing call runs first."""
+        import torch
+        mode = lines_mode(mode)
+        units, off = _units_tensors(units, off, 'split_lines_tensors', self.device)
+        n = off.numel() - 1
+        up = units.data_ptr() if units.numel() else None
+        ns, need = ctypes.c_int64(), ctypes.c_int64()
+        if out is not None and out_off is not None:
+            if out.dtype != torch.int16 or out_off.dtype != torch.int64 or out.device != units.device or \
+                    out_off.device != units.device or not (out.is_contiguous() and out_off.is_contiguous()):
+                raise BpeError('split_lines_tensors takes contiguous int16 and int64 outputs on the device', ERR_ARG)
+            _check(lib().bpe_encoder_split_lines_device(self._enc, mode, up, off.data_ptr(), n, out.data_ptr(),
+                                                        out.numel(), out_off.data_ptr(), out_off.numel(),
+                                                        ctypes.byref(ns), ctypes.byref(need)),
+                   'bpe_encoder_split_lines_device')
+            return out[:need.value], out_off[:ns.value + 1]
+        rc = lib().bpe_encoder_split_lines_device(self._enc, mode, up, off.data_ptr(), n, None, 0, None, 0,
+                                                  ctypes.byref(ns), ctypes.byref(need))
+        # (the sizing call: too small even for no sample's one offset, so ERR_ARG with the numbers;
+        # without a sample there was no text, and nothing else can be wrong)
+        if rc != ERR_ARG or (ns.value <= 0 and n != 0):
+            _check(rc, 'bpe_encoder_split_lines_device')
+        out = torch.empty(max(need.value, 1), dtype=torch.int16, device=units.device)
+        out_off = torch.zeros(ns.value + 1, dtype=torch.int64, device=units.device)
+        torch.cuda.synchronize(units.device)
+        _check(lib().bpe_encoder_split_lines_device(self._enc, mode, up, off.data_ptr(), n, out.data_ptr(),
+                                                    out.numel(), out_off.data_ptr(), out_off.numel(),
+                                                    ctypes.byref(ns), ctypes.byref(need)),
+               'bpe_encoder_split_lines_device')
+        return out[:need.value], out_off
+
+    def lines_stats(self):
+        s = LinesStats()
+        _check(lib().bpe_encoder_get_lines_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_lines_stats')
+        return s.as_dict()
+
+    def reset_lines_stats(self):
+        _check(lib().bpe_encoder_reset_lines_stats(self._enc), 'bpe_encoder_reset_lines_stats')
+
+
+def lines_mode(mode):
+    """'trim' | 'keep' | 'file' (or the LINES_* constant) -> the constant; anything else is an error."""
+    try:
+        return _LINES_MODES[mode]
+    except (KeyError, TypeError):
+        raise BpeError('unknown lines mode %r (trim, keep or file)' % (mode,), ERR_ARG)
+
+
+def _units_flat(texts):
+    """A list of str (or unit arrays) as (uint16 array, int64 offsets)."""
+    parts = [_units(t) for t in texts]
+    off = np.zeros(len(parts) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in parts], out=off[1:])
+    units = np.concatenate(parts).astype(np.uint16) if parts and off[-1] else np.zeros(0, np.uint16)
+    return units, off
+
+
+def _units_tensors(units, off, what, device=None):
+    """Checks a device batch of UTF-16 units: a torch int16 or uint16 tensor and int64 offsets on one
+    device (`device`: which one)."""
+    import torch
+    if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+        raise BpeError('%s takes int16 or uint16 units and int64 offsets' % what, ERR_ARG)
+    if not (units.is_cuda and off.is_cuda and units.device == off.device) or \
+            (device is not None and units.device.index != device):
+        raise BpeError('%s takes tensors on the device of the call' % what, ERR_ARG)
+    units, off = units.contiguous(), off.contiguous()
+    torch.cuda.synchronize(units.device)   # (contexts and encoders run on streams of their own)
+    return units, off
 
 
 def _utf8_flat(texts, off):

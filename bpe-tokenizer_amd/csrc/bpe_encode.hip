@@ -472,6 +472,7 @@ k_text_ooff(const int64_t *__restrict__ ooff, const int64_t *__restrict__ seg_of
 
 #include "bpe_text.hip.h"   // the text front end and the vector back end (bpe_encode_text_batch)
 #include "bpe_utf8.hip.h"   // text as UTF-8: bytes -> units in front of it (bpe_encode_utf8_batch)
+#include "bpe_lines.hip.h"  // lines as samples: texts -> samples (bpe_encoder_split_lines)
 
 struct bpe_encoder {
     int device = 0;
@@ -506,6 +507,9 @@ struct bpe_encoder {
     bpe_text_state txt;                       // the text form (bpe_encode_text_batch)
     Utf8State u8;                             // text as UTF-8 (bpe_encoder_utf8_to_utf16 and what builds on it)
     Utf8Call u8_pending;                      // a restore's transcode, counted when the restore is done
+    LinesState ln;                            // lines as samples (bpe_encoder_split_lines and the restore from lines)
+    LinesCall ln_pending;                     // a restore's split, counted when the restore is done
+    bool ln_pending_u8 = false;               // ... which had a transcode in front
     // long texts in segments (BPE_LONG_SPLIT): first and last base id of every id (identity until
     // a merge makes it), the ids made so far, and the tables k_cuts reads (built and uploaded
     // with the rank table when dirty)
@@ -1665,6 +1669,45 @@ int encoder_utf8_units(bpe_encoder *E, const uint8_t *bytes, const int64_t *off,
 
 void encoder_utf8_done(bpe_encoder *E) { u8_commit(E->u8, E->u8_pending); }
 
+// The restore from lines (bpe_engine.hip): the texts (UTF-16 units, or UTF-8 bytes transcoded first)
+// split into samples in the encoder's scratch, on its device; the call's numbers are counted by
+// encoder_lines_done once the restore has succeeded.
+int encoder_lines_units(bpe_encoder *E, int mode, const void *src, const int64_t *off, int64_t n_texts, bool dev,
+                        bool utf8, const uint16_t **d_units, const int64_t **d_uoff, int64_t *n_samples,
+                        int64_t *n_units) {
+    if (!E || !d_units || !d_uoff || !n_samples || !n_units) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    ENC_TRY(hipSetDevice(E->device));
+    E->ln.st.calls++;
+    LinesCall J;
+    J.mode = mode, J.n_texts = n_texts;
+    E->ln_pending_u8 = utf8;
+    if (utf8) {
+        E->u8.st.calls++;
+        Utf8Call U;
+        U.bytes = static_cast<const uint8_t *>(src), U.off = off, U.n_texts = n_texts, U.dev = dev;
+        const int rc = u8_transcode(E->u8, E->stream, U);
+        if (rc) return rc;
+        J.units = U.d_units, J.off = U.d_uoff, J.dev = true;
+        U.h_off.clear();
+        E->u8_pending = U;
+    } else {
+        J.units = static_cast<const uint16_t *>(src), J.off = off, J.dev = dev;
+    }
+    const int rc = ln_split(E->ln, E->stream, J);
+    if (rc) return rc;
+    *d_units = J.d_out;
+    *d_uoff = J.d_ooff;
+    *n_samples = J.samples;
+    *n_units = J.units_out;
+    E->ln_pending = J;
+    return BPE_OK;
+}
+
+void encoder_lines_done(bpe_encoder *E) {
+    if (E->ln_pending_u8) u8_commit(E->u8, E->u8_pending);
+    ln_commit(E->ln, E->ln_pending);
+}
+
 extern "C" {
 
 int bpe_encoder_create(bpe_encoder **out, int device) {
@@ -1721,6 +1764,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     if (E->h_buf) (void)hipHostFree(E->h_buf);
     text_free(E);
     u8_free(E->u8);
+    ln_free(E->ln);
     if (E->ev0) (void)hipEventDestroy(E->ev0);
     if (E->ev1) (void)hipEventDestroy(E->ev1);
     for (int i = 0; i < 2; ++i)
@@ -2011,6 +2055,63 @@ int bpe_encoder_get_utf8_stats(bpe_encoder *E, bpe_utf8_stats *out) {
 int bpe_encoder_reset_utf8_stats(bpe_encoder *E) {
     if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
     E->u8.st = bpe_utf8_stats{};
+    return BPE_OK;
+}
+
+int bpe_encoder_split_lines(bpe_encoder *E, int mode, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                            uint16_t *units_out, int64_t units_cap, int64_t *out_off, int64_t off_cap,
+                            int64_t *n_samples) {
+    if (!E || !n_samples || units_cap < 0 || off_cap < 0 || (units_cap && !units_out) || (off_cap && !out_off))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad split_lines arguments");
+    *n_samples = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->ln.st.calls++;
+    LinesCall J;
+    J.mode = mode, J.units = units, J.off = off, J.n_texts = n_texts, J.dev = false;
+    J.units_cap = units_cap, J.off_cap = off_cap;
+    const int rc = ln_split(E->ln, E->stream, J);
+    *n_samples = J.samples;
+    if (rc) return rc;
+    if (!J.fits) return ln_cap_error(J);
+    ENC_TRY(hipMemcpyAsync(out_off, J.d_ooff, (size_t)(J.samples + 1) * 8, hipMemcpyDeviceToHost, E->stream));
+    if (J.units_out)
+        ENC_TRY(hipMemcpyAsync(units_out, J.d_out, (size_t)J.units_out * 2, hipMemcpyDeviceToHost, E->stream));
+    ENC_TRY(hipStreamSynchronize(E->stream));
+    ln_commit(E->ln, J);
+    return BPE_OK;
+}
+
+int bpe_encoder_split_lines_device(bpe_encoder *E, int mode, const uint16_t *d_units, const int64_t *d_off,
+                                   int64_t n_texts, uint16_t *d_units_out, int64_t units_cap, int64_t *d_out_off,
+                                   int64_t off_cap, int64_t *n_samples, int64_t *needed) {
+    if (!E || !n_samples || !needed || units_cap < 0 || off_cap < 0 || (units_cap && !d_units_out) ||
+        (off_cap && !d_out_off) || ((uintptr_t)d_units_out & 1))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad split_lines arguments");
+    *n_samples = *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->ln.st.calls++;
+    LinesCall J;
+    J.mode = mode, J.units = d_units, J.off = d_off, J.n_texts = n_texts, J.dev = true;
+    J.units_cap = units_cap, J.off_cap = off_cap;
+    J.d_out = units_cap ? d_units_out : nullptr, J.d_ooff = off_cap ? d_out_off : nullptr;
+    const int rc = ln_split(E->ln, E->stream, J);
+    *n_samples = J.samples;
+    *needed = J.units_out;
+    if (rc) return rc;
+    if (!J.fits) return ln_cap_error(J);
+    ln_commit(E->ln, J);
+    return BPE_OK;
+}
+
+int bpe_encoder_get_lines_stats(bpe_encoder *E, bpe_lines_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->ln.st;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_lines_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->ln.st = bpe_lines_stats{};
     return BPE_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "bpe_export.hip.h"   // the corpus export (bpe_export_samples, bpe_export_text_batch)
 #include "bpe_multi.h"
 #include "bpe_utf8.hip.h"     // text as UTF-8: bytes -> units in front of the ingest (bpe_add_utf8_batch)
+#include "bpe_lines.hip.h"    // lines as samples: texts -> samples in front of the ingest (bpe_add_lines_batch)
 #include "bpe_tools.h"
 
 namespace bpe_step {
@@ -248,6 +249,7 @@ struct bpe_ctx {
     struct ExportState *exp = nullptr;
     // text as UTF-8: the transcode's scratch and counters (made by its first call)
     Utf8State *u8 = nullptr;
+    LinesState *ln = nullptr;
 };
 
 void ingest_free(bpe_ctx *c);
@@ -2836,6 +2838,10 @@ int bpe_destroy(bpe_ctx *c) {
         u8_free(*c->u8);
         delete c->u8;
     }
+    if (c->ln) {
+        ln_free(*c->ln);
+        delete c->ln;
+    }
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -4221,6 +4227,143 @@ int bpe_reset_utf8_stats(bpe_ctx *c) {
     if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
     bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
     if (t->u8) t->u8->st = bpe_utf8_stats{};
+    return BPE_OK;
+}
+
+}  // extern "C"
+
+// ---- lines as samples (include/bpe.h): the split of bpe_lines.hip.h, then the UTF-16 device forms ----
+
+namespace {
+
+int add_lines(bpe_ctx *c, int mode, const void *src, const int64_t *off, int64_t n_texts, bool dev, bool utf8,
+              uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    // (the UTF-16 form's own argument check, made before any work here as it is made there)
+    if (!c || !n_new || n_texts < 0 || n_texts >= 0x7FFFFFFF || new_cap < 0 || hist_cap < 0 || (n_texts && !off) ||
+        (new_cap && !new_chars) || (hist_cap && !id_hist))
+        return fail(BPE_ERR_ARG, "bpe native: bad add_text_batch arguments");
+    *n_new = 0;
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;   // the context that splits
+    int rc = set_device(t);
+    if (rc) return rc;
+    if (!t->ln) t->ln = new LinesState();
+    t->ln->st.calls++;
+    LinesCall J;
+    J.mode = mode, J.n_texts = n_texts;
+    Utf8Call U;
+    if (utf8) {
+        if (!t->u8) t->u8 = new Utf8State();
+        t->u8->st.calls++;
+        U.bytes = static_cast<const uint8_t *>(src), U.off = off, U.n_texts = n_texts, U.dev = dev;
+        if ((rc = u8_transcode(*t->u8, t->stream, U))) return rc;
+        J.units = U.d_units, J.off = U.d_uoff, J.dev = true;
+    } else {
+        J.units = static_cast<const uint16_t *>(src), J.off = off, J.dev = dev;
+    }
+    if ((rc = ln_split(*t->ln, t->stream, J))) return rc;
+    if (c->multi) {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> uoff;
+        if ((rc = utf8_units_to_host(t->stream, J.d_out, J.d_ooff, J.samples, J.units_out, units, uoff))) return rc;
+        rc = multi_add_text_batch(c->multi, units.data(), uoff.data(), J.samples, false, new_chars, new_cap, n_new,
+                                  id_hist, hist_cap);
+    } else {
+        rc = ingest_text(c, J.d_out, J.d_ooff, J.samples, true, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+    }
+    if (rc) return rc;
+    if (utf8) u8_commit(*t->u8, U);
+    ln_commit(*t->ln, J);
+    return BPE_OK;
+}
+
+int restore_lines(bpe_ctx *c, bpe_encoder *E, int mode, const void *src, const int64_t *off, int64_t n, bool dev,
+                  bool utf8) {
+    // (the UTF-16 form's own checks, made before any work here as they are made there)
+    if (!c || n < 0 || n >= 0x7FFFFFFF || (n && !off))
+        return fail(BPE_ERR_ARG, "bpe native: bad restore_text_batch arguments");
+    if (!E) return fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int enc_device = -1;
+    int rc = encoder_device(E, &enc_device);
+    if (rc) return rc;
+    if (!c->multi && enc_device != c->device)
+        return fail(BPE_ERR_ARG, "bpe native: the encoder is on another device than the context");
+    const uint16_t *d_units = nullptr;
+    const int64_t *d_uoff = nullptr;
+    int64_t n_samples = 0, n_units = 0;
+    if ((rc = encoder_lines_units(E, mode, src, off, n, dev, utf8, &d_units, &d_uoff, &n_samples, &n_units))) return rc;
+    if (c->multi) {
+        std::vector<uint16_t> units;
+        std::vector<int64_t> uoff;
+        HIP_TRY(hipSetDevice(enc_device));
+        // (the encoder's split has synchronised its stream: a plain copy follows it)
+        if ((rc = utf8_units_to_host(nullptr, d_units, d_uoff, n_samples, n_units, units, uoff))) return rc;
+        rc = multi_restore_text_batch(c->multi, E, units.data(), uoff.data(), n_samples, false);
+    } else {
+        rc = restore_text(c, E, d_units, d_uoff, n_samples, true);
+    }
+    if (rc) return rc;
+    encoder_lines_done(E);
+    return BPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpe_add_lines_batch(bpe_ctx *c, int mode, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                        uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap) {
+    return add_lines(c, mode, units, off, n_texts, false, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_add_lines_batch_device(bpe_ctx *c, int mode, const uint16_t *d_units, const int64_t *d_off, int64_t n_texts,
+                               uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                               int64_t hist_cap) {
+    return add_lines(c, mode, d_units, d_off, n_texts, true, false, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_add_lines_utf8_batch(bpe_ctx *c, int mode, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                             uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                             int64_t hist_cap) {
+    return add_lines(c, mode, bytes, off, n_texts, false, true, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_add_lines_utf8_batch_device(bpe_ctx *c, int mode, const uint8_t *d_bytes, const int64_t *d_off,
+                                    int64_t n_texts, uint32_t *new_chars, int64_t new_cap, int64_t *n_new,
+                                    int64_t *id_hist, int64_t hist_cap) {
+    return add_lines(c, mode, d_bytes, d_off, n_texts, true, true, new_chars, new_cap, n_new, id_hist, hist_cap);
+}
+
+int bpe_restore_lines_batch(bpe_ctx *c, bpe_encoder *enc, int mode, const uint16_t *units, const int64_t *off,
+                            int64_t n_texts) {
+    return restore_lines(c, enc, mode, units, off, n_texts, false, false);
+}
+
+int bpe_restore_lines_batch_device(bpe_ctx *c, bpe_encoder *enc, int mode, const uint16_t *d_units,
+                                   const int64_t *d_off, int64_t n_texts) {
+    return restore_lines(c, enc, mode, d_units, d_off, n_texts, true, false);
+}
+
+int bpe_restore_lines_utf8_batch(bpe_ctx *c, bpe_encoder *enc, int mode, const uint8_t *bytes, const int64_t *off,
+                                 int64_t n_texts) {
+    return restore_lines(c, enc, mode, bytes, off, n_texts, false, true);
+}
+
+int bpe_restore_lines_utf8_batch_device(bpe_ctx *c, bpe_encoder *enc, int mode, const uint8_t *d_bytes,
+                                        const int64_t *d_off, int64_t n_texts) {
+    return restore_lines(c, enc, mode, d_bytes, d_off, n_texts, true, true);
+}
+
+int bpe_get_lines_stats(bpe_ctx *c, bpe_lines_stats *out) {
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    const bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    *out = t->ln ? t->ln->st : bpe_lines_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_lines_stats(bpe_ctx *c) {
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    if (t->ln) t->ln->st = bpe_lines_stats{};
     return BPE_OK;
 }
 

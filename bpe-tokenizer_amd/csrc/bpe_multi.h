@@ -90,6 +90,13 @@ int encoder_device(bpe_encoder *enc, int *device);
 int encoder_utf8_units(bpe_encoder *enc, const uint8_t *bytes, const int64_t *off, int64_t n_texts, bool dev,
                        const uint16_t **d_units, const int64_t **d_uoff, int64_t *n_units);
 void encoder_utf8_done(bpe_encoder *enc);
+// (bpe_encode.hip) the restore from lines: the texts (units, or with utf8 bytes transcoded first)
+// split into samples on the encoder, their units and offsets left in its scratch on its device;
+// encoder_lines_done counts the call in the encoder's counters once the restore has succeeded
+int encoder_lines_units(bpe_encoder *enc, int mode, const void *src, const int64_t *off, int64_t n_texts, bool dev,
+                        bool utf8, const uint16_t **d_units, const int64_t **d_uoff, int64_t *n_samples,
+                        int64_t *n_units);
+void encoder_lines_done(bpe_encoder *enc);
 // (bpe_decode.hip) the same for a decoder (the text export checks it)
 int decoder_device(bpe_decoder *dec, int *device);
 

@@ -28,6 +28,7 @@ export type Markers = {
   end_marker: string
 }
 export declare function fileContentToCorpus(content: string | Buffer): string
+export type CorpusHelperName = 'linesToCorpus' | 'linesTrimmedToCorpus' | 'fileContentToCorpus'
 export declare function linesToCorpus(text: string): string[]
 export declare function linesTrimmedToCorpus(text: string): string[]
 export declare class BPETokenizer {
@@ -93,6 +94,16 @@ export declare class BPETokenizer {
   addToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>): void
   restoreToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>): void
   encodeToVectorBatchUtf8(buffers: Array<Buffer | Uint8Array>): number[][]
+  /**
+   * The corpus helpers on the GPU: every text (file) is split into samples by `helper` (default
+   * 'linesToCorpus') on the device and ingested or restored there; the tokenizer is left exactly as
+   * `texts.flatMap(helper).forEach(s => t.addToCorpus(s))` (or restoreToCorpus) leaves it.  They need
+   * a HIP device; any other helper name throws.
+   */
+  addLinesToCorpusBatch(texts: string[], helper?: CorpusHelperName): void
+  addLinesToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>, helper?: CorpusHelperName): void
+  restoreLinesToCorpusBatch(texts: string[], helper?: CorpusHelperName): void
+  restoreLinesToCorpusBatchUtf8(buffers: Array<Buffer | Uint8Array>, helper?: CorpusHelperName): void
   /**
    * the trained corpus as vectors on the GPU: `encodeToVector` of every training sample (of the samples
    * `indices`, in that order, when given) without encoding the raw text again; throws

@@ -36,6 +36,8 @@ const {
   corpusTextsUtf8OnDevice,
   decodeVectorsUtf8OnDevice,
   loadNativeUtf8,
+  loadNativeLines,
+  linesMode,
   buffersToBytes,
 } = require('./native')
 
@@ -69,6 +71,16 @@ function linesTrimmedToCorpus(text) {
     }
     return '\r' + line + '\n'
   })
+}
+
+/** texts.flatMap(helper) for a BPE_LINES_* mode (Node 12: no need of Array.prototype.flatMap) */
+function helperSamples(texts, mode) {
+  let out = []
+  for (let text of texts) {
+    if (mode === 2) out.push(fileContentToCorpus(text))
+    else for (let s of mode === 0 ? linesToCorpus(text) : linesTrimmedToCorpus(text)) out.push(s)
+  }
+  return out
 }
 
 /** `String.prototype.replaceAll(p, r)` for the single-code-point replacements used here. */
@@ -372,6 +384,38 @@ class BPETokenizer {
     this._addedOnDevice(loadNativeUtf8().addUtf8Batch(engine, bytes, off))
   }
 
+  /**
+   * @description the corpus helpers on the GPU (bpe_add_lines_batch): every text is split into samples
+   * by `helper` ('linesToCorpus', the default, 'linesTrimmedToCorpus' or 'fileContentToCorpus') on the
+   * device and ingested there.  Leaves the tokenizer exactly as
+   * `texts.flatMap(helper).forEach(s => this.addToCorpus(s))` does ('fileContentToCorpus' gives one
+   * sample per text).  An addition to the reference's surface, like addToCorpusBatch.  Needs a HIP
+   * device.
+   */
+  addLinesToCorpusBatch(texts, helper) {
+    let mode = linesMode(helper)
+    if (!texts.every(t => typeof t === 'string')) throw new TypeError('addLinesToCorpusBatch expects strings')
+    if (texts.length === 0) return
+    let engine = this.engine()
+    syncEngineChars(this, engine)
+    let [units, off] = textsToUnits(texts)
+    this._addedOnDevice(loadNativeLines().addLinesBatch(engine, mode, units, off))
+  }
+
+  /**
+   * @description addLinesToCorpusBatch for UTF-8 bytes: an array of Buffer / Uint8Array (files),
+   * decoded on the device exactly as `buffer.toString()` decodes them, then split
+   * (bpe_add_lines_utf8_batch).  Needs a HIP device.
+   */
+  addLinesToCorpusBatchUtf8(buffers, helper) {
+    let mode = linesMode(helper)
+    if (buffers.length === 0) return
+    let engine = this.engine()
+    syncEngineChars(this, engine)
+    let [bytes, off] = buffersToBytes(buffers)
+    this._addedOnDevice(loadNativeLines().addLinesUtf8Batch(engine, mode, bytes, off))
+  }
+
   /** the bookkeeping of core.ts:186-202 for a batch the engine ingested: [new_chars, hist] */
   _addedOnDevice([new_chars, hist]) {
     let { char_to_token, code_to_token, token_table } = this
@@ -440,6 +484,33 @@ class BPETokenizer {
     let engine = this.engine()
     if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, buffers, true)) return
     this.restoreToCorpusBatch(buffers.map(b => Buffer.from(b.buffer, b.byteOffset, b.length).toString()))
+  }
+
+  /**
+   * @description restoreToCorpusBatch behind a corpus helper on the GPU (bpe_restore_lines_batch):
+   * leaves the tokenizer exactly as `this.restoreToCorpusBatch(texts.flatMap(helper))` does, the
+   * errors included; when the device cannot take the call, that is what runs.
+   */
+  restoreLinesToCorpusBatch(texts, helper) {
+    let mode = linesMode(helper)
+    if (!texts.every(t => typeof t === 'string')) throw new TypeError('restoreLinesToCorpusBatch expects strings')
+    if (texts.length === 0) return
+    let engine = this.engine()
+    if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, texts, false, mode)) return
+    this.restoreToCorpusBatch(helperSamples(texts, mode))
+  }
+
+  /**
+   * @description restoreLinesToCorpusBatch for UTF-8 bytes: an array of Buffer / Uint8Array, decoded
+   * on the device as `buffer.toString()` decodes them, then split (bpe_restore_lines_utf8_batch).
+   */
+  restoreLinesToCorpusBatchUtf8(buffers, helper) {
+    let mode = linesMode(helper)
+    if (buffers.length === 0) return
+    let engine = this.engine()
+    if (restoreTextsMaybeOnDevice(this, engine, this.merge_tokens, tokenTriple, buffers, true, mode)) return
+    let texts = buffers.map(b => Buffer.from(b.buffer, b.byteOffset, b.length).toString())
+    this.restoreToCorpusBatch(helperSamples(texts, mode))
   }
 
   /**

@@ -40,6 +40,25 @@ function loadNativeUtf8() {
   return nativeUtf8
 }
 
+// the addon of the corpus helpers on the device (addon/bpe_lines_napi.node: addLinesBatch,
+// addLinesUtf8Batch, restoreLinesBatch, restoreLinesUtf8Batch on an engine handle)
+let nativeLines = null
+function loadNativeLines() {
+  if (!nativeLines) nativeLines = require(path.join(__dirname, '..', 'addon', 'bpe_lines_napi.node'))
+  return nativeLines
+}
+
+// the corpus helpers by name -> BPE_LINES_TRIM, BPE_LINES_KEEP, BPE_LINES_FILE (include/bpe.h)
+const LINES_HELPERS = { linesToCorpus: 0, linesTrimmedToCorpus: 1, fileContentToCorpus: 2 }
+function linesMode(helper) {
+  let name = helper === undefined ? 'linesToCorpus' : helper
+  if (typeof name !== 'string' || !Object.prototype.hasOwnProperty.call(LINES_HELPERS, name))
+    throw new Error(
+      'unknown corpus helper: ' + String(helper) + ' (linesToCorpus, linesTrimmedToCorpus or fileContentToCorpus)',
+    )
+  return LINES_HELPERS[name]
+}
+
 // the addon of the ways out as UTF-8 (addon/bpe_utf8_out_napi.node: decodeUtf8Batch on a decoder
 // handle, exportUtf8 on an engine handle and a decoder handle)
 let nativeUtf8Out = null
@@ -392,8 +411,10 @@ function encodeTextsMaybeOnDevice(owner, list, tripleOf, texts, utf8) {
  * `unknown token, char: "x"` is thrown with its string either way; the batch is atomic, so no text has
  * been added then (the reference's loop would have added the texts before the failing one).
  * utf8: `texts` are Buffers / Uint8Arrays of UTF-8 bytes, decoded on the device (bpe_restore_utf8_batch).
+ * lines (a BPE_LINES_* mode, or undefined): the texts are split into samples by that corpus helper on
+ * the device first (bpe_restore_lines_batch, bpe_restore_lines_utf8_batch).
  */
-function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts, utf8) {
+function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts, utf8, lines) {
   if (ENCODE_DEVICE === '0') return false
   if (
     ENCODE_DEVICE !== '1' &&
@@ -404,10 +425,12 @@ function restoreTextsMaybeOnDevice(owner, engine, list, tripleOf, texts, utf8) {
     let enc = syncTextEncoder(owner, list, tripleOf)
     if (utf8) {
       let [bytes, off] = buffersToBytes(texts)
-      loadNativeUtf8().restoreUtf8Batch(engine, enc, bytes, off)
+      if (lines === undefined) loadNativeUtf8().restoreUtf8Batch(engine, enc, bytes, off)
+      else loadNativeLines().restoreLinesUtf8Batch(engine, enc, lines, bytes, off)
     } else {
       let [units, off] = textsToUnits(texts)
-      loadNativeRestore().restoreTextBatch(engine, enc, units, off)
+      if (lines === undefined) loadNativeRestore().restoreTextBatch(engine, enc, units, off)
+      else loadNativeLines().restoreLinesBatch(engine, enc, lines, units, off)
     }
   } catch (e) {
     let msg = String((e && e.message) || e)
@@ -587,6 +610,8 @@ module.exports = {
   loadNativeRestore,
   loadNativeUtf8,
   loadNativeUtf8Out,
+  loadNativeLines,
+  linesMode,
   buffersToBytes,
   maxLengthArg,
   minWeightArg,

@@ -830,6 +830,91 @@ int bpe_encoder_reset_utf8_stats(bpe_encoder *enc);
 int bpe_get_utf8_stats(bpe_ctx *ctx, bpe_utf8_stats *out);
 int bpe_reset_utf8_stats(bpe_ctx *ctx);
 
+/* ---- lines as samples ----------------------------------------------------------------------------
+ * The corpus helpers (core.ts:35-75) on the device: a batch of texts becomes a batch of samples,
+ * exactly texts.flatMap(helper), so that a file's bytes reach the corpus without a host loop over
+ * chars or lines.
+ *   BPE_LINES_TRIM  linesToCorpus (core.ts:61-64): the text cut at every U+000A; each piece p becomes
+ *                   U+000D + p.trim() + U+000A.  trim() removes, at both ends, the 25 units ECMAScript
+ *                   calls WhiteSpace or LineTerminator: 0009-000D, 0020, 00A0, 1680, 2000-200A, 2028,
+ *                   2029, 202F, 205F, 3000, FEFF (not 001C-001F, 0085, 180E or 200B);
+ *   BPE_LINES_KEEP  linesTrimmedToCorpus (core.ts:67-75): the same cut; from each piece exactly one
+ *                   trailing U+000D is dropped if present, nothing else; the same wrap;
+ *   BPE_LINES_FILE  fileContentToCorpus (core.ts:55-58): one sample per text, U+001C + text + U+0004.
+ * (The reference's doc comments of the two line helpers are swapped relative to their code; this
+ * follows the code.)  A text with m line feeds gives m + 1 samples, the empty text one (CR LF); a
+ * text boundary always ends a line and nothing is trimmed across it.  No cut or trim separates a
+ * surrogate pair: all 25 units are BMP non-surrogates.
+ *
+ * bpe_encoder_split_lines is the split alone, on the encoder's device and stream and in its own
+ * grow-only scratch.  Text k is units[off[k] .. off[k+1]) with bpe_encode_text_batch's offset rules.
+ * Sizing follows bpe_decode_batch: *n_samples (and *needed, the units of all samples, in the
+ * `_device` form) are always written once the arguments are valid; off_cap counts offsets, so
+ * n_samples + 1 suffice; when off_cap or units_cap is too small nothing else is written and
+ * BPE_ERR_ARG comes back (NULL outputs with zero capacities are the sizing call).  units_cap >=
+ * 3 * (off[n_texts] - off[0]) + 2 * n_texts always suffices.  n_samples at or past 0x7FFFFFFF and an
+ * unknown mode give BPE_ERR_ARG.  The `_device` form takes and fills buffers on the encoder's device
+ * (any 2-byte aligned unit pointers), reads the offsets back (8 B per text) and synchronises before
+ * returning.
+ *
+ * bpe_add_lines_batch and bpe_restore_lines_batch are that split (on the context for the ingest, on
+ * the encoder for the restore) followed by bpe_add_text_batch_device / bpe_restore_text_batch_device
+ * on the samples; the `_utf8_` forms run the UTF-8 transcode ("text as UTF-8") in front of the
+ * split.  The context is left exactly as `for (t of texts) for (s of helper(t)) addToCorpus(s)`
+ * leaves it: new_chars and id_hist are the ingest's own, and outputs, error codes, messages and
+ * atomicity are those of the UTF-16 form given the produced samples (a failed call changes
+ * nothing).  Error places (text K, unit I) refer to the produced sample K and its units, markers
+ * included, not to the input text.  A multi-device context splits on its first shard's device,
+ * brings the samples to the host and takes its UTF-16 host form (the restore: on the encoder's
+ * device).  There is no encode-from-lines form: bpe_encoder_split_lines_device followed by
+ * bpe_encode_text_batch_device composes it.
+ *
+ * bpe_lines_stats counts the calls and, for those whose whole pipeline succeeded, their texts,
+ * units in, samples, units out (markers included) and `trimmed`: the units the mode dropped
+ * (whitespace, the line feeds themselves, a CR in KEEP).  The kernels work on
+ * bpe_encode_text_batch's tiles (BPE_TEXT_TILE, BPE_TEXT_SCAN_ROUND; csrc/bpe_lines.hip.h). */
+#define BPE_LINES_TRIM 0
+#define BPE_LINES_KEEP 1
+#define BPE_LINES_FILE 2
+typedef struct {
+    int64_t calls;            /* line-split calls */
+    int64_t texts;            /* texts of the calls that succeeded */
+    int64_t units_in;         /* ... their UTF-16 units */
+    int64_t samples;          /* ... the samples they gave */
+    int64_t units_out;        /* ... the samples' units, markers included */
+    int64_t trimmed;          /* ... the units the mode dropped */
+    double kernel_ms;         /* HIP-event time of the split kernels */
+} bpe_lines_stats;
+int bpe_encoder_split_lines(bpe_encoder *enc, int mode, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                            uint16_t *units_out, int64_t units_cap, int64_t *out_off, int64_t off_cap,
+                            int64_t *n_samples);
+int bpe_encoder_split_lines_device(bpe_encoder *enc, int mode, const uint16_t *d_units, const int64_t *d_off,
+                                   int64_t n_texts, uint16_t *d_units_out, int64_t units_cap, int64_t *d_out_off,
+                                   int64_t off_cap, int64_t *n_samples, int64_t *needed);
+int bpe_add_lines_batch(bpe_ctx *ctx, int mode, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                        uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist, int64_t hist_cap);
+int bpe_add_lines_batch_device(bpe_ctx *ctx, int mode, const uint16_t *d_units, const int64_t *d_off,
+                               int64_t n_texts, uint32_t *new_chars, int64_t new_cap, int64_t *n_new,
+                               int64_t *id_hist, int64_t hist_cap);
+int bpe_add_lines_utf8_batch(bpe_ctx *ctx, int mode, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                             uint32_t *new_chars, int64_t new_cap, int64_t *n_new, int64_t *id_hist,
+                             int64_t hist_cap);
+int bpe_add_lines_utf8_batch_device(bpe_ctx *ctx, int mode, const uint8_t *d_bytes, const int64_t *d_off,
+                                    int64_t n_texts, uint32_t *new_chars, int64_t new_cap, int64_t *n_new,
+                                    int64_t *id_hist, int64_t hist_cap);
+int bpe_restore_lines_batch(bpe_ctx *ctx, bpe_encoder *enc, int mode, const uint16_t *units, const int64_t *off,
+                            int64_t n_texts);
+int bpe_restore_lines_batch_device(bpe_ctx *ctx, bpe_encoder *enc, int mode, const uint16_t *d_units,
+                                   const int64_t *d_off, int64_t n_texts);
+int bpe_restore_lines_utf8_batch(bpe_ctx *ctx, bpe_encoder *enc, int mode, const uint8_t *bytes, const int64_t *off,
+                                 int64_t n_texts);
+int bpe_restore_lines_utf8_batch_device(bpe_ctx *ctx, bpe_encoder *enc, int mode, const uint8_t *d_bytes,
+                                        const int64_t *d_off, int64_t n_texts);
+int bpe_encoder_get_lines_stats(bpe_encoder *enc, bpe_lines_stats *out);
+int bpe_encoder_reset_lines_stats(bpe_encoder *enc);
+int bpe_get_lines_stats(bpe_ctx *ctx, bpe_lines_stats *out);
+int bpe_reset_lines_stats(bpe_ctx *ctx);
+
 /* ---- text out as UTF-8 ---------------------------------------------------------------------------
  * The ways out of the device that end in text (bpe_decode_batch, bpe_export_text_batch) as UTF-8
  * bytes (files, dataset shards, sockets, byte tensors) instead of UTF-16 units: the units are
