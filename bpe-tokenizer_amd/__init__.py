@@ -34,6 +34,7 @@ C_API = [
     'bpe_apply_merge', 'bpe_apply_merges', 'bpe_merge_until', 'bpe_stats_enable', 'bpe_get_stats', 'bpe_reset_stats',
     'bpe_get_stream', 'bpe_synth_latin1', 'bpe_synth_zipf', 'bpe_recount', 'bpe_export_counts',
     'bpe_debug_tables', 'bpe_table_state',
+    'bpe_debug_pix', 'bpe_debug_pix_shard', 'bpe_debug_pix_hook',
     'bpe_digest',
     'bpe_heavy_counts', 'bpe_select_counts', 'bpe_tie_positions', 'bpe_rank_loop_begin',
     'bpe_rank_loop_select', 'bpe_rank_loop_decide', 'bpe_rank_loop_count', 'bpe_rank_loop_end',
@@ -66,6 +67,21 @@ C_API = [
     'bpe_encoder_get_lines_stats', 'bpe_encoder_reset_lines_stats', 'bpe_get_lines_stats', 'bpe_reset_lines_stats',
 ]
 HOT_BINS = 65536
+# bpe_debug_pix (include/bpe_tools.h): the info words in order (BPE_PIX_INFO_*), and the arrays in
+# order with their element types and which info word sizes them
+PIX_INFO_WORDS = 24
+PIX_INFO = ['present', 'n', 'cap', 'nblocks', 'nsuper', 'ml', 'status', 'tie', 'err', 'used', 'used_cap',
+            'pool_top', 'pool_cap', 'n_dblocks', 'n_dsuper', 'next_id', 'merged', 'n_done', 'sharded',
+            'delta_pending', 'pair_slot', 'max_id']
+PIX_ARRAYS = [('tok', np.int32, 'n'), ('nxt', np.uint32, 'n'), ('prv', np.uint32, 'n'),
+              ('keys', np.uint32, 'cap'), ('cnt', np.uint64, 'cap'), ('off', np.uint32, 'cap'),
+              ('len', np.uint32, 'cap'), ('fill', np.uint32, 'cap'), ('bmax', np.uint64, 'nblocks'),
+              ('sbmax', np.uint64, 'nsuper'), ('bdirty', np.uint32, 'nblocks'),
+              ('sbdirty', np.uint32, 'nsuper'), ('pool', np.uint32, 'pool_top'),
+              ('dblocks', np.uint32, 'n_dblocks'), ('dsuper', np.uint32, 'n_dsuper')]
+PIX_HOOK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
+PIX_RUN, PIX_DONE, PIX_HOST, PIX_ERROR, PIX_PAUSE = range(5)          # PixStatus
+PIX_TIE_NONE, PIX_TIE_SCAN, PIX_TIE_DECIDED, PIX_TIE_WAIT = range(4)  # PixTie
 TABLE_BINS = 81920
 DIGEST_MOD = 254    # BPE_DIGEST_MOD: the digest plane's code of a token id t >= 0 is t % DIGEST_MOD
 DIGEST_SEP = 254    # BPE_DIGEST_SEP: ... of a sample separator (-1)
@@ -294,6 +310,9 @@ def lib():
         'bpe_recount': ([vp], ctypes.c_int),
         'bpe_debug_tables': ([vp, vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
         'bpe_table_state': ([vp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        'bpe_debug_pix': ([vp, i64p, vp], ctypes.c_int),
+        'bpe_debug_pix_shard': ([vp, ctypes.c_int, i64p, vp], ctypes.c_int),
+        'bpe_debug_pix_hook': ([vp, PIX_HOOK, vp, ctypes.c_int64], ctypes.c_int),
         'bpe_export_counts': ([vp, vp], ctypes.c_int),
         'bpe_heavy_counts': ([vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
         'bpe_select_counts': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -1225,6 +1244,45 @@ class Engine:
                    'bpe_debug_tables')
         k = min(n.value, cap)
         return hot, keys[:k], counts[:k]
+
+    # the position index of the incremental mode, for checking (include/bpe_tools.h) ----------------
+    def pix_view(self, shard=None):
+        """The live position index copied out (bpe_debug_pix; shard=k: shard k of a multi-device
+        context, bpe_debug_pix_shard): a dict of the PIX_INFO scalars and the PIX_ARRAYS numpy
+        arrays, or None when the context holds no index."""
+        L = lib()
+        info = (ctypes.c_int64 * PIX_INFO_WORDS)()
+
+        def call(arrays):
+            if shard is None:
+                _check(L.bpe_debug_pix(self._ctx, info, arrays), 'bpe_debug_pix')
+            else:
+                _check(L.bpe_debug_pix_shard(self._ctx, int(shard), info, arrays), 'bpe_debug_pix_shard')
+
+        call(None)
+        v = {name: int(info[i]) for i, name in enumerate(PIX_INFO)}
+        if not v['present']:
+            return None
+        sizes = {'n': v['n'], 'cap': v['cap'], 'nblocks': v['nblocks'], 'nsuper': v['nsuper'],
+                 'pool_top': v['pool_top'], 'n_dblocks': v['n_dblocks'], 'n_dsuper': v['n_dsuper']}
+        ptrs = (ctypes.c_void_p * len(PIX_ARRAYS))()
+        for i, (name, dt, size) in enumerate(PIX_ARRAYS):
+            v[name] = np.zeros(max(sizes[size], 1), dt)
+            ptrs[i] = v[name].ctypes.data
+        call(ptrs)
+        for name, _, size in PIX_ARRAYS:
+            v[name] = v[name][:sizes[size]]
+        return v
+
+    def pix_hook(self, fn, batch=0):
+        """fn(where) is called by merge_until in the incremental mode while its index is live
+        (bpe_debug_pix_hook: where 0 before a batch, 1 after one), with `batch` iterations per
+        batch (0: the default).  fn may call pix_view and must not raise: ctypes drops an
+        exception raised in a callback, so a checker records its findings and the caller asserts
+        on them afterwards.  fn=None removes the hook."""
+        cb = PIX_HOOK((lambda user, where: fn(where)) if fn is not None else 0)
+        _check(lib().bpe_debug_pix_hook(self._ctx, cb, None, int(batch)), 'bpe_debug_pix_hook')
+        self._pix_hook = cb   # (kept alive while the library holds it)
 
 
 class Encoder:

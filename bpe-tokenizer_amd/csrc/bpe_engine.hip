@@ -241,6 +241,11 @@ struct bpe_ctx {
     uint32_t pix_lane[3] = {0, 0, 0}, pix_lane_prev[3] = {0, 0, 0};
     int64_t pix_nw_last = 0;   // words the last rank-loop batch all-reduced (its pending merge's)
     bool pix_first_pending = false;
+    // checking (bpe_tools.h bpe_debug_pix_hook): called by pix_merge_until while its index is live,
+    // and the merges per host round trip it then makes (0: PIX_BATCH)
+    void (*pix_hook)(void *user, int where) = nullptr;
+    void *pix_hook_user = nullptr;
+    int64_t pix_dbg_batch = 0;
     // the corpus ingest from text: char table, scratch and counters (made by its first call)
     struct IngestState *ing = nullptr;
     // the corpus append from encoded samples: scratch and counters (made by its first call)
@@ -2080,6 +2085,22 @@ int pix_build(bpe_ctx *c, int64_t max_length) {
     return rc;
 }
 
+// A size knob of the index build and of pix_reserve, read from the environment where the size is
+// used (once per build or reserve): `dflt` when unset or not a positive number, never below `least`.
+static uint64_t pix_knob(const char *name, uint64_t dflt, uint64_t least) {
+    const char *v = getenv(name);
+    const long long x = v ? atoll(v) : 0;
+    return x > 0 ? std::max<uint64_t>((uint64_t)x, least) : dflt;
+}
+// BPE_PIX_TABLE_FLOOR=n (tests): the pair table's least capacity in slots (default 2^20, at least
+// 2^10; the build rounds it up to a power of two), so that a small corpus fills its table and
+// pix_reserve's rehash is reached.
+static uint64_t pix_table_floor() { return pix_knob("BPE_PIX_TABLE_FLOOR", 1u << 20, 1u << 10); }
+// BPE_PIX_POOL_SLACK=n (tests): the floor, in entries, of the pool's room beyond the corpus at the
+// build (default 2^22) and of the free room below which pix_reserve grows it (default 2^20), so
+// that a small corpus reaches the pool's growth.
+static uint64_t pix_pool_slack(uint64_t dflt) { return pix_knob("BPE_PIX_POOL_SLACK", dflt, 1); }
+
 int pix_build_timed(bpe_ctx *c, int64_t max_length) {
     int rc;
     if ((rc = settle(c))) return rc;
@@ -2102,7 +2123,7 @@ int pix_build_timed(bpe_ctx *c, int64_t max_length) {
     digest_stale(c, WRITER_OUTSIDE);   // (the index merges in place in d_ids)
     C.n = N;
     if ((rc = pix_alloc(P, &C.nxt, N)) || (rc = pix_alloc(P, &C.prv, N))) return rc;
-    const uint64_t pool_cap = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)N + std::max<uint64_t>(N / 2, 1u << 22));
+    const uint64_t pool_cap = std::min<uint64_t>(0xFFFFFFF0ull, (uint64_t)N + std::max<uint64_t>(N / 2, pix_pool_slack(1u << 22)));
     PixBufs &B = P->B;
     if ((rc = pix_alloc(P, &B.pool, pool_cap))) return rc;
     const uint32_t nblk = (N + PB - 1) / PB;
@@ -2126,8 +2147,9 @@ int pix_build_timed(bpe_ctx *c, int64_t max_length) {
         return rc;
     // the pair table: room for the current pairs and the ones merges will add (a shard of a
     // sharded corpus: also every pair of the other shards, pix_min_cap)
-    uint64_t cap = 1u << 20;
-    while (cap < (uint64_t)N / 8 || cap < c->pix_min_cap) cap <<= 1;
+    uint64_t cap = 1u << 10;
+    const uint64_t floor_cap = pix_table_floor();
+    while (cap < floor_cap || cap < (uint64_t)N / 8 || cap < c->pix_min_cap) cap <<= 1;
     PixTable &T = P->T;
     for (int attempt = 0;; ++attempt) {
         if (cap >= (1ull << 31)) return PIX_NOT_ELIGIBLE;   // (slot numbers keep PIX_OWNER free)
@@ -2326,10 +2348,12 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
         if (builds && !just_built)
             if ((rc = pix_reserve(c))) return rc;   // (grow the pool / table in place)
         just_built = false;
+        if (c->pix_hook) c->pix_hook(c->pix_hook_user, 0);   // (checking: the index before a batch)
         PixState *P = c->pix;
         hipStream_t s = c->stream;
         const int64_t base = (int64_t)c->h_len16.size();
-        int64_t want = std::min<int64_t>(PIX_BATCH, BPE_MAX_VOCAB - base);
+        const int64_t batch = c->pix_dbg_batch > 0 ? c->pix_dbg_batch : PIX_BATCH;
+        int64_t want = std::min<int64_t>(batch, BPE_MAX_VOCAB - base);
         if (max_iterations) want = std::min<int64_t>(want, max_iterations - n);
         if ((rc = len16_for_batch(c, std::max<int64_t>(want, 1)))) return rc;
         int status = PIX_HOST;
@@ -2368,6 +2392,7 @@ int pix_merge_until(bpe_ctx *c, int64_t max_length, int64_t min_weight, int64_t 
                 put_merge(out_abw, cap, n, a, b, W);
             }
             c->len16_lo = base + nd;   // pix_commit wrote the new lengths on the device
+            if (c->pix_hook) c->pix_hook(c->pix_hook_user, 1);   // (checking: the index after a batch)
             if (status == PIX_DONE) break;
             if (status == PIX_RUN || status == PIX_PAUSE) continue;
             if (c->stats_on) c->stats.pix_host += 1;
@@ -2457,7 +2482,7 @@ int pix_reserve(bpe_ctx *c) {
     HIP_TRY(hipStreamSynchronize(s));
     if (h->status != PIX_RUN && h->status != PIX_PAUSE) return BPE_OK;
     const uint64_t N = P->C.n;
-    const uint64_t slack = std::max<uint64_t>(N / 8, 1u << 20);
+    const uint64_t slack = std::max<uint64_t>(N / 8, pix_pool_slack(1u << 20));
     if (h->pool_top + slack > h->pool_cap && h->pool_cap < 0xFFFFFFF0ull) {
         const uint64_t ncap = std::min<uint64_t>(0xFFFFFFF0ull, h->pool_cap + std::max<uint64_t>(N / 2, 4 * slack));
         uint32_t *np = nullptr;
@@ -2498,6 +2523,10 @@ int pix_reserve(bpe_ctx *c) {
             return BPE_OK;   // (no memory: the table fills, and the batch hands over)
         }
         HIP_TRY(hipMemsetAsync(T.keys, 0xFF, ncap * sizeof(uint32_t), s));
+        // (as in the build: a pair claimed later counts and lists from 0; k_pix_rehash writes only
+        // the slots of the pairs it moves, and fresh device memory is not always zero)
+        HIP_TRY(hipMemsetAsync(T.cnt, 0, ncap * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(T.len, 0, ncap * sizeof(uint32_t), s));
         HIP_TRY(hipMemsetAsync(T.bdirty, 0, T.nblocks * sizeof(uint32_t), s));
         HIP_TRY(hipMemsetAsync(T.sbdirty, 0, T.nsuper * sizeof(uint32_t), s));
         k_pix_rehash<<<4096, 256, 0, s>>>(P->T, T, P->d_ctl, (uint32_t)P->cap);
@@ -3455,6 +3484,14 @@ int bpe_leave_global(bpe_ctx *c) {
     return BPE_OK;
 }
 
+// (internal, bpe_multi.cpp) whether this shard still holds the global state it entered: anything
+// that reads its corpus between two batches makes it leave (settle)
+int bpe_holds_global(bpe_ctx *c, int *yes) {
+    if (!c || c->multi || !yes) return fail(BPE_ERR_ARG, "bpe native: bad shard context");
+    *yes = c->rl_global ? 1 : 0;
+    return BPE_OK;
+}
+
 // (bpe_tools.h; BPE_DEBUG_GLOBAL in bpe_multi.cpp, and the tests) this context's maintained
 // tables: the hot bins (HOT_BINS u64 into hot) and the cold table's dense entries (up to cap;
 // *n = n_used)
@@ -3480,6 +3517,84 @@ int bpe_debug_tables(bpe_ctx *c, uint64_t *hot, uint32_t *keys, uint64_t *counts
         HIP_TRY(hipMemcpy(keys, c->cold.dkeys, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(counts, c->cold.dcounts, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    return BPE_OK;
+}
+
+// (bpe_tools.h) the live position index of a single-device context, copied out
+int bpe_debug_pix(bpe_ctx *c, int64_t *info, void *const *arrays) {
+    if (!c || c->multi || !info) return fail(BPE_ERR_ARG, "bpe native: bad debug_pix arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    PixState *P = c->pix;
+    if (!P || !P->d_ctl) {
+        if (arrays) return fail(BPE_ERR_ARG, "bpe native: debug_pix: no index to copy");
+        for (int i = 0; i < BPE_PIX_INFO_WORDS; ++i) info[i] = 0;
+        return BPE_OK;
+    }
+    PixCtl h;
+    HIP_TRY(hipMemcpy(&h, P->d_ctl, sizeof h, hipMemcpyDeviceToHost));
+    const PixTable &T = P->T;
+    int64_t now[BPE_PIX_INFO_WORDS] = {0};
+    now[0] = 1;
+    now[1] = P->C.n;
+    now[2] = (int64_t)P->cap;
+    now[3] = T.nblocks;
+    now[4] = T.nsuper;
+    now[5] = T.ml;
+    now[6] = h.status;
+    now[7] = h.tie;
+    now[8] = h.err;
+    now[9] = (int64_t)h.used;
+    now[10] = (int64_t)h.used_cap;
+    now[11] = (int64_t)h.pool_top;
+    now[12] = (int64_t)h.pool_cap;
+    now[13] = std::min<uint32_t>(h.n_dblocks, T.nblocks);
+    now[14] = std::min<uint32_t>(h.n_dsuper, T.nsuper);
+    now[15] = h.next_id;
+    now[16] = h.merged;
+    now[17] = h.n_done;
+    now[18] = c->rl_pix ? 1 : 0;
+    now[19] = c->rl_pix && c->rl_delta_pending ? 1 : 0;
+    now[20] = h.pair_slot;
+    now[21] = h.max_id;
+    if (!arrays) {
+        for (int i = 0; i < BPE_PIX_INFO_WORDS; ++i) info[i] = now[i];
+        return BPE_OK;
+    }
+    // (the arrays were sized by the first call: nothing may have changed since)
+    for (int i = 0; i < BPE_PIX_INFO_WORDS; ++i)
+        if (info[i] != now[i]) return fail(BPE_ERR_ARG, "bpe native: debug_pix: the index changed since the sizing call");
+    for (int i = 0; i < BPE_PIX_ARRAYS; ++i)
+        if (!arrays[i]) return fail(BPE_ERR_ARG, "bpe native: bad debug_pix arguments");
+    const size_t n = P->C.n, cap = (size_t)P->cap;
+    const size_t top = (size_t)std::min<unsigned long long>(h.pool_top, h.pool_cap);
+    const struct { const void *src; size_t bytes; } cp[BPE_PIX_ARRAYS] = {
+        {P->C.tok, n * sizeof(int32_t)},       {P->C.nxt, n * sizeof(uint32_t)},
+        {P->C.prv, n * sizeof(uint32_t)},      {T.keys, cap * sizeof(uint32_t)},
+        {T.cnt, cap * sizeof(uint64_t)},       {T.off, cap * sizeof(uint32_t)},
+        {T.len, cap * sizeof(uint32_t)},       {T.fill, cap * sizeof(uint32_t)},
+        {T.bmax, T.nblocks * sizeof(uint64_t)}, {T.sbmax, T.nsuper * sizeof(uint64_t)},
+        {T.bdirty, T.nblocks * sizeof(uint32_t)}, {T.sbdirty, T.nsuper * sizeof(uint32_t)},
+        {P->B.pool, top * sizeof(uint32_t)},   {P->B.dblocks, (size_t)now[13] * sizeof(uint32_t)},
+        {P->B.dsuper, (size_t)now[14] * sizeof(uint32_t)},
+    };
+    for (int i = 0; i < BPE_PIX_ARRAYS; ++i)
+        if (cp[i].bytes) HIP_TRY(hipMemcpy(arrays[i], cp[i].src, cp[i].bytes, hipMemcpyDeviceToHost));
+    return BPE_OK;
+}
+
+int bpe_debug_pix_shard(bpe_ctx *c, int shard, int64_t *info, void *const *arrays) {
+    if (!c || !c->multi || !info) return fail(BPE_ERR_ARG, "bpe native: bad debug_pix_shard arguments");
+    return multi_debug_pix_shard(c->multi, shard, info, arrays);
+}
+
+int bpe_debug_pix_hook(bpe_ctx *c, void (*hook)(void *user, int where), void *user, int64_t batch) {
+    if (!c || c->multi || batch < 0 || batch > PIX_BATCH)
+        return fail(BPE_ERR_ARG, "bpe native: bad debug_pix_hook arguments");
+    c->pix_hook = hook;
+    c->pix_hook_user = user;
+    c->pix_dbg_batch = batch;
     return BPE_OK;
 }
 

@@ -36,6 +36,7 @@
 #include <vector>
 
 extern "C" int bpe_leave_global(bpe_ctx *c);
+extern "C" int bpe_holds_global(bpe_ctx *c, int *yes);
 
 namespace {
 
@@ -444,6 +445,13 @@ int multi_destroy(bpe_multi *m) {
 int multi_shard_count(bpe_multi *m, int *n) {
     *n = m->n;
     return BPE_OK;
+}
+
+// (checking, bpe_tools.h: the shards' indices are compared with a recount by the tests; the
+// BPE_DEBUG_GLOBAL comparison of the shards' tables does not cover them)
+int multi_debug_pix_shard(bpe_multi *m, int shard, int64_t *info, void *const *arrays) {
+    if (shard < 0 || shard >= m->n) return bpe_fail(BPE_ERR_ARG, "bpe native: bad shard index");
+    return bpe_debug_pix(m->sh[shard], info, arrays);
 }
 
 bpe_ctx *multi_first_shard(bpe_multi *m) { return m->sh[0]; }
@@ -1280,6 +1288,19 @@ int multi_merge_until(bpe_multi *m, int64_t max_length, int64_t min_weight,
             // (the incremental mode enters its global state, the shards' position indexes, at
             // once; the streaming mode when the cold pairs outgrow the sketch)
             const bool pix = m->pix && !m->pix_off;
+            if (m->maintained && pix) {
+                // A read of the corpus between two calls (its size, its samples) made the shards
+                // it touched drop their indices (settle), unseen from here: the batch would run on
+                // the streaming rank loop from then on, and with some shards only, the shards
+                // would disagree on the exchange.  All leave alike, and this batch builds again.
+                bool all = true;
+                for (auto s : m->sh) {
+                    int yes = 0;
+                    MTRY(bpe_holds_global(s, &yes));
+                    all = all && yes;
+                }
+                if (!all) MTRY(drop_global(m));
+            }
             if (!m->maintained && (m->heavy_streak >= 2 || pix)) {
                 // (more than 64 entries since the mode was set, at least one per 16 merges made:
                 // the index keeps handing over here, and the stream goes on)

@@ -55,6 +55,8 @@ int multi_get_stats(bpe_multi *m, bpe_stats *out);
 int multi_reset_stats(bpe_multi *m);
 int multi_get_stream(bpe_multi *m, void **stream);
 int multi_shard_count(bpe_multi *m, int *n);
+// (bpe_tools.h bpe_debug_pix_shard) the position index of one shard, for checking
+int multi_debug_pix_shard(bpe_multi *m, int shard, int64_t *info, void *const *arrays);
 // the shard whose device and stream a multi-device context's UTF-8 ingest transcodes on
 bpe_ctx *multi_first_shard(bpe_multi *m);
 // explicit_choice: the caller's bpe_set_mode (false: the automatic switch past AUTO_PIX_VOCAB ids)

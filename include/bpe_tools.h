@@ -43,6 +43,48 @@ int bpe_debug_tables(struct bpe_ctx *ctx, uint64_t *hot, uint32_t *keys, uint64_
  * BPE_ERR_ARG for a multi-device context and for null arguments. */
 int bpe_table_state(struct bpe_ctx *ctx, int *maintained);
 
+/* The live position index of the incremental mode (csrc/bpe_pix.hip.h), copied out for checking.
+ * Two calls, like bpe_debug_tables: with arrays == NULL the sizes and scalars into info
+ * (BPE_PIX_INFO_WORDS int64 words, BPE_PIX_INFO_* below; info[BPE_PIX_INFO_PRESENT] = 0 and the
+ * rest zero when the context holds no index), then with the same info and BPE_PIX_ARRAYS host
+ * pointers, in this order and of these element counts:
+ *   tok (int32, n)  nxt, prv (uint32, n)                          the slot array and its links
+ *   keys (uint32, cap)  cnt (uint64, cap)  off, len, fill (uint32, cap)   the pair table
+ *   bmax (uint64, nblocks)  sbmax (uint64, nsuper)  bdirty (uint32, nblocks)  sbdirty (uint32, nsuper)
+ *   pool (uint32, pool_top)  dblocks (uint32, n_dblocks)  dsuper (uint32, n_dsuper)
+ * The second call fails with BPE_ERR_ARG when the index is gone or no longer has the sizes and
+ * scalars of info.  The call synchronises the context's stream and launches nothing.  BPE_ERR_ARG
+ * for null arguments and for a multi-device context.  In a single context the index lives only
+ * inside bpe_merge_until: see bpe_debug_pix_hook. */
+enum {
+    BPE_PIX_INFO_PRESENT = 0, BPE_PIX_INFO_N = 1, BPE_PIX_INFO_CAP = 2, BPE_PIX_INFO_NBLOCKS = 3,
+    BPE_PIX_INFO_NSUPER = 4, BPE_PIX_INFO_ML = 5, BPE_PIX_INFO_STATUS = 6, BPE_PIX_INFO_TIE = 7,
+    BPE_PIX_INFO_ERR = 8, BPE_PIX_INFO_USED = 9, BPE_PIX_INFO_USED_CAP = 10,
+    BPE_PIX_INFO_POOL_TOP = 11, BPE_PIX_INFO_POOL_CAP = 12, BPE_PIX_INFO_N_DBLOCKS = 13,
+    BPE_PIX_INFO_N_DSUPER = 14, BPE_PIX_INFO_NEXT_ID = 15, BPE_PIX_INFO_MERGED = 16,
+    BPE_PIX_INFO_N_DONE = 17,
+    BPE_PIX_INFO_SHARDED = 18,        /* a shard's index: cnt holds the global counts */
+    BPE_PIX_INFO_DELTA_PENDING = 19,  /* ... whose last merge's delta rows are not added yet */
+    BPE_PIX_INFO_PAIR_SLOT = 20, BPE_PIX_INFO_MAX_ID = 21,
+    BPE_PIX_INFO_WORDS = 24, BPE_PIX_ARRAYS = 15
+};
+int bpe_debug_pix(struct bpe_ctx *ctx, int64_t *info, void *const *arrays);
+
+/* The same for shard `shard` of a multi-device context, whose shards keep their indices between
+ * the batches and the calls of bpe_merge_until in the incremental mode, until something reads or
+ * changes the corpus.  BPE_ERR_ARG for a single-device context, a bad shard and null arguments. */
+int bpe_debug_pix_shard(struct bpe_ctx *ctx, int shard, int64_t *info, void *const *arrays);
+
+/* Checking a single context's index while it lives: bpe_merge_until in the incremental mode calls
+ * hook(user, 0) after an index build or after the room for the next batch was reserved (the pool
+ * grown, the table rehashed), before the batch starts, and hook(user, 1) after a batch's host
+ * synchronisation and merge accounting; the hook may call bpe_debug_pix and must change nothing.
+ * batch (1 to 256; 0: the default, 256) is the number of iterations per batch for this context:
+ * with 1 the index is seen after every merge, and between a tie's scan and its commit.
+ * hook == NULL removes the hook.  BPE_ERR_ARG for a multi-device context and a bad batch. */
+int bpe_debug_pix_hook(struct bpe_ctx *ctx, void (*hook)(void *user, int where), void *user,
+                       int64_t batch);
+
 #ifdef __cplusplus
 }
 #endif

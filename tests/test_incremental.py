@@ -2,7 +2,9 @@
 position index, O(W) work per merge.  The same merges and corpus as the reference's full recount
 are required: against the oracle, against the streaming mode on corpora the oracle cannot finish,
 and across the hand-offs between the index and the stream.  (The randomized, golden, tie, run and
-compaction tests of test_gpu_parity.py run in this mode too: MODES includes 'pix'.)"""
+compaction tests of test_gpu_parity.py run in this mode too: MODES includes 'pix'.)  What the
+index keeps between the merges (counts, lists, links, maxima) is checked against a recount in
+test_index_state.py."""
 import random
 
 import numpy as np
