@@ -33,7 +33,7 @@ C_API = [
     'bpe_read_samples', 'bpe_find_next_merge',
     'bpe_apply_merge', 'bpe_apply_merges', 'bpe_merge_until', 'bpe_stats_enable', 'bpe_get_stats', 'bpe_reset_stats',
     'bpe_get_stream', 'bpe_synth_latin1', 'bpe_synth_zipf', 'bpe_recount', 'bpe_export_counts',
-    'bpe_debug_tables', 'bpe_table_state',
+    'bpe_debug_tables', 'bpe_table_state', 'bpe_debug_tables_shard', 'bpe_debug_global',
     'bpe_debug_pix', 'bpe_debug_pix_shard', 'bpe_debug_pix_hook',
     'bpe_digest',
     'bpe_heavy_counts', 'bpe_select_counts', 'bpe_tie_positions', 'bpe_rank_loop_begin',
@@ -67,6 +67,8 @@ C_API = [
     'bpe_encoder_get_lines_stats', 'bpe_encoder_reset_lines_stats', 'bpe_get_lines_stats', 'bpe_reset_lines_stats',
 ]
 HOT_BINS = 65536
+# bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
+GLOBAL_INFO = ['held', 'pending', 'a', 'b', 'c', 'w', 'multi_maintained', 'xchg_words']
 # bpe_debug_pix (include/bpe_tools.h): the info words in order (BPE_PIX_INFO_*), and the arrays in
 # order with their element types and which info word sizes them
 PIX_INFO_WORDS = 24
@@ -310,6 +312,8 @@ def lib():
         'bpe_recount': ([vp], ctypes.c_int),
         'bpe_debug_tables': ([vp, vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
         'bpe_table_state': ([vp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        'bpe_debug_tables_shard': ([vp, ctypes.c_int, vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_debug_global': ([vp, ctypes.c_int, i64p, vp, ctypes.c_int64], ctypes.c_int),
         'bpe_debug_pix': ([vp, i64p, vp], ctypes.c_int),
         'bpe_debug_pix_shard': ([vp, ctypes.c_int, i64p, vp], ctypes.c_int),
         'bpe_debug_pix_hook': ([vp, PIX_HOOK, vp, ctypes.c_int64], ctypes.c_int),
@@ -1227,23 +1231,49 @@ class Engine:
         _check(lib().bpe_table_state(self._ctx, ctypes.byref(m)), 'bpe_table_state')
         return bool(m.value)
 
-    def maintained_tables(self):
+    def maintained_tables(self, shard=None):
         """(hot, keys, counts): the HOT_BINS u64 hot bins (pair (a, b) at b * 256 + a) and the
         cold table's dense entries (key a << 16 | b as uint32, count as uint64; bpe_debug_tables:
-        the sizing call, then the real one)."""
+        the sizing call, then the real one).  shard=k: the copy of the global tables that shard k
+        of a multi-device context holds (bpe_debug_tables_shard)."""
+        L = lib()
         hot = np.zeros(HOT_BINS, np.uint64)
         n = ctypes.c_int64()
-        _check(lib().bpe_debug_tables(self._ctx, hot.ctypes.data, None, None, 0, ctypes.byref(n)),
-               'bpe_debug_tables')
+
+        def call(keys, counts, cap):
+            if shard is None:
+                _check(L.bpe_debug_tables(self._ctx, hot.ctypes.data, keys, counts, cap, ctypes.byref(n)),
+                       'bpe_debug_tables')
+            else:
+                _check(L.bpe_debug_tables_shard(self._ctx, int(shard), hot.ctypes.data, keys, counts, cap,
+                                                ctypes.byref(n)), 'bpe_debug_tables_shard')
+
+        call(None, None, 0)
         keys = np.zeros(max(n.value, 1), np.uint32)
         counts = np.zeros(max(n.value, 1), np.uint64)
         cap = n.value
         if cap:
-            _check(lib().bpe_debug_tables(self._ctx, hot.ctypes.data, keys.ctypes.data,
-                                          counts.ctypes.data, cap, ctypes.byref(n)),
-                   'bpe_debug_tables')
+            call(keys.ctypes.data, counts.ctypes.data, cap)
         k = min(n.value, cap)
         return hot, keys[:k], counts[:k]
+
+    def global_state(self, shard=None):
+        """(state, xchg) of bpe_debug_global: what this context (a single context used as one rank)
+        or shard `shard` of a multi-device context holds of the streaming mode's sharded
+        maintained state, as a dict of the GLOBAL_INFO words with 'held' and 'pending' as bools,
+        and a copy of the exchange buffer it last began a batch with (uint64, XCHG_WORDS words
+        while the state is held, else empty)."""
+        L = lib()
+        info = (ctypes.c_int64 * len(GLOBAL_INFO))()
+        sh = -1 if shard is None else int(shard)
+        _check(L.bpe_debug_global(self._ctx, sh, info, None, 0), 'bpe_debug_global')
+        words = int(info[GLOBAL_INFO.index('xchg_words')])
+        xchg = np.zeros(max(words, 1), np.uint64)
+        if words:
+            _check(L.bpe_debug_global(self._ctx, sh, info, xchg.ctypes.data, words), 'bpe_debug_global')
+        state = {name: int(info[i]) for i, name in enumerate(GLOBAL_INFO)}
+        state['held'], state['pending'] = bool(state['held']), bool(state['pending'])
+        return state, xchg[:min(words, state['xchg_words'])]
 
     # the position index of the incremental mode, for checking (include/bpe_tools.h) ----------------
     def pix_view(self, shard=None):

@@ -1840,6 +1840,7 @@ int set_global_counts(bpe_ctx *c, const unsigned long long *table, const uint32_
     }
     c->rl_global = true;
     c->rl_delta_pending = false;
+    c->rl_table = nullptr;   // (no batch of this state was begun yet: bpe_debug_global reads none)
     c->counts_valid = true;
     c->sketch_valid = false;
     c->cold_exact = false;   // (the single-context maintained state is not this one)
@@ -3517,6 +3518,41 @@ int bpe_debug_tables(bpe_ctx *c, uint64_t *hot, uint32_t *keys, uint64_t *counts
         HIP_TRY(hipMemcpy(keys, c->cold.dkeys, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(counts, c->cold.dcounts, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    return BPE_OK;
+}
+
+int bpe_debug_tables_shard(bpe_ctx *c, int shard, uint64_t *hot, uint32_t *keys, uint64_t *counts,
+                           int64_t cap, int64_t *n) {
+    if (!c || !c->multi || !hot || !n || cap < 0 || (cap > 0 && (!keys || !counts)))
+        return fail(BPE_ERR_ARG, "bpe native: bad debug_tables_shard arguments");
+    return multi_debug_tables_shard(c->multi, shard, hot, keys, counts, cap, n);
+}
+
+// (bpe_tools.h) what this context holds of the sharded maintained state of the streaming mode,
+// and the exchange buffer it last began a batch with, copied out; nothing is launched or changed
+int bpe_debug_global(bpe_ctx *c, int shard, int64_t *info, uint64_t *xchg, int64_t cap) {
+    if (!c || !info || cap < 0 || (cap > 0 && !xchg) || (!c->multi && shard != -1))
+        return fail(BPE_ERR_ARG, "bpe native: bad debug_global arguments");
+    if (c->multi) return multi_debug_global(c->multi, shard, info, xchg, cap);
+    int rc = set_device(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const bool held = c->rl_global && !c->rl_pix;
+    const bool pending = held && c->rl_delta_pending;
+    // (the buffer is the caller's: it is read only while the state that was begun with it is held)
+    const int64_t words = held && c->rl_table ? (int64_t)XCHG_WORDS : 0;
+    for (int i = 0; i < BPE_GLOBAL_INFO_WORDS; ++i) info[i] = 0;
+    info[BPE_GLOBAL_INFO_HELD] = held ? 1 : 0;
+    info[BPE_GLOBAL_INFO_PENDING] = pending ? 1 : 0;
+    info[BPE_GLOBAL_INFO_A] = pending ? c->rl_last_a : -1;
+    info[BPE_GLOBAL_INFO_B] = pending ? c->rl_last_b : -1;
+    info[BPE_GLOBAL_INFO_C] = pending ? c->rl_last_c : -1;
+    info[BPE_GLOBAL_INFO_W] = pending ? c->rl_last_w : -1;
+    info[BPE_GLOBAL_INFO_MULTI] = -1;
+    info[BPE_GLOBAL_INFO_XCHG] = words;
+    if (cap == 0 || words == 0) return BPE_OK;
+    if (cap < words) return fail(BPE_ERR_ARG, "bpe native: debug_global: the buffer is smaller than the sizing call said");
+    HIP_TRY(hipMemcpy(xchg, c->rl_table, (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return BPE_OK;
 }
 

@@ -454,6 +454,21 @@ int multi_debug_pix_shard(bpe_multi *m, int shard, int64_t *info, void *const *a
     return bpe_debug_pix(m->sh[shard], info, arrays);
 }
 
+// (checking, bpe_tools.h: a shard's copy of the global tables of the streaming mode's maintained
+// state, and what it holds of that state; compared with a recount by the tests)
+int multi_debug_tables_shard(bpe_multi *m, int shard, uint64_t *hot, uint32_t *keys,
+                             uint64_t *counts, int64_t cap, int64_t *n) {
+    if (shard < 0 || shard >= m->n) return bpe_fail(BPE_ERR_ARG, "bpe native: bad shard index");
+    return bpe_debug_tables(m->sh[shard], hot, keys, counts, cap, n);
+}
+
+int multi_debug_global(bpe_multi *m, int shard, int64_t *info, uint64_t *xchg, int64_t cap) {
+    if (shard < 0 || shard >= m->n) return bpe_fail(BPE_ERR_ARG, "bpe native: bad shard index");
+    MTRY(bpe_debug_global(m->sh[shard], -1, info, xchg, cap));
+    info[BPE_GLOBAL_INFO_MULTI] = m->maintained ? 1 : 0;
+    return BPE_OK;
+}
+
 bpe_ctx *multi_first_shard(bpe_multi *m) { return m->sh[0]; }
 
 int multi_set_mode(bpe_multi *m, int mode, bool explicit_choice) {
@@ -1054,8 +1069,10 @@ int find_next_merge_host(bpe_multi *m, int64_t max_length, int64_t min_weight, i
         int64_t nc = 0;
         int rc = bpe_heavy_counts(m->sh[r], (uint64_t *)m->d_table[r], max_length, m->d_keys[r],
                                   (uint64_t *)m->d_counts[r], m->cold_cap, &nc);
-        if (rc < 0 && nc > m->cold_cap) {
-            MTRY(ensure_cold_bufs(m, nc));
+        // (the list's length counts the claims that lost a race too, holes, so the pass again may
+        // list a few more than the pass that sized the buffers: room to spare, and again if needed)
+        for (int attempt = 0; rc < 0 && nc > m->cold_cap && attempt < 3; ++attempt) {
+            MTRY(ensure_cold_bufs(m, nc + nc / 8 + 1024));
             rc = bpe_heavy_counts(m->sh[r], (uint64_t *)m->d_table[r], max_length, m->d_keys[r],
                                   (uint64_t *)m->d_counts[r], m->cold_cap, &nc);
         }

@@ -57,6 +57,11 @@ int multi_get_stream(bpe_multi *m, void **stream);
 int multi_shard_count(bpe_multi *m, int *n);
 // (bpe_tools.h bpe_debug_pix_shard) the position index of one shard, for checking
 int multi_debug_pix_shard(bpe_multi *m, int shard, int64_t *info, void *const *arrays);
+// (bpe_tools.h bpe_debug_tables_shard, bpe_debug_global) one shard's copy of the global tables and
+// what it holds of the streaming mode's maintained state, for checking
+int multi_debug_tables_shard(bpe_multi *m, int shard, uint64_t *hot, uint32_t *keys,
+                             uint64_t *counts, int64_t cap, int64_t *n);
+int multi_debug_global(bpe_multi *m, int shard, int64_t *info, uint64_t *xchg, int64_t cap);
 // the shard whose device and stream a multi-device context's UTF-8 ingest transcodes on
 bpe_ctx *multi_first_shard(bpe_multi *m);
 // explicit_choice: the caller's bpe_set_mode (false: the automatic switch past AUTO_PIX_VOCAB ids)

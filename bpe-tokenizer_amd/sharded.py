@@ -102,12 +102,18 @@ class GpuShard:
                                      self.cap, max_length)
         if n < 0:
             return None   # no heavy bucket anywhere (same decision on every rank)
-        if n > self.cap:
-            self.cap = 1 << max(16, int(n - 1).bit_length())
+        for _ in range(3):
+            # (n counts the claims that lost a race too: the pass again may list a few more)
+            if n <= self.cap:
+                break
+            self.cap = 1 << max(16, int(n + n // 8).bit_length())
             self.keys = torch.zeros(self.cap, dtype=torch.int32, device=self.device)
             self.counts = torch.zeros(self.cap, dtype=torch.int64, device=self.device)
             n = self.engine.heavy_counts(table.data_ptr(), self.keys.data_ptr(),
                                          self.counts.data_ptr(), self.cap, max_length)
+        if n > self.cap:
+            raise RuntimeError('bpe sharded: the heavy cold list (%d) outgrew its buffers (%d) three times'
+                               % (n, self.cap))
         return self.keys[:n], self.counts[:n]
 
     def select(self, table, keys, counts, max_length, min_weight):

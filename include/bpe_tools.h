@@ -43,6 +43,41 @@ int bpe_debug_tables(struct bpe_ctx *ctx, uint64_t *hot, uint32_t *keys, uint64_
  * BPE_ERR_ARG for a multi-device context and for null arguments. */
 int bpe_table_state(struct bpe_ctx *ctx, int *maintained);
 
+/* bpe_debug_tables for shard `shard` of a multi-device context: that shard's own copy of the
+ * tables (in the streaming mode's sharded maintained state every shard holds a copy of the global
+ * tables; what they hold between two batches is bpe_debug_global's matter).  The same two calls.
+ * The call synchronises the shard's stream, launches nothing and changes nothing.  BPE_ERR_ARG for
+ * a single-device context, a bad shard and null arguments. */
+int bpe_debug_tables_shard(struct bpe_ctx *ctx, int shard, uint64_t *hot, uint32_t *keys,
+                           uint64_t *counts, int64_t cap, int64_t *n);
+
+/* What a context holds of the sharded maintained state of the streaming mode (the "global state":
+ * bpe_set_global_counts, then the rank loop keeps the tables with delta rows), for shard `shard` of
+ * a multi-device context or, with shard == -1, for a single-device context used as one rank
+ * (bpe_rank_loop_*).  info receives BPE_GLOBAL_INFO_WORDS int64 words:
+ *   HELD      1 while the context holds the global tables of the streaming mode, else 0 (the
+ *             incremental mode's global state, a shard's position index, is bpe_debug_pix's)
+ *   PENDING   1 while the last batch's last merge is applied to the corpus and zeroed in the tables
+ *             (every pair with a side a or b), but its recount, this shard's delta rows, still
+ *             waits in the exchange buffer for the next batch's first all-reduce
+ *   A B C W   that merge (a, b) -> c and its weight; -1 each when none is pending
+ *   MULTI     the multi-device context's own flag that its batches run in the maintained state
+ *             (either mode); -1 for a single-device context
+ *   XCHG      the words of the exchange buffer that can be copied: BPE_XCHG_WORDS while HELD and a
+ *             batch was begun, else 0
+ * and xchg a copy of the exchange buffer the context last began a batch with, word for word
+ * (include/bpe.h BPE_XCHG_*: word 0 this shard's replacement count of the pending merge, the delta
+ * rows from BPE_XCHG_HDR on).  Two calls, like bpe_debug_tables: cap 0 (xchg may be null) for
+ * info, then with cap >= info[XCHG].  The call synchronises the context's stream, launches nothing
+ * and changes nothing.  BPE_ERR_ARG for null arguments, a bad shard, a shard other than -1 with a
+ * single-device context, and a cap between 1 and info[XCHG] - 1. */
+enum {
+    BPE_GLOBAL_INFO_HELD = 0, BPE_GLOBAL_INFO_PENDING = 1, BPE_GLOBAL_INFO_A = 2,
+    BPE_GLOBAL_INFO_B = 3, BPE_GLOBAL_INFO_C = 4, BPE_GLOBAL_INFO_W = 5, BPE_GLOBAL_INFO_MULTI = 6,
+    BPE_GLOBAL_INFO_XCHG = 7, BPE_GLOBAL_INFO_WORDS = 8
+};
+int bpe_debug_global(struct bpe_ctx *ctx, int shard, int64_t *info, uint64_t *xchg, int64_t cap);
+
 /* The live position index of the incremental mode (csrc/bpe_pix.hip.h), copied out for checking.
  * Two calls, like bpe_debug_tables: with arrays == NULL the sizes and scalars into info
  * (BPE_PIX_INFO_WORDS int64 words, BPE_PIX_INFO_* below; info[BPE_PIX_INFO_PRESENT] = 0 and the

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 def worker(rank, world, port, q, mode='step', n=60, max_length=0, seed=777, A=40, base=60,
            mib=3, corpus='uniform', backend='gloo', engine_mode='stream', rank_loop='native',
-           env=None):
+           env=None, views=False):
     import importlib
     import sys
     os.environ['BPE_RANK_LOOP'] = rank_loop
@@ -45,11 +45,14 @@ def worker(rank, world, port, q, mode='step', n=60, max_length=0, seed=777, A=40
                     break
         else:
             tr.run(n, max_length, 2)     # the device-resident rank loop
+        # (views: this rank's copy of the global tables and its exchange buffer, before anything
+        # reads the corpus: test_global_state.check_global in the parent)
+        view = (tr.engine.maintained_tables(), tr.engine.global_state()) if views else None
         ids, off = tr.engine.read_corpus()
         if mode != 'step':
             assert tr._native == native, (tr._native, native)   # (the path asked for ran)
         st = dict(tr.engine.stats(), trainer_pix_fallbacks=tr.pix_fallbacks)
-        q.put((rank, tr.merges, ids.tolist(), off.tolist(), st))
+        q.put((rank, tr.merges, ids.tolist(), off.tolist(), st, view))
     finally:
         dist.destroy_process_group()
 
@@ -82,17 +85,27 @@ def single_engine(world, n=60, max_length=0, seed=777, A=40, base=60, mib=3, cor
     e = pkg.Engine(0)
     e.add_latin1(data, sample_bytes=1 << 20)
     want = e.merge_until(max_length, 2, n)
-    ids, _ = e.read_corpus()
+    ids, off = e.read_corpus()
+    tokens = e.num_tokens()
     e.close()
-    return want, ids.tolist()
+    return want, ids.tolist(), off, tokens
 
 
 def check(world, **kw):
     res = run_ranks(world, **kw)
-    want, ids = single_engine(world, **kw)
+    want, ids, off, tokens = single_engine(world, **kw)
     for r in range(world):
         assert [tuple(m) for m in res[r][0]] == want, 'rank %d merges' % r
     assert sum((res[r][1] for r in range(world)), []) == ids
+    if kw.get('views'):
+        # every rank's copy of the global state against a recount of the single engine's corpus
+        from test_global_state import check_global
+        from test_maintained_state import pair_count_arrays
+        views = [dict(zip(('hot', 'keys', 'counts'), res[r][4][0]), state=res[r][4][1][0], xchg=res[r][4][1][1])
+                 for r in range(world)]
+        assert all(v['state']['held'] and v['state']['pending'] for v in views), [v['state'] for v in views]
+        a, b, W = want[-1]
+        check_global(views, *pair_count_arrays(np.array(ids), off), (a, b, tokens - 1, W))
     return [res[r][3] for r in range(world)]
 
 
@@ -115,8 +128,10 @@ def test_rank_loop_maintained_state_on_zipf_words():
     """A skewed corpus (Zipf words): the cold pairs outgrow the sketch, so the ranks move to the
     maintained state (every rank holds the global tables; each merge exchanges only the delta
     rows of the pairs it touched, bpe_set_global_counts) and stay there: most merges in that
-    state, few host iterations, the same merges and corpus as one engine."""
-    st = check(2, mode='loop', n=700, corpus='zipf', mib=4, seed=12345)
+    state, few host iterations, the same merges and corpus as one engine; and at the end the two
+    ranks' tables and pending delta rows equal a recount of that corpus
+    (test_global_state.check_global)."""
+    st = check(2, mode='loop', n=700, corpus='zipf', mib=4, seed=12345, views=True)
     for s in st:
         assert s['fused_passes'] > 300, s
         assert s['loop_host'] <= 12, s
