@@ -65,6 +65,10 @@ C_API = [
     'bpe_add_lines_utf8_batch', 'bpe_add_lines_utf8_batch_device', 'bpe_restore_lines_batch',
     'bpe_restore_lines_batch_device', 'bpe_restore_lines_utf8_batch', 'bpe_restore_lines_utf8_batch_device',
     'bpe_encoder_get_lines_stats', 'bpe_encoder_reset_lines_stats', 'bpe_get_lines_stats', 'bpe_reset_lines_stats',
+    'bpe_encoder_skipgram', 'bpe_encoder_skipgram_device', 'bpe_skipgram_text_batch', 'bpe_skipgram_text_batch_device',
+    'bpe_skipgram_utf8_batch', 'bpe_skipgram_utf8_batch_device', 'bpe_export_skipgram', 'bpe_export_skipgram_device',
+    'bpe_encoder_get_skipgram_stats', 'bpe_encoder_reset_skipgram_stats', 'bpe_get_skipgram_stats',
+    'bpe_reset_skipgram_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -122,6 +126,9 @@ UTF16_TILE = 2048   # BPE_UTF16_TILE: units per workgroup of the transcode to UT
 LINES_TRIM = 0      # BPE_LINES_TRIM: linesToCorpus (cut at LF, trim(), wrapped in CR .. LF)
 LINES_KEEP = 1      # BPE_LINES_KEEP: linesTrimmedToCorpus (cut at LF, one trailing CR dropped, the same wrap)
 LINES_FILE = 2      # BPE_LINES_FILE: fileContentToCorpus (U+001C + text + U+0004)
+SKIPGRAM_MAX_WINDOW = 64    # BPE_SKIPGRAM_MAX_WINDOW: the widest window of the skip-gram expansion
+SKIPGRAM_TILE = 2048        # BPE_SKIPGRAM_TILE: pairs per workgroup of the expand kernel
+SKIPGRAM_SCAN_ROUND = 8192  # BPE_SKIPGRAM_SCAN_ROUND: texts per round of the scan of the pair counts
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
@@ -253,6 +260,15 @@ class LinesStats(ctypes.Structure):
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('units_in', ctypes.c_int64),
                 ('samples', ctypes.c_int64), ('units_out', ctypes.c_int64), ('trimmed', ctypes.c_int64),
                 ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramStats(ctypes.Structure):
+    """bpe_skipgram_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
+                ('pairs_out', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -440,6 +456,26 @@ def lib():
         'bpe_encoder_reset_lines_stats': ([vp], ctypes.c_int),
         'bpe_get_lines_stats': ([vp, ctypes.POINTER(LinesStats)], ctypes.c_int),
         'bpe_reset_lines_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_skipgram': ([vp, vp, i64p, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, i64p],
+                                 ctypes.c_int),
+        'bpe_encoder_skipgram_device': ([vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp, i64p],
+                                        ctypes.c_int),
+        'bpe_skipgram_text_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64,
+                                     i64p], ctypes.c_int),
+        'bpe_skipgram_text_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp,
+                                            ctypes.c_int64, vp, i64p], ctypes.c_int),
+        'bpe_skipgram_utf8_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64,
+                                     i64p], ctypes.c_int),
+        'bpe_skipgram_utf8_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp,
+                                            ctypes.c_int64, vp, i64p], ctypes.c_int),
+        'bpe_export_skipgram': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32, ctypes.c_int, vp, vp,
+                                 ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_export_skipgram_device': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32, ctypes.c_int, vp,
+                                        vp, ctypes.c_int64, vp, i64p], ctypes.c_int),
+        'bpe_encoder_get_skipgram_stats': ([vp, ctypes.POINTER(SkipgramStats)], ctypes.c_int),
+        'bpe_encoder_reset_skipgram_stats': ([vp], ctypes.c_int),
+        'bpe_get_skipgram_stats': ([vp, ctypes.POINTER(SkipgramStats)], ctypes.c_int),
+        'bpe_reset_skipgram_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -1023,6 +1059,33 @@ class Engine:
 
     def reset_export_stats(self):
         _check(lib().bpe_reset_export_stats(self._ctx), 'bpe_reset_export_stats')
+
+    # skip-gram pairs of corpus samples (include/bpe.h "skip-gram pairs") -----------------------------
+    def export_skipgram(self, idx=None, window=2, kind='vectors', to_vector_index=None):
+        """Corpus samples expanded into the (target, context) pairs of example/skip-gram.ts's loop on
+        the device (bpe_export_skipgram): idx, kind ('vectors' or 'ids') and to_vector_index as in
+        export_samples -> (targets int32, contexts int32, pair_off int64) as numpy arrays.  The sizing
+        call, then the real one."""
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        return _skipgram_host('bpe_export_skipgram', lambda t, c, cap, po: lib().bpe_export_skipgram(
+            self._ctx, kind, idx_p, n, tvi_p, n_index, int(window), t, c, cap, po), n)
+
+    def export_skipgram_tensors(self, idx=None, window=2, kind='vectors', to_vector_index=None, out=None):
+        """Device form (bpe_export_skipgram_device): (targets, contexts, pair_off) as torch tensors on
+        the context's device, two int32 planes and int64 offsets; no value touches the host.  out: a
+        pair of contiguous int32 tensors on the device to write the planes into, else a sizing call
+        runs first."""
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        return _skipgram_device('bpe_export_skipgram_device', lambda t, c, cap, po, need: lib().bpe_export_skipgram_device(
+            self._ctx, kind, idx_p, n, tvi_p, n_index, int(window), t, c, cap, po, need), n, self.device, out)
+
+    def skipgram_stats(self):
+        s = SkipgramStats()
+        _check(lib().bpe_get_skipgram_stats(self._ctx, ctypes.byref(s)), 'bpe_get_skipgram_stats')
+        return s.as_dict()
+
+    def reset_skipgram_stats(self):
+        _check(lib().bpe_reset_skipgram_stats(self._ctx), 'bpe_reset_skipgram_stats')
 
     def clear_corpus(self):
         _check(lib().bpe_clear_corpus(self._ctx), 'bpe_clear_corpus')
@@ -1641,6 +1704,145 @@ class Encoder:
 
     def reset_lines_stats(self):
         _check(lib().bpe_encoder_reset_lines_stats(self._enc), 'bpe_encoder_reset_lines_stats')
+
+    # skip-gram pairs (include/bpe.h "skip-gram pairs"): values -> (target, context) pairs on the device
+    def skipgram_flat(self, vals, off, window=2):
+        """The expansion alone (bpe_encoder_skipgram): texts vals[off[k]:off[k+1]] (int32 vector indices
+        or ids) -> (targets int32, contexts int32, pair_off int64), the pairs of example/skip-gram.ts's
+        loop over `window` values on each side.  The sizing call, then the real one."""
+        vals = _i32(vals).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = vals if vals.size else np.zeros(1, np.int32)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_host('bpe_encoder_skipgram', lambda t, c, cap, po: lib().bpe_encoder_skipgram(
+            self._enc, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), t, c, cap, po),
+            len(off) - 1)
+
+    def skipgram(self, texts, window=2):
+        """texts: a list of int sequences (encode_text's output) -> (targets, contexts, pair_off)."""
+        parts = [_i32(t).ravel() for t in texts]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        vals = np.concatenate(parts) if parts and off[-1] else np.zeros(0, np.int32)
+        return self.skipgram_flat(vals, off, window)
+
+    def skipgram_tensors(self, vals, off, window=2, out=None):
+        """Device form (bpe_encoder_skipgram_device): vals a torch int32 tensor and off a torch int64
+        tensor on the encoder's device -> (targets, contexts, pair_off) tensors there: two int32 planes
+        an nn.Embedding takes as they are, and int64 offsets.  out: a pair of contiguous int32 tensors
+        on the device to write the planes into (views of them come back), else a sizing call runs
+        first."""
+        import torch
+        if vals.dtype != torch.int32 or off.dtype != torch.int64:
+            raise BpeError('skipgram_tensors takes int32 values and int64 offsets', ERR_ARG)
+        if not (vals.is_cuda and off.is_cuda and vals.device.index == self.device and off.device.index == self.device):
+            raise BpeError('skipgram_tensors takes tensors on the encoder\'s device', ERR_ARG)
+        vals, off = vals.contiguous(), off.contiguous()
+        vp = vals.data_ptr() if vals.numel() else None
+        return _skipgram_device('bpe_encoder_skipgram_device', lambda t, c, cap, po, need: lib().bpe_encoder_skipgram_device(
+            self._enc, vp, off.data_ptr(), off.numel() - 1, int(window), t, c, cap, po, need),
+            off.numel() - 1, self.device, out)
+
+    def skipgram_text_flat(self, units, off, window=2, kind='vectors'):
+        """Texts units[off[k]:off[k+1]] (UTF-16 units) encoded and expanded on the device
+        (bpe_skipgram_text_batch) -> (targets, contexts, pair_off)."""
+        kind = self._KINDS[kind]
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_host('bpe_skipgram_text_batch', lambda t, c, cap, po: lib().bpe_skipgram_text_batch(
+            self._enc, kind, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), t, c, cap, po),
+            len(off) - 1)
+
+    def skipgram_text(self, texts, window=2, kind='vectors'):
+        """texts: a list of str -> (targets, contexts, pair_off): encode_text, then skipgram."""
+        units, off = _units_flat(texts)
+        return self.skipgram_text_flat(units, off, window, kind)
+
+    def skipgram_text_tensors(self, units, off, window=2, kind='vectors', out=None):
+        """Device form (bpe_skipgram_text_batch_device): torch int16 or uint16 units and int64 offsets
+        on the encoder's device -> (targets, contexts, pair_off) tensors there; no value touches the
+        host.  out: as in skipgram_tensors."""
+        kind = self._KINDS[kind]
+        units, off = _units_tensors(units, off, 'skipgram_text_tensors', self.device)
+        up = units.data_ptr() if units.numel() else None
+        return _skipgram_device('bpe_skipgram_text_batch_device', lambda t, c, cap, po, need: lib().bpe_skipgram_text_batch_device(
+            self._enc, kind, up, off.data_ptr(), off.numel() - 1, int(window), t, c, cap, po, need),
+            off.numel() - 1, self.device, out)
+
+    def skipgram_utf8(self, texts, off=None, window=2, kind='vectors'):
+        """skipgram_text for UTF-8 (bpe_skipgram_utf8_batch): texts a list of bytes, or the flat form
+        (uint8 array, int64 offsets) -> (targets, contexts, pair_off)."""
+        kind = self._KINDS[kind]
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_host('bpe_skipgram_utf8_batch', lambda t, c, cap, po: lib().bpe_skipgram_utf8_batch(
+            self._enc, kind, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), t, c, cap, po),
+            len(off) - 1)
+
+    def skipgram_utf8_tensors(self, data, off, window=2, kind='vectors', out=None):
+        """Device form (bpe_skipgram_utf8_batch_device): torch uint8 bytes and int64 offsets on the
+        encoder's device -> (targets, contexts, pair_off) tensors there.  out: as in skipgram_tensors."""
+        kind = self._KINDS[kind]
+        data, off = _utf8_tensors(data, off, 'skipgram_utf8_tensors', self.device)
+        dp = data.data_ptr() if data.numel() else None
+        return _skipgram_device('bpe_skipgram_utf8_batch_device', lambda t, c, cap, po, need: lib().bpe_skipgram_utf8_batch_device(
+            self._enc, kind, dp, off.data_ptr(), off.numel() - 1, int(window), t, c, cap, po, need),
+            off.numel() - 1, self.device, out)
+
+    def skipgram_stats(self):
+        s = SkipgramStats()
+        _check(lib().bpe_encoder_get_skipgram_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_skipgram_stats')
+        return s.as_dict()
+
+    def reset_skipgram_stats(self):
+        _check(lib().bpe_encoder_reset_skipgram_stats(self._enc), 'bpe_encoder_reset_skipgram_stats')
+
+
+def _skipgram_host(what, call, n):
+    """A skip-gram host form: call(targets, contexts, cap, pair_off) -> rc.  The sizing call, then the
+    real one -> (targets int32, contexts int32, pair_off int64)."""
+    off = np.zeros(n + 1, np.int64)
+    po = off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    rc = call(None, None, 0, po)
+    if rc == BPE_OK:   # (no pair to write)
+        return np.zeros(0, np.int32), np.zeros(0, np.int32), off
+    if rc != ERR_ARG or off[n] <= 0:
+        _check(rc, what)
+    t, c = np.empty(int(off[n]), np.int32), np.empty(int(off[n]), np.int32)
+    _check(call(t.ctypes.data, c.ctypes.data, t.size, po), what)
+    return t, c, off
+
+
+def _skipgram_device(what, call, n, device, out=None):
+    """A skip-gram device form: call(d_targets, d_contexts, cap, d_pair_off, needed) -> rc, into `out`
+    (two contiguous int32 tensors on the device) or, after a sizing call, into new tensors
+    -> (targets, contexts, pair_off) tensors."""
+    import torch
+    dev = torch.device('cuda', device)
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    need = ctypes.c_int64()
+    torch.cuda.synchronize(dev)   # (encoders and contexts run on streams of their own)
+    if out is None:
+        rc = call(None, None, 0, off.data_ptr(), ctypes.byref(need))
+        if rc == BPE_OK:   # (no pair to write)
+            return (torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), off)
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, what)
+        t = torch.empty(need.value, dtype=torch.int32, device=dev)
+        c = torch.empty(need.value, dtype=torch.int32, device=dev)
+    else:
+        t, c = out
+        for x in (t, c):
+            if x.dtype != torch.int32 or not x.is_cuda or x.device.index != device or not x.is_contiguous():
+                raise BpeError('%s takes two contiguous int32 tensors on the device as out' % what, ERR_ARG)
+    cap = min(t.numel(), c.numel())
+    torch.cuda.synchronize(dev)
+    _check(call(t.data_ptr() if cap else None, c.data_ptr() if cap else None, cap, off.data_ptr(), ctypes.byref(need)),
+           what)
+    return t[:need.value], c[:need.value], off
 
 
 def lines_mode(mode):

@@ -473,6 +473,7 @@ k_text_ooff(const int64_t *__restrict__ ooff, const int64_t *__restrict__ seg_of
 #include "bpe_text.hip.h"   // the text front end and the vector back end (bpe_encode_text_batch)
 #include "bpe_utf8.hip.h"   // text as UTF-8: bytes -> units in front of it (bpe_encode_utf8_batch)
 #include "bpe_lines.hip.h"  // lines as samples: texts -> samples (bpe_encoder_split_lines)
+#include "bpe_skipgram.hip.h"   // skip-gram pairs from the values behind it (bpe_encoder_skipgram)
 
 struct bpe_encoder {
     int device = 0;
@@ -510,6 +511,7 @@ struct bpe_encoder {
     LinesState ln;                            // lines as samples (bpe_encoder_split_lines and the restore from lines)
     LinesCall ln_pending;                     // a restore's split, counted when the restore is done
     bool ln_pending_u8 = false;               // ... which had a transcode in front
+    SgState sg;                               // skip-gram pairs (bpe_encoder_skipgram and the forms from text)
     // long texts in segments (BPE_LONG_SPLIT): first and last base id of every id (identity until
     // a merge makes it), the ids made so far, and the tables k_cuts reads (built and uploaded
     // with the rank table when dirty)
@@ -1374,19 +1376,36 @@ int text_index_error(int32_t id, int64_t k, int64_t pos) {
     return bpe_fail(BPE_ERR_VOCAB, msg);
 }
 
+// What every form that ends in the text pipeline checks before any work, in this order and with
+// these messages (text_run itself, and the forms that do work in front of it: the UTF-8 transcode,
+// the skip-gram forms).  outputs_ok: the caller's capacity and output pointers hold together.
+int text_check_call(bpe_encoder *E, int kind, int64_t n_texts, const int64_t *off, bool outputs_ok) {
+    if (kind != BPE_ENCODE_IDS && kind != BPE_ENCODE_VECTORS)
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode kind");
+    if (n_texts < 0 || n_texts >= 0x7FFFFFFF || !outputs_ok || (n_texts && !off))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_text_batch arguments");
+    if (kind == BPE_ENCODE_VECTORS && !E->txt.has_tvi)
+        return bpe_fail(BPE_ERR_STATE, "bpe native: encode to vectors without a vector index "
+                                       "(bpe_encoder_set_vector_index)");
+    return BPE_OK;
+}
+
+// ... and of the n_texts + 1 offsets once they are on the host
+int text_check_offsets(const int64_t *h_off, int64_t n_texts) {
+    if (n_texts && h_off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
+    for (int64_t k = 0; k < n_texts; ++k)
+        if (h_off[k + 1] < h_off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+    return BPE_OK;
+}
+
 // The pipeline.  dev: units, off, vals_out and out_off are device buffers (the device form);
 // otherwise host buffers, staged through the encoder's device buffer.
 int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off, int64_t n_texts,
              int32_t *vals_out, int64_t cap, int64_t *out_off, bool dev, int64_t *needed) {
     bpe_text_state &T = E->txt;
     *needed = 0;
-    if (kind != BPE_ENCODE_IDS && kind != BPE_ENCODE_VECTORS)
-        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode kind");
-    if (n_texts < 0 || n_texts >= 0x7FFFFFFF || cap < 0 || !out_off || (n_texts && !off) || (cap && !vals_out))
-        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_text_batch arguments");
-    if (kind == BPE_ENCODE_VECTORS && !T.has_tvi)
-        return bpe_fail(BPE_ERR_STATE, "bpe native: encode to vectors without a vector index "
-                                       "(bpe_encoder_set_vector_index)");
+    int rc0 = text_check_call(E, kind, n_texts, off, !(cap < 0 || !out_off || (cap && !vals_out)));
+    if (rc0) return rc0;
     ENC_TRY(hipSetDevice(E->device));
     hipStream_t s = E->stream;
     T.st.calls++;
@@ -1399,9 +1418,7 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
         ENC_TRY(hipStreamSynchronize(s));
         h_off = off_copy.data();
     }
-    if (n_texts && h_off[0] < 0) return bpe_fail(BPE_ERR_ARG, "bpe native: negative text offset");
-    for (int64_t k = 0; k < n_texts; ++k)
-        if (h_off[k + 1] < h_off[k]) return bpe_fail(BPE_ERR_ARG, "bpe native: text offsets must not decrease");
+    if ((rc0 = text_check_offsets(h_off, n_texts))) return rc0;
     const int64_t base = n_texts ? h_off[0] : 0, total = n_texts ? h_off[n_texts] - base : 0;
     if (total && !units) return bpe_fail(BPE_ERR_ARG, "bpe native: null unit buffer");
     if (total && !T.has_chars)
@@ -1765,6 +1782,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     text_free(E);
     u8_free(E->u8);
     ln_free(E->ln);
+    sg_free(E->sg);
     if (E->ev0) (void)hipEventDestroy(E->ev0);
     if (E->ev1) (void)hipEventDestroy(E->ev1);
     for (int i = 0; i < 2; ++i)
@@ -2002,20 +2020,15 @@ int utf8_encode(bpe_encoder *E, int kind, const uint8_t *bytes, const int64_t *o
                 int64_t cap, int64_t *out_off, bool dev, int64_t *needed) {
     *needed = 0;
     // (the UTF-16 form's own checks, made before any work here as they are made there)
-    if (kind != BPE_ENCODE_IDS && kind != BPE_ENCODE_VECTORS) return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode kind");
-    if (n_texts < 0 || n_texts >= 0x7FFFFFFF || cap < 0 || !out_off || (n_texts && !off) || (cap && !vals_out))
-        return bpe_fail(BPE_ERR_ARG, "bpe native: bad encode_text_batch arguments");
-    if (kind == BPE_ENCODE_VECTORS && !E->txt.has_tvi)
-        return bpe_fail(BPE_ERR_STATE, "bpe native: encode to vectors without a vector index "
-                                       "(bpe_encoder_set_vector_index)");
+    int rc = text_check_call(E, kind, n_texts, off, !(cap < 0 || !out_off || (cap && !vals_out)));
+    if (rc) return rc;
     ENC_TRY(hipSetDevice(E->device));
     E->u8.st.calls++;
     Utf8Call J;
     J.bytes = bytes, J.off = off, J.n_texts = n_texts, J.dev = dev;
     // the host form's values go through scratch: at most min(cap, bytes) of them (a text never grows)
     if (!dev) J.vals_cap = cap;
-    int rc = u8_transcode(E->u8, E->stream, J);
-    if (rc) return rc;
+    if ((rc = u8_transcode(E->u8, E->stream, J))) return rc;
     if (dev) {
         rc = text_run(E, kind, J.d_units, J.d_uoff, n_texts, vals_out, cap, out_off, true, needed);
     } else {
@@ -2112,6 +2125,167 @@ int bpe_encoder_get_lines_stats(bpe_encoder *E, bpe_lines_stats *out) {
 int bpe_encoder_reset_lines_stats(bpe_encoder *E) {
     if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
     E->ln.st = bpe_lines_stats{};
+    return BPE_OK;
+}
+
+// ---- skip-gram pairs (include/bpe.h; csrc/bpe_skipgram.hip.h) ---------------------------------------
+
+int bpe_encoder_skipgram(bpe_encoder *E, const int32_t *vals, const int64_t *off, int64_t n_texts, int window,
+                         int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    ENC_TRY(hipSetDevice(E->device));
+    E->sg.st.calls++;
+    int rc = sg_check_window(window);
+    if (rc) return rc;
+    if (pairs_cap < 0 || !pair_off || (pairs_cap && (!targets || !contexts)))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram output arguments");
+    SgCall J;
+    J.window = window;
+    if ((rc = sg_stage_host(E->sg, E->stream, vals, off, n_texts, J))) return rc;
+    return sg_host_form(E->sg, E->stream, J, targets, contexts, pairs_cap, pair_off);
+}
+
+int bpe_encoder_skipgram_device(bpe_encoder *E, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                int window, int32_t *d_targets, int32_t *d_contexts, int64_t pairs_cap,
+                                int64_t *d_pair_off, int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->sg.st.calls++;
+    if (pairs_cap < 0 || !d_pair_off || (pairs_cap && (!d_targets || !d_contexts)))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram output arguments");
+    SgCall J;
+    J.d_vals = d_vals, J.d_off = d_off, J.n_texts = n_texts, J.window = window;
+    J.d_t = pairs_cap ? d_targets : nullptr, J.d_c = pairs_cap ? d_contexts : nullptr;
+    J.d_poff = d_pair_off, J.cap = pairs_cap;
+    return sg_device_form(E->sg, E->stream, J, needed);
+}
+
+namespace {
+
+// The texts (UTF-16 units, or UTF-8 bytes transcoded first) through the encoder's device form into
+// the skip-gram scratch: J's values and offsets.  A transcode's numbers wait in *U for the commit.
+int sg_encode(bpe_encoder *E, int kind, const void *src, const int64_t *off, int64_t n, bool dev, bool utf8,
+              SgCall &J, Utf8Call *U) {
+    // (the encoder's own checks, made before any work here as they are made there: text_check_call)
+    int rc = text_check_call(E, kind, n, off, true);
+    if (rc) return rc;
+    hipStream_t s = E->stream;
+    SgState &S = E->sg;
+    const size_t b_off = sg_align((size_t)(n + 1) * 8);
+    const uint16_t *d_units = nullptr;
+    const int64_t *d_uoff = nullptr;
+    int64_t total = 0;   // units the texts have: their values are at most that many
+    size_t b_units = 0, b_uoff = 0;
+    if (utf8) {
+        E->u8.st.calls++;
+        U->bytes = static_cast<const uint8_t *>(src), U->off = off, U->n_texts = n, U->dev = dev;
+        if ((rc = u8_transcode(E->u8, s, *U))) return rc;
+        U->h_off.clear();
+        d_units = U->d_units, d_uoff = U->d_uoff, total = U->units;
+    } else if (dev) {
+        int64_t ends[2] = {0, 0};
+        if (n) {
+            ENC_TRY(hipMemcpyAsync(&ends[0], off, 8, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipMemcpyAsync(&ends[1], off + n, 8, hipMemcpyDeviceToHost, s));
+            ENC_TRY(hipStreamSynchronize(s));
+        }
+        total = std::max<int64_t>(ends[1] - ends[0], 0);   // (bad offsets: the encoder says so below)
+        d_units = static_cast<const uint16_t *>(src), d_uoff = off;
+    } else {
+        if ((rc = text_check_offsets(off, n))) return rc;   // (before the units they name are staged)
+        total = n ? off[n] - off[0] : 0;
+        if (total && !src) return bpe_fail(BPE_ERR_ARG, "bpe native: null unit buffer");
+        b_units = sg_align((size_t)total * 2), b_uoff = b_off;
+    }
+    // scratch: [values | their offsets | the host form's units | its offsets]
+    const size_t b_vals = sg_align((size_t)total * 4);
+    if ((rc = sg_grow(s, &S.d_in, &S.in_cap, b_vals + b_off + b_units + b_uoff))) return rc;
+    int32_t *d_vals = reinterpret_cast<int32_t *>(S.d_in);
+    int64_t *d_voff = reinterpret_cast<int64_t *>(S.d_in + b_vals);
+    if (!utf8 && !dev) {
+        uint16_t *s_units = reinterpret_cast<uint16_t *>(S.d_in + b_vals + b_off);
+        int64_t *s_uoff = reinterpret_cast<int64_t *>(S.d_in + b_vals + b_off + b_units);
+        std::vector<int64_t> rel((size_t)n + 1, 0);
+        for (int64_t k = 0; k <= n && n; ++k) rel[(size_t)k] = off[k] - off[0];
+        if (total)
+            ENC_TRY(hipMemcpyAsync(s_units, static_cast<const uint16_t *>(src) + off[0], (size_t)total * 2,
+                                   hipMemcpyHostToDevice, s));
+        ENC_TRY(hipMemcpyAsync(s_uoff, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        ENC_TRY(hipStreamSynchronize(s));   // (rel goes away)
+        d_units = s_units, d_uoff = s_uoff;
+    }
+    int64_t n_vals = 0;
+    if ((rc = text_run(E, kind, d_units, d_uoff, n, d_vals, total, d_voff, true, &n_vals))) return rc;
+    J.d_vals = d_vals, J.d_off = d_voff, J.n_texts = n;
+    return BPE_OK;
+}
+
+int sg_text(bpe_encoder *E, int kind, const void *src, const int64_t *off, int64_t n, bool utf8, int window,
+            int32_t *targets, int32_t *contexts, int64_t cap, int64_t *pair_off, bool dev, int64_t *needed) {
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->sg.st.calls++;
+    int rc = sg_check_window(window);
+    if (rc) return rc;
+    if (cap < 0 || !pair_off || (cap && (!targets || !contexts)))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram output arguments");
+    SgCall J;
+    Utf8Call U;
+    J.window = window;
+    if ((rc = sg_encode(E, kind, src, off, n, dev, utf8, J, &U))) return rc;
+    if (dev) {
+        J.d_t = cap ? targets : nullptr, J.d_c = cap ? contexts : nullptr, J.d_poff = pair_off, J.cap = cap;
+        rc = sg_device_form(E->sg, E->stream, J, needed);
+    } else {
+        rc = sg_host_form(E->sg, E->stream, J, targets, contexts, cap, pair_off);
+    }
+    if (rc) return rc;
+    if (utf8) u8_commit(E->u8, U);
+    return BPE_OK;
+}
+
+}  // namespace
+
+int bpe_skipgram_text_batch(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                            int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int64_t needed = 0;
+    return sg_text(E, kind, units, off, n_texts, false, window, targets, contexts, pairs_cap, pair_off, false, &needed);
+}
+
+int bpe_skipgram_text_batch_device(bpe_encoder *E, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                   int64_t n_texts, int window, int32_t *d_targets, int32_t *d_contexts,
+                                   int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    return sg_text(E, kind, d_units, d_off, n_texts, false, window, d_targets, d_contexts, pairs_cap, d_pair_off, true,
+                   needed);
+}
+
+int bpe_skipgram_utf8_batch(bpe_encoder *E, int kind, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                            int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
+    int64_t needed = 0;
+    return sg_text(E, kind, bytes, off, n_texts, true, window, targets, contexts, pairs_cap, pair_off, false, &needed);
+}
+
+int bpe_skipgram_utf8_batch_device(bpe_encoder *E, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                   int64_t n_texts, int window, int32_t *d_targets, int32_t *d_contexts,
+                                   int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    return sg_text(E, kind, d_bytes, d_off, n_texts, true, window, d_targets, d_contexts, pairs_cap, d_pair_off, true,
+                   needed);
+}
+
+int bpe_encoder_get_skipgram_stats(bpe_encoder *E, bpe_skipgram_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->sg.st;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_skipgram_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->sg.st = bpe_skipgram_stats{};
     return BPE_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "bpe_multi.h"
 #include "bpe_utf8.hip.h"     // text as UTF-8: bytes -> units in front of the ingest (bpe_add_utf8_batch)
 #include "bpe_lines.hip.h"    // lines as samples: texts -> samples in front of the ingest (bpe_add_lines_batch)
+#include "bpe_skipgram.hip.h" // skip-gram pairs behind the export (bpe_export_skipgram)
 #include "bpe_tools.h"
 
 namespace bpe_step {
@@ -255,6 +256,7 @@ struct bpe_ctx {
     // text as UTF-8: the transcode's scratch and counters (made by its first call)
     Utf8State *u8 = nullptr;
     LinesState *ln = nullptr;
+    SgState *sg = nullptr;    // skip-gram pairs of exported samples (made by its first call)
 };
 
 void ingest_free(bpe_ctx *c);
@@ -2872,6 +2874,10 @@ int bpe_destroy(bpe_ctx *c) {
         ln_free(*c->ln);
         delete c->ln;
     }
+    if (c->sg) {
+        sg_free(*c->sg);
+        delete c->sg;
+    }
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -4861,6 +4867,71 @@ int export_text(bpe_ctx *c, bpe_decoder *D, const int64_t *idx, int64_t n, void 
     return BPE_OK;
 }
 
+// ---- skip-gram pairs of corpus samples (bpe_export_skipgram, include/bpe.h): the export above into
+// scratch, then bpe_skipgram.hip.h's expansion on the context's stream ---------------------------------
+int skipgram_state(bpe_ctx *c, SgState **out) {
+    if (!c->sg) c->sg = new SgState();
+    *out = c->sg;
+    return BPE_OK;
+}
+
+int skipgram_kind(int kind) {
+    if (kind == EXP_IDS || kind == EXP_VEC) return BPE_OK;
+    return fail(BPE_ERR_ARG, "bpe native: a skip-gram export takes BPE_EXPORT_IDS or BPE_EXPORT_VECTORS");
+}
+
+int export_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                    int window, int32_t *targets, int32_t *contexts, int64_t cap, int64_t *pair_off,
+                    int64_t *needed_out, bool dev) {
+    if (!c || cap < 0 || !pair_off || (cap && (!targets || !contexts)) || (dev && !needed_out))
+        return fail(BPE_ERR_ARG, "bpe native: bad export_skipgram arguments");
+    int rc = set_device(c);
+    if (rc) return rc;
+    SgState *S;
+    if ((rc = skipgram_state(c, &S))) return rc;
+    S->st.calls++;
+    if ((rc = sg_check_window(window)) || (rc = skipgram_kind(kind))) return rc;
+    ExportState *X;
+    if ((rc = export_state(c, &X))) return rc;
+    X->st.calls++;
+    hipStream_t s = c->stream;
+    ExportSync guard{s};
+    if ((rc = export_prepare(c, X, kind, idx, n, tvi, n_index))) return rc;
+    const int64_t n_vals = X->needed;
+    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, exp_align((size_t)std::max<int64_t>(n_vals, 1) * 4)))) return rc;
+    if ((rc = export_emit(c, X, kind, X->d_vals))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = export_timing(X))) return rc;
+    X->st.samples += n;
+    X->st.values += n_vals;
+    SgCall J;
+    J.d_vals = reinterpret_cast<const int32_t *>(X->d_vals), J.d_off = X->d_off, J.n_texts = n, J.window = window;
+    if (!dev) return sg_host_form(*S, s, J, targets, contexts, cap, pair_off);
+    J.d_t = cap ? targets : nullptr, J.d_c = cap ? contexts : nullptr, J.d_poff = pair_off, J.cap = cap;
+    return sg_device_form(*S, s, J, needed_out);
+}
+
+// A multi-device context: the samples through its host export, shard by shard, and the expansion of
+// the assembled batch on its first shard's device.
+int multi_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                   int window, int32_t *targets, int32_t *contexts, int64_t cap, int64_t *pair_off) {
+    bpe_ctx *t = multi_first_shard(c->multi);
+    int rc = set_device(t);
+    if (rc) return rc;
+    SgState *S;
+    if ((rc = skipgram_state(t, &S))) return rc;
+    S->st.calls++;
+    if ((rc = sg_check_window(window)) || (rc = skipgram_kind(kind))) return rc;
+    std::vector<int64_t> off;
+    std::vector<int32_t> vals;
+    if ((rc = multi_export_values(c->multi, kind, idx, n, tvi, n_index, vals, off))) return rc;
+    if ((rc = set_device(t))) return rc;
+    SgCall J;
+    J.window = window;
+    if ((rc = sg_stage_host(*S, t->stream, vals.data(), off.data(), n, J))) return rc;
+    return sg_host_form(*S, t->stream, J, targets, contexts, cap, pair_off);
+}
+
 }  // namespace
 
 extern "C" {
@@ -4922,6 +4993,39 @@ int bpe_reset_export_stats(bpe_ctx *c) {
     MULTI(reset_export_stats(c->multi));
     if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
     if (c->exp) c->exp->st = bpe_export_stats{};
+    return BPE_OK;
+}
+
+int bpe_export_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                        int32_t n_index, int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap,
+                        int64_t *pair_off) {
+    if (c && c->multi && n >= 0 && pairs_cap >= 0 && pair_off && (!pairs_cap || (targets && contexts)))
+        return multi_skipgram(c, kind, idx, n, to_vector_index, n_index, window, targets, contexts, pairs_cap, pair_off);
+    return export_skipgram(c, kind, idx, n, to_vector_index, n_index, window, targets, contexts, pairs_cap, pair_off,
+                           nullptr, false);
+}
+
+int bpe_export_skipgram_device(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                               int32_t n_index, int window, int32_t *d_targets, int32_t *d_contexts,
+                               int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed) {
+    if (c && c->multi)
+        return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
+                                 "(its shards sit on different devices: take the host form)");
+    return export_skipgram(c, kind, idx, n, to_vector_index, n_index, window, d_targets, d_contexts, pairs_cap,
+                           d_pair_off, needed, true);
+}
+
+int bpe_get_skipgram_stats(bpe_ctx *c, bpe_skipgram_stats *out) {
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    const bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    *out = t->sg ? t->sg->st : bpe_skipgram_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_skipgram_stats(bpe_ctx *c) {
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    if (t->sg) t->sg->st = bpe_skipgram_stats{};
     return BPE_OK;
 }
 

@@ -1026,6 +1026,19 @@ int multi_export_utf8_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, 
     return bpe_decode_utf8_batch(dec, BPE_DECODE_IDS, ids.data(), off.data(), n, bytes_out, bytes_cap, out_off);
 }
 
+int multi_export_values(bpe_multi *m, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                        std::vector<int32_t> &vals, std::vector<int64_t> &off) {
+    off.assign((size_t)n + 1, 0);
+    int rc = multi_export_samples(m, kind, idx, n, tvi, n_index, nullptr, 0, off.data());
+    if (rc < 0 && !(rc == BPE_ERR_ARG && off[(size_t)n] > 0)) return rc;
+    vals.assign((size_t)std::max<int64_t>(off[(size_t)n], 1), 0);
+    if (off[(size_t)n]) {
+        m->exp.calls--;   // (one call, asked twice)
+        MTRY(multi_export_samples(m, kind, idx, n, tvi, n_index, vals.data(), off[(size_t)n], off.data()));
+    }
+    return BPE_OK;
+}
+
 int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out) {
     *out = m->exp;
     for (auto s : m->sh) {

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "bpe.h"
 
 struct bpe_multi;
@@ -34,6 +36,10 @@ int multi_export_text_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, 
                             int64_t units_cap, int64_t *out_off);
 int multi_export_utf8_batch(bpe_multi *m, bpe_decoder *dec, const int64_t *idx, int64_t n, uint8_t *bytes_out,
                             int64_t bytes_cap, int64_t *out_off);
+// the samples' ids or vector indices assembled on the host (sized, then filled: one export call),
+// for the skip-gram expansion of a multi-device context (bpe_engine.hip)
+int multi_export_values(bpe_multi *m, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                        int32_t n_index, std::vector<int32_t> &vals, std::vector<int64_t> &off);
 int multi_get_export_stats(bpe_multi *m, bpe_export_stats *out);
 int multi_reset_export_stats(bpe_multi *m);
 int multi_clear_corpus(bpe_multi *m);

@@ -29,6 +29,8 @@ export type Markers = {
 }
 export declare function fileContentToCorpus(content: string | Buffer): string
 export type CorpusHelperName = 'linesToCorpus' | 'linesTrimmedToCorpus' | 'fileContentToCorpus'
+/** two planes of vector indices and one pair offset per text, plus the total */
+export type SkipGramPairs = { targets: Int32Array; contexts: Int32Array; offsets: Float64Array }
 export declare function linesToCorpus(text: string): string[]
 export declare function linesTrimmedToCorpus(text: string): string[]
 export declare class BPETokenizer {
@@ -121,6 +123,16 @@ export declare class BPETokenizer {
    * allocation.  Without the addon (or with BPE_ENCODE_DEVICE=0) the strings are encoded on the host.
    */
   corpusToTextBatchUtf8(indices?: number[]): Buffer[]
+  /**
+   * skip-gram training pairs on the GPU: the (target, context) pairs the loop of example/skip-gram.ts
+   * makes of `encodeToVector(text)` over `window` (default 2, at most 64) values on each side, for many
+   * texts, UTF-8 buffers or corpus samples at once; text k owns the pairs offsets[k] .. offsets[k + 1].
+   * The errors are those of encodeToVectorBatch and corpusToVectorBatch.  When the device cannot take a
+   * call, their vectors are expanded in JS.
+   */
+  skipGramBatch(texts: string[], window?: number): SkipGramPairs
+  skipGramBatchUtf8(buffers: Array<Buffer | Uint8Array>, window?: number): SkipGramPairs
+  corpusToSkipGramBatch(indices?: number[] | null, window?: number): SkipGramPairs
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

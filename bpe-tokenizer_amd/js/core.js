@@ -34,6 +34,10 @@ const {
   corpusVectorsOnDevice,
   corpusTextsOnDevice,
   corpusTextsUtf8OnDevice,
+  skipGramWindow,
+  expandSkipGram,
+  skipGramTextsMaybeOnDevice,
+  corpusSkipGramOnDevice,
   decodeVectorsUtf8OnDevice,
   loadNativeUtf8,
   loadNativeLines,
@@ -247,6 +251,23 @@ class BPETokenizer {
     let out = corpusTextsUtf8OnDevice(this, this.engine(), indices)
     if (out) return out
     return this.corpusToTextBatch(indices).map(s => Buffer.from(s))
+  }
+
+  /**
+   * @description the trained corpus as skip-gram training pairs, on the GPU (bpe_export_skipgram): the
+   * (target, context) pairs example/skip-gram.ts makes of every vector of
+   * `this.corpusToVectorBatch(indices)` over `window` (default 2) values on each side, as
+   * `{targets: Int32Array, contexts: Int32Array, offsets: Float64Array}`; sample s owns the pairs
+   * offsets[s] .. offsets[s + 1].  Throws the reference's `unknown token index: N`.  Without the addon
+   * (or with BPE_ENCODE_DEVICE=0) the vectors are expanded in JS, with the same results.
+   */
+  corpusToSkipGramBatch(indices, window) {
+    window = skipGramWindow(window)
+    if (!this._engine) return expandSkipGram([], window)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let out = corpusSkipGramOnDevice(this, this.engine(), indices, window)
+    if (out) return out
+    return expandSkipGram(this.corpusToVectorBatch(indices), window)
   }
 
   set corpus_in_code(samples) {
@@ -729,6 +750,39 @@ class BPETokenizer {
     let out = encodeTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, buffers, true)
     if (out) return out
     return this.encodeToVectorBatch(buffers.map(b => Buffer.from(b.buffer, b.byteOffset, b.length).toString()))
+  }
+
+  /**
+   * @description skip-gram training pairs of many texts at once on the GPU (bpe_skipgram_text_batch):
+   * every text is encoded as encodeToVectorBatch encodes it and its vector expanded, on the device,
+   * into the (target, context) pairs of example/skip-gram.ts's loop over `window` (default 2) values
+   * on each side.  Returns `{targets: Int32Array, contexts: Int32Array, offsets: Float64Array}`; text
+   * k owns the pairs offsets[k] .. offsets[k + 1].  The errors are encodeToVectorBatch's; when the
+   * device cannot take the call, its vectors are expanded in JS, with the same results.
+   */
+  skipGramBatch(texts, window) {
+    window = skipGramWindow(window)
+    if (texts.length === 0) return expandSkipGram([], window)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    if (texts.every(t => typeof t === 'string')) {
+      let out = skipGramTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, texts, window, false)
+      if (out) return out
+    }
+    return expandSkipGram(this.encodeToVectorBatch(texts), window)
+  }
+
+  /**
+   * @description skipGramBatch for UTF-8 bytes: an array of Buffer / Uint8Array, decoded on the device
+   * as `buffer.toString()` decodes them (bpe_skipgram_utf8_batch).  Equals
+   * `this.skipGramBatch(buffers.map(b => b.toString()), window)`.
+   */
+  skipGramBatchUtf8(buffers, window) {
+    window = skipGramWindow(window)
+    if (buffers.length === 0) return expandSkipGram([], window)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let out = skipGramTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, buffers, window, true)
+    if (out) return out
+    return expandSkipGram(this.encodeToVectorBatchUtf8(buffers), window)
   }
 
   /** core.ts:447-453 */

@@ -76,6 +76,14 @@ function loadNativeExport() {
   return nativeExport
 }
 
+// the skip-gram addon (addon/bpe_skipgram_napi.node: skipGramTextBatch and skipGramUtf8Batch on a
+// text encoder handle, exportSkipGram on an engine handle)
+let nativeSkipGram = null
+function loadNativeSkipGram() {
+  if (!nativeSkipGram) nativeSkipGram = require(path.join(__dirname, '..', 'addon', 'bpe_skipgram_napi.node'))
+  return nativeSkipGram
+}
+
 let nativeText = null
 function loadNativeText() {
   if (!nativeText) nativeText = require(path.join(__dirname, '..', 'addon', 'bpe_text_napi.node'))
@@ -571,6 +579,105 @@ function corpusTextsUtf8OnDevice(owner, engine, indices) {
   return addon.exportUtf8(engine, syncDecoder(owner), exportIndices(indices))
 }
 
+/** BPE_SKIPGRAM_MAX_WINDOW (include/bpe.h) */
+const SKIPGRAM_MAX_WINDOW = 64
+
+/** the window of a skip-gram call: an integer in [1, SKIPGRAM_MAX_WINDOW], 2 when left out */
+function skipGramWindow(window) {
+  if (window === undefined) return 2
+  if (!Number.isInteger(window) || window < 1 || window > SKIPGRAM_MAX_WINDOW)
+    throw new RangeError(`skip-gram window ${window} outside [1, ${SKIPGRAM_MAX_WINDOW}]`)
+  return window
+}
+
+/**
+ * Vectors (one array per text) -> their (target, context) pairs over `window` values on each side, in
+ * JS: for every value of a text in order, its neighbours from `window` before to `window` after it,
+ * in order, without itself and without places outside the text.  What the device forms compute; the
+ * route of a call the device cannot take.
+ */
+function expandSkipGram(vectors, window) {
+  let offsets = new Float64Array(vectors.length + 1)
+  vectors.forEach((v, k) => {
+    let n = v.length
+    offsets[k + 1] = offsets[k] + (n <= 1 ? 0 : n <= window + 1 ? n * (n - 1) : window * (2 * n - window - 1))
+  })
+  let targets = new Int32Array(offsets[vectors.length])
+  let contexts = new Int32Array(offsets[vectors.length])
+  let p = 0
+  for (let v of vectors) {
+    for (let i = 0; i < v.length; i++) {
+      let last = Math.min(i + window, v.length - 1)
+      for (let j = Math.max(i - window, 0); j <= last; j++) {
+        if (j === i) continue
+        targets[p] = v[i]
+        contexts[p++] = v[j]
+      }
+    }
+  }
+  return { targets, contexts, offsets }
+}
+
+/**
+ * A batch of texts through the owner's device text encoder and the skip-gram expansion behind it
+ * (bpe_skipgram_text_batch; utf8: Buffers / Uint8Arrays through bpe_skipgram_utf8_batch) ->
+ * {targets, contexts, offsets}, or null when the device cannot take the call (the caller then expands
+ * encodeToVectorBatch's vectors in JS, which settles what the device can do under its own rules).  The
+ * reference's own errors are thrown with its strings; with BPE_ENCODE_DEVICE=1 the device's go through.
+ */
+function skipGramTextsMaybeOnDevice(owner, list, tripleOf, texts, window, utf8) {
+  if (ENCODE_DEVICE === '0') return null
+  if (
+    ENCODE_DEVICE !== '1' &&
+    (owner._tenc_failed === true || (owner._tenc_failed && owner._tenc_failed === list))
+  )
+    return null
+  try {
+    let addon = loadNativeSkipGram()
+    let enc = syncTextEncoder(owner, list, tripleOf)
+    let [data, off] = utf8 ? buffersToBytes(texts) : textsToUnits(texts)
+    let res = utf8 ? addon.skipGramUtf8Batch(enc, data, off, window, 1) : addon.skipGramTextBatch(enc, data, off, window, 1)
+    return { targets: res[0], contexts: res[1], offsets: res[2] }
+  } catch (e) {
+    let msg = String((e && e.message) || e)
+    let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
+    if (m) throw new Error('unknown token, char: ' + JSON.stringify(String.fromCodePoint(parseInt(m[1], 16))))
+    m = /^unknown token index: (-?\d+) \(text \d+, position \d+\)$/.exec(msg)
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    if (ENCODE_DEVICE === '1') throw e
+    return null
+  }
+}
+
+/**
+ * The samples `indices` (null: every sample) as skip-gram pairs of their vectors through
+ * `owner.to_vector_index` (bpe_export_skipgram) -> {targets, contexts, offsets}, or null when there is
+ * no addon to ask.  The device's `unknown token index: N (sample K, position I)` is thrown as the
+ * reference's `unknown token index: N`.
+ */
+function corpusSkipGramOnDevice(owner, engine, indices, window) {
+  if (!exportAddon()) return null
+  let addon
+  try {
+    addon = loadNativeSkipGram()
+  } catch (e) {
+    if (ENCODE_DEVICE === '1') throw e
+    return null
+  }
+  let index = new Int32Array(owner.to_vector_index.length).fill(-1)
+  owner.to_vector_index.forEach((v, i) => {
+    index[i] = v
+  })
+  try {
+    let res = addon.exportSkipGram(engine, EXPORT_VECTORS, exportIndices(indices), index, window)
+    return { targets: res[0], contexts: res[1], offsets: res[2] }
+  } catch (e) {
+    let m = /^unknown token index: (\d+) \(sample \d+, position \d+\)$/.exec(String(e && e.message))
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    throw e
+  }
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -632,4 +739,9 @@ module.exports = {
   corpusVectorsOnDevice,
   corpusTextsOnDevice,
   corpusTextsUtf8OnDevice,
+  loadNativeSkipGram,
+  skipGramWindow,
+  expandSkipGram,
+  skipGramTextsMaybeOnDevice,
+  corpusSkipGramOnDevice,
 }

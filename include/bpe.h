@@ -979,6 +979,87 @@ int bpe_export_utf8_batch_device(bpe_ctx *ctx, bpe_decoder *dec, const int64_t *
 int bpe_decoder_get_utf8_stats(bpe_decoder *dec, bpe_utf8_stats *out);
 int bpe_decoder_reset_utf8_stats(bpe_decoder *dec);
 
+/* ---- skip-gram pairs -----------------------------------------------------------------------------
+ * What the reference's own consumer of vectors does with them (example/skip-gram.ts:28-47): every text
+ * is expanded into (target, context) pairs over a window of `window` values on each side, on the
+ * device, so that bytes -> vectors -> training pairs and corpus -> training pairs cross PCIe as nothing
+ * or as bytes only, and a framework gets two int32 arrays it can feed to an embedding.
+ *
+ * For one text with values v[0 .. n) and window w >= 1: for i = 0 .. n - 1 ascending, and for
+ * j = i - w .. i + w ascending, skipping j < 0, j == i and j >= n, the pair (target = v[i], context =
+ * v[j]).  Token i emits min(i, w) + min(n - 1 - i, w) pairs; a text n (n - 1) pairs if n <= w + 1, else
+ * w (2n - w - 1); n = 0 and n = 1 emit nothing; pairs never cross texts.  Values are copied as given
+ * (vector indices or ids): the expansion knows no vocabulary.
+ * The output is two int32 planes, targets[P] and contexts[P], and n_texts + 1 int64 pair offsets
+ * (pair_off[0] = 0, P = pair_off[n_texts]).  Counts and offsets are 64-bit everywhere.  A window outside
+ * [1, BPE_SKIPGRAM_MAX_WINDOW] gives BPE_ERR_ARG.
+ *
+ * Capacity and sizing follow bpe_decode_batch: the offsets are always written; when pair_off[n_texts]
+ * exceeds pairs_cap (the pairs each plane holds) no pair is written and BPE_ERR_ARG comes back; NULL
+ * planes with pairs_cap 0 are the sizing call.  The `_device` forms take and fill buffers on the
+ * owner's device (4-byte aligned values and planes, 8-byte aligned offsets; the planes are stored
+ * 16 B per lane when both sit at the same address mod 16, pair by pair otherwise), report *needed (a
+ * host int64: P), run on the owner's stream and synchronise before returning.  The host forms are the
+ * device forms plus the copies.
+ *
+ * bpe_encoder_skipgram is the expansion alone: text k is vals[off[k] .. off[k+1]); off[0] need not be 0
+ * and values before it are never read; decreasing or negative offsets give BPE_ERR_ARG with nothing
+ * written; n_texts == 0 is fine.
+ * bpe_skipgram_text_batch and bpe_skipgram_utf8_batch run bpe_encode_text_batch_device /
+ * bpe_encode_utf8_batch_device (`kind`: BPE_ENCODE_IDS or BPE_ENCODE_VECTORS) into grow-only scratch of
+ * the encoder and expand from there: in the device form no value touches the host.  The encoder's
+ * errors, messages and long-text mode are its own (`unknown token, char: U+XXXX (text K, unit I)`,
+ * BPE_ERR_STATE without a char table or a vector index, ...), with nothing written.
+ * bpe_export_skipgram sends corpus samples through bpe_export_samples_device (kind BPE_EXPORT_IDS or
+ * BPE_EXPORT_VECTORS with to_vector_index; idx NULL for every sample) into scratch of the context and
+ * expands from there.  It has the export's errors and its read-only guarantee: a bpe_merge_until after
+ * it gives the merges it would have given without it.  A multi-device context takes the host form
+ * shard by shard (the samples through its host export, the expansion on its first shard's device);
+ * the device form refuses it with BPE_ERR_ARG.
+ *
+ * bpe_skipgram_stats: `calls` counts every call (sizing and failed ones too); the other fields count
+ * the calls that wrote their pairs: their texts, the values they read, the pairs they wrote, and the
+ * HIP-event time of the two kernels alone (the encode's and the export's stay in their own stats).  A
+ * multi-device context reports its first shard's.
+ * The expand kernel works on tiles of BPE_SKIPGRAM_TILE pairs, and the scan of the texts' pair counts
+ * takes BPE_SKIPGRAM_SCAN_ROUND texts per round (csrc/bpe_skipgram.hip.h; exported for the tests, which
+ * place texts around the first and size a batch past the second). */
+#define BPE_SKIPGRAM_MAX_WINDOW 64
+#define BPE_SKIPGRAM_TILE 2048
+#define BPE_SKIPGRAM_SCAN_ROUND 8192
+typedef struct {
+    int64_t calls;            /* skip-gram calls */
+    int64_t texts;            /* texts of the calls that wrote their pairs */
+    int64_t values_in;        /* ... their values */
+    int64_t pairs_out;        /* ... the pairs written (to each plane) */
+    double kernel_ms;         /* HIP-event time of the offsets and expand kernels */
+} bpe_skipgram_stats;
+int bpe_encoder_skipgram(bpe_encoder *enc, const int32_t *vals, const int64_t *off, int64_t n_texts, int window,
+                         int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off);
+int bpe_encoder_skipgram_device(bpe_encoder *enc, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                int window, int32_t *d_targets, int32_t *d_contexts, int64_t pairs_cap,
+                                int64_t *d_pair_off, int64_t *needed);
+int bpe_skipgram_text_batch(bpe_encoder *enc, int kind, const uint16_t *units, const int64_t *off, int64_t n_texts,
+                            int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off);
+int bpe_skipgram_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                   int64_t n_texts, int window, int32_t *d_targets, int32_t *d_contexts,
+                                   int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed);
+int bpe_skipgram_utf8_batch(bpe_encoder *enc, int kind, const uint8_t *bytes, const int64_t *off, int64_t n_texts,
+                            int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap, int64_t *pair_off);
+int bpe_skipgram_utf8_batch_device(bpe_encoder *enc, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                   int64_t n_texts, int window, int32_t *d_targets, int32_t *d_contexts,
+                                   int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed);
+int bpe_export_skipgram(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                        int32_t n_index, int window, int32_t *targets, int32_t *contexts, int64_t pairs_cap,
+                        int64_t *pair_off);
+int bpe_export_skipgram_device(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                               int32_t n_index, int window, int32_t *d_targets, int32_t *d_contexts,
+                               int64_t pairs_cap, int64_t *d_pair_off, int64_t *needed);
+int bpe_encoder_get_skipgram_stats(bpe_encoder *enc, bpe_skipgram_stats *out);
+int bpe_encoder_reset_skipgram_stats(bpe_encoder *enc);
+int bpe_get_skipgram_stats(bpe_ctx *ctx, bpe_skipgram_stats *out);
+int bpe_reset_skipgram_stats(bpe_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
