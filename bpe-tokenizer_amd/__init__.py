@@ -69,6 +69,10 @@ C_API = [
     'bpe_skipgram_utf8_batch', 'bpe_skipgram_utf8_batch_device', 'bpe_export_skipgram', 'bpe_export_skipgram_device',
     'bpe_encoder_get_skipgram_stats', 'bpe_encoder_reset_skipgram_stats', 'bpe_get_skipgram_stats',
     'bpe_reset_skipgram_stats',
+    'bpe_encoder_skipgram_counts', 'bpe_encoder_skipgram_counts_device', 'bpe_skipgram_counts_text_batch',
+    'bpe_skipgram_counts_text_batch_device', 'bpe_skipgram_counts_utf8_batch', 'bpe_skipgram_counts_utf8_batch_device',
+    'bpe_export_skipgram_counts', 'bpe_export_skipgram_counts_device', 'bpe_encoder_get_skipgram_counts_stats',
+    'bpe_encoder_reset_skipgram_counts_stats', 'bpe_get_skipgram_counts_stats', 'bpe_reset_skipgram_counts_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -129,6 +133,9 @@ LINES_FILE = 2      # BPE_LINES_FILE: fileContentToCorpus (U+001C + text + U+000
 SKIPGRAM_MAX_WINDOW = 64    # BPE_SKIPGRAM_MAX_WINDOW: the widest window of the skip-gram expansion
 SKIPGRAM_TILE = 2048        # BPE_SKIPGRAM_TILE: pairs per workgroup of the expand kernel
 SKIPGRAM_SCAN_ROUND = 8192  # BPE_SKIPGRAM_SCAN_ROUND: texts per round of the scan of the pair counts
+SKIPGRAM_COUNTS_MAX_DIM = 16384  # BPE_SKIPGRAM_COUNTS_MAX_DIM: the largest `dim` of the skip-gram pair counts
+SKIPGRAM_COUNTS_TILE = 2048      # BPE_SKIPGRAM_COUNTS_TILE: positions per workgroup of the count kernel
+SKIPGRAM_COUNTS_SLOTS = 4096     # BPE_SKIPGRAM_COUNTS_SLOTS: slots of its LDS table
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
@@ -269,6 +276,16 @@ class SkipgramStats(ctypes.Structure):
     """bpe_skipgram_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
                 ('pairs_out', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramCountsStats(ctypes.Structure):
+    """bpe_skipgram_counts_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
+                ('pairs_counted', ctypes.c_int64), ('distinct_out', ctypes.c_int64), ('lds_overflow', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -476,6 +493,27 @@ def lib():
         'bpe_encoder_reset_skipgram_stats': ([vp], ctypes.c_int),
         'bpe_get_skipgram_stats': ([vp, ctypes.POINTER(SkipgramStats)], ctypes.c_int),
         'bpe_reset_skipgram_stats': ([vp], ctypes.c_int),
+        'bpe_encoder_skipgram_counts': ([vp, vp, i64p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+                                         ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_encoder_skipgram_counts_device': ([vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+                                                ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_skipgram_counts_text_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp,
+                                            vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_skipgram_counts_text_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                   vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_skipgram_counts_utf8_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp,
+                                            vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_skipgram_counts_utf8_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                   vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_export_skipgram_counts': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32, ctypes.c_int,
+                                        ctypes.c_int, vp, vp, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_export_skipgram_counts_device': ([vp, ctypes.c_int, i64p, ctypes.c_int64, i32p, ctypes.c_int32,
+                                               ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64, i64p],
+                                              ctypes.c_int),
+        'bpe_encoder_get_skipgram_counts_stats': ([vp, ctypes.POINTER(SkipgramCountsStats)], ctypes.c_int),
+        'bpe_encoder_reset_skipgram_counts_stats': ([vp], ctypes.c_int),
+        'bpe_get_skipgram_counts_stats': ([vp, ctypes.POINTER(SkipgramCountsStats)], ctypes.c_int),
+        'bpe_reset_skipgram_counts_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -1086,6 +1124,44 @@ class Engine:
 
     def reset_skipgram_stats(self):
         _check(lib().bpe_reset_skipgram_stats(self._ctx), 'bpe_reset_skipgram_stats')
+
+    # skip-gram pair counts of corpus samples (include/bpe.h "skip-gram pair counts") -------------------
+    def _counts_dim(self, kind, dim, tvi_a):
+        """dim=None: the token count for ids, the vector index's size for vectors."""
+        if dim is not None:
+            return int(dim)
+        if kind == EXPORT_VECTORS and tvi_a is not None:
+            return max(int(tvi_a.max()) + 1, 1)
+        return max(self.num_tokens(), 1)
+
+    def export_skipgram_counts(self, idx=None, window=2, kind='vectors', dim=None, to_vector_index=None):
+        """Corpus samples' skip-gram pairs counted on the device (bpe_export_skipgram_counts): idx, kind
+        ('vectors' or 'ids') and to_vector_index as in export_skipgram -> (targets int32, contexts
+        int32, counts int64): every distinct (target, context) pair in ascending order with the
+        number of times it occurs.  dim: values lie in [0, dim); None is the token count for ids and
+        the vector index's size for vectors.  The sizing call, then the real one."""
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        dim = self._counts_dim(kind, dim, tvi_a)
+        return _skipgram_counts_host('bpe_export_skipgram_counts', lambda t, c, k, cap, need: lib().bpe_export_skipgram_counts(
+            self._ctx, kind, idx_p, n, tvi_p, n_index, int(window), dim, t, c, k, cap, need))
+
+    def export_skipgram_counts_tensors(self, idx=None, window=2, kind='vectors', dim=None, to_vector_index=None,
+                                       out=None):
+        """Device form (bpe_export_skipgram_counts_device): (targets, contexts, counts) as torch tensors
+        on the context's device.  out: (int32, int32, int64) contiguous tensors there to write into,
+        else a sizing call runs first."""
+        kind, idx_a, idx_p, n, tvi_a, tvi_p, n_index = self._export_args(idx, kind, to_vector_index)
+        dim = self._counts_dim(kind, dim, tvi_a)
+        return _skipgram_counts_device('bpe_export_skipgram_counts_device', lambda t, c, k, cap, need: lib().bpe_export_skipgram_counts_device(
+            self._ctx, kind, idx_p, n, tvi_p, n_index, int(window), dim, t, c, k, cap, need), self.device, out)
+
+    def skipgram_counts_stats(self):
+        s = SkipgramCountsStats()
+        _check(lib().bpe_get_skipgram_counts_stats(self._ctx, ctypes.byref(s)), 'bpe_get_skipgram_counts_stats')
+        return s.as_dict()
+
+    def reset_skipgram_counts_stats(self):
+        _check(lib().bpe_reset_skipgram_counts_stats(self._ctx), 'bpe_reset_skipgram_counts_stats')
 
     def clear_corpus(self):
         _check(lib().bpe_clear_corpus(self._ctx), 'bpe_clear_corpus')
@@ -1800,6 +1876,85 @@ class Encoder:
     def reset_skipgram_stats(self):
         _check(lib().bpe_encoder_reset_skipgram_stats(self._enc), 'bpe_encoder_reset_skipgram_stats')
 
+    # skip-gram pair counts (include/bpe.h "skip-gram pair counts"): values in [0, dim) -> every distinct
+    # (target, context) pair in ascending order with its count, (targets int32, contexts int32, counts int64)
+    def skipgram_counts(self, vals, off, window, dim):
+        """The counts alone (bpe_encoder_skipgram_counts): texts vals[off[k]:off[k+1]] (int32 vector
+        indices or ids in [0, dim)) -> (targets, contexts, counts).  The sizing call, then the real one."""
+        vals = _i32(vals).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        src = vals if vals.size else np.zeros(1, np.int32)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_counts_host('bpe_encoder_skipgram_counts', lambda t, c, k, cap, need: lib().bpe_encoder_skipgram_counts(
+            self._enc, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), int(dim), t, c, k, cap, need))
+
+    def skipgram_counts_tensors(self, vals, off, window, dim, out=None):
+        """Device form (bpe_encoder_skipgram_counts_device): vals a torch int32 tensor and off a torch
+        int64 tensor on the encoder's device -> (targets, contexts, counts) tensors there.  out:
+        (int32, int32, int64) contiguous tensors on the device to write into (views of them come
+        back), else a sizing call runs first."""
+        import torch
+        if vals.dtype != torch.int32 or off.dtype != torch.int64:
+            raise BpeError('skipgram_counts_tensors takes int32 values and int64 offsets', ERR_ARG)
+        if not (vals.is_cuda and off.is_cuda and vals.device.index == self.device and off.device.index == self.device):
+            raise BpeError('skipgram_counts_tensors takes tensors on the encoder\'s device', ERR_ARG)
+        if not vals.is_contiguous():
+            vals = vals.contiguous()
+        off = off.contiguous()
+        vp = vals.data_ptr() if vals.numel() else None
+        return _skipgram_counts_device('bpe_encoder_skipgram_counts_device', lambda t, c, k, cap, need: lib().bpe_encoder_skipgram_counts_device(
+            self._enc, vp, off.data_ptr(), off.numel() - 1, int(window), int(dim), t, c, k, cap, need), self.device, out)
+
+    def skipgram_counts_text(self, texts, window, kind, dim):
+        """texts: a list of str, encoded and counted on the device (bpe_skipgram_counts_text_batch)."""
+        kind = self._KINDS[kind]
+        units, off = _units_flat(texts)
+        src = units if units.size else np.zeros(1, np.uint16)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_counts_host('bpe_skipgram_counts_text_batch', lambda t, c, k, cap, need: lib().bpe_skipgram_counts_text_batch(
+            self._enc, kind, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), int(dim), t, c, k, cap,
+            need))
+
+    def skipgram_counts_text_tensors(self, units, off, window, kind, dim, out=None):
+        """Device form (bpe_skipgram_counts_text_batch_device): torch int16 or uint16 units and int64
+        offsets on the encoder's device; no value touches the host."""
+        kind = self._KINDS[kind]
+        units, off = _units_tensors(units, off, 'skipgram_counts_text_tensors', self.device)
+        up = units.data_ptr() if units.numel() else None
+        return _skipgram_counts_device('bpe_skipgram_counts_text_batch_device', lambda t, c, k, cap, need: lib().bpe_skipgram_counts_text_batch_device(
+            self._enc, kind, up, off.data_ptr(), off.numel() - 1, int(window), int(dim), t, c, k, cap, need),
+            self.device, out)
+
+    def skipgram_counts_utf8(self, texts, off=None, window=2, kind='vectors', dim=None):
+        """skipgram_counts_text for UTF-8 (bpe_skipgram_counts_utf8_batch): texts a list of bytes, or
+        the flat form (uint8 array, int64 offsets)."""
+        kind = self._KINDS[kind]
+        data, off = _utf8_flat(texts, off)
+        src = data if data.size else np.zeros(1, np.uint8)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        return _skipgram_counts_host('bpe_skipgram_counts_utf8_batch', lambda t, c, k, cap, need: lib().bpe_skipgram_counts_utf8_batch(
+            self._enc, kind, src.ctypes.data, off.ctypes.data_as(i64p), len(off) - 1, int(window), int(dim), t, c, k, cap,
+            need))
+
+    def skipgram_counts_utf8_tensors(self, data, off, window, kind, dim, out=None):
+        """Device form (bpe_skipgram_counts_utf8_batch_device): torch uint8 bytes and int64 offsets on
+        the encoder's device."""
+        kind = self._KINDS[kind]
+        data, off = _utf8_tensors(data, off, 'skipgram_counts_utf8_tensors', self.device)
+        dp = data.data_ptr() if data.numel() else None
+        return _skipgram_counts_device('bpe_skipgram_counts_utf8_batch_device', lambda t, c, k, cap, need: lib().bpe_skipgram_counts_utf8_batch_device(
+            self._enc, kind, dp, off.data_ptr(), off.numel() - 1, int(window), int(dim), t, c, k, cap, need),
+            self.device, out)
+
+    def skipgram_counts_stats(self):
+        s = SkipgramCountsStats()
+        _check(lib().bpe_encoder_get_skipgram_counts_stats(self._enc, ctypes.byref(s)),
+               'bpe_encoder_get_skipgram_counts_stats')
+        return s.as_dict()
+
+    def reset_skipgram_counts_stats(self):
+        _check(lib().bpe_encoder_reset_skipgram_counts_stats(self._enc), 'bpe_encoder_reset_skipgram_counts_stats')
+
 
 def _skipgram_host(what, call, n):
     """A skip-gram host form: call(targets, contexts, cap, pair_off) -> rc.  The sizing call, then the
@@ -1843,6 +1998,49 @@ def _skipgram_device(what, call, n, device, out=None):
     _check(call(t.data_ptr() if cap else None, c.data_ptr() if cap else None, cap, off.data_ptr(), ctypes.byref(need)),
            what)
     return t[:need.value], c[:need.value], off
+
+
+def _skipgram_counts_host(what, call):
+    """A pair-count host form: call(targets, contexts, counts, cap, needed) -> rc.  The sizing call,
+    then the real one -> (targets int32, contexts int32, counts int64)."""
+    need = ctypes.c_int64()
+    rc = call(None, None, None, 0, ctypes.byref(need))
+    if rc != ERR_ARG or need.value <= 0:
+        _check(rc, what)
+    t, c = np.empty(need.value, np.int32), np.empty(need.value, np.int32)
+    k = np.empty(need.value, np.int64)
+    if need.value:
+        _check(call(t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, ctypes.byref(need)), what)
+    return t, c, k
+
+
+def _skipgram_counts_device(what, call, device, out=None):
+    """A pair-count device form: call(d_targets, d_contexts, d_counts, cap, needed) -> rc, into `out`
+    ((int32, int32, int64) contiguous tensors on the device) or, after a sizing call, into new
+    tensors -> (targets, contexts, counts) tensors."""
+    import torch
+    dev = torch.device('cuda', device)
+    need = ctypes.c_int64()
+    torch.cuda.synchronize(dev)   # (encoders and contexts run on streams of their own)
+    if out is None:
+        rc = call(None, None, None, 0, ctypes.byref(need))
+        if rc != ERR_ARG or need.value <= 0:
+            _check(rc, what)
+        t = torch.empty(need.value, dtype=torch.int32, device=dev)
+        c = torch.empty(need.value, dtype=torch.int32, device=dev)
+        k = torch.empty(need.value, dtype=torch.int64, device=dev)
+        if not need.value:
+            return t, c, k
+    else:
+        t, c, k = out
+        for x, dt in ((t, torch.int32), (c, torch.int32), (k, torch.int64)):
+            if x.dtype != dt or not x.is_cuda or x.device.index != device or not x.is_contiguous():
+                raise BpeError('%s takes contiguous (int32, int32, int64) tensors on the device as out' % what, ERR_ARG)
+    cap = min(t.numel(), c.numel(), k.numel())
+    torch.cuda.synchronize(dev)
+    _check(call(t.data_ptr() if cap else None, c.data_ptr() if cap else None, k.data_ptr() if cap else None, cap,
+                ctypes.byref(need)), what)
+    return t[:need.value], c[:need.value], k[:need.value]
 
 
 def lines_mode(mode):

@@ -474,6 +474,7 @@ k_text_ooff(const int64_t *__restrict__ ooff, const int64_t *__restrict__ seg_of
 #include "bpe_utf8.hip.h"   // text as UTF-8: bytes -> units in front of it (bpe_encode_utf8_batch)
 #include "bpe_lines.hip.h"  // lines as samples: texts -> samples (bpe_encoder_split_lines)
 #include "bpe_skipgram.hip.h"   // skip-gram pairs from the values behind it (bpe_encoder_skipgram)
+#include "bpe_skipgram_counts.hip.h"   // ... and their counts (bpe_encoder_skipgram_counts)
 
 struct bpe_encoder {
     int device = 0;
@@ -512,6 +513,7 @@ struct bpe_encoder {
     LinesCall ln_pending;                     // a restore's split, counted when the restore is done
     bool ln_pending_u8 = false;               // ... which had a transcode in front
     SgState sg;                               // skip-gram pairs (bpe_encoder_skipgram and the forms from text)
+    SgcState sgc;                             // skip-gram pair counts (bpe_encoder_skipgram_counts and the forms from text)
     // long texts in segments (BPE_LONG_SPLIT): first and last base id of every id (identity until
     // a merge makes it), the ids made so far, and the tables k_cuts reads (built and uploaded
     // with the rank table when dirty)
@@ -1783,6 +1785,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     u8_free(E->u8);
     ln_free(E->ln);
     sg_free(E->sg);
+    sgc_free(E->sgc);
     if (E->ev0) (void)hipEventDestroy(E->ev0);
     if (E->ev1) (void)hipEventDestroy(E->ev1);
     for (int i = 0; i < 2; ++i)
@@ -2286,6 +2289,102 @@ int bpe_encoder_get_skipgram_stats(bpe_encoder *E, bpe_skipgram_stats *out) {
 int bpe_encoder_reset_skipgram_stats(bpe_encoder *E) {
     if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
     E->sg.st = bpe_skipgram_stats{};
+    return BPE_OK;
+}
+
+// ---- skip-gram pair counts (include/bpe.h; csrc/bpe_skipgram_counts.hip.h) --------------------------
+
+int bpe_encoder_skipgram_counts(bpe_encoder *E, const int32_t *vals, const int64_t *off, int64_t n_texts, int window,
+                                int dim, int32_t *targets, int32_t *contexts, int64_t *counts, int64_t cap,
+                                int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->sgc.st.calls++;
+    int rc = sg_check_window(window);
+    if (rc || (rc = sgc_check_dim(dim))) return rc;
+    if (!sgc_outputs_ok(targets, contexts, counts, cap, needed))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram counts output arguments");
+    SgCall J;
+    J.window = window;
+    if ((rc = sg_stage_host(E->sg, E->stream, vals, off, n_texts, J))) return rc;
+    return sgc_host_form(E->sg, E->sgc, E->stream, J, dim, targets, contexts, counts, cap, needed);
+}
+
+int bpe_encoder_skipgram_counts_device(bpe_encoder *E, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                       int window, int dim, int32_t *d_targets, int32_t *d_contexts, int64_t *d_counts,
+                                       int64_t cap, int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->sgc.st.calls++;
+    if (!sgc_outputs_ok(d_targets, d_contexts, d_counts, cap, needed))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram counts output arguments");
+    SgCall J;
+    J.d_vals = d_vals, J.d_off = d_off, J.n_texts = n_texts, J.window = window;
+    return sgc_device_form(E->sg, E->sgc, E->stream, J, dim, d_targets, d_contexts, d_counts, cap, needed);
+}
+
+namespace {
+
+int sgc_text(bpe_encoder *E, int kind, const void *src, const int64_t *off, int64_t n, bool utf8, int window, int dim,
+             int32_t *targets, int32_t *contexts, int64_t *counts, int64_t cap, bool dev, int64_t *needed) {
+    if (!E || !needed) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *needed = 0;
+    ENC_TRY(hipSetDevice(E->device));
+    E->sgc.st.calls++;
+    int rc = sg_check_window(window);
+    if (rc || (rc = sgc_check_dim(dim))) return rc;
+    if (!sgc_outputs_ok(targets, contexts, counts, cap, needed))
+        return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram counts output arguments");
+    SgCall J;
+    Utf8Call U;
+    J.window = window;
+    if ((rc = sg_encode(E, kind, src, off, n, dev, utf8, J, &U))) return rc;
+    rc = dev ? sgc_device_form(E->sg, E->sgc, E->stream, J, dim, targets, contexts, counts, cap, needed)
+             : sgc_host_form(E->sg, E->sgc, E->stream, J, dim, targets, contexts, counts, cap, needed);
+    if (rc) return rc;
+    if (utf8) u8_commit(E->u8, U);
+    return BPE_OK;
+}
+
+}  // namespace
+
+int bpe_skipgram_counts_text_batch(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off,
+                                   int64_t n_texts, int window, int dim, int32_t *targets, int32_t *contexts,
+                                   int64_t *counts, int64_t cap, int64_t *needed) {
+    return sgc_text(E, kind, units, off, n_texts, false, window, dim, targets, contexts, counts, cap, false, needed);
+}
+
+int bpe_skipgram_counts_text_batch_device(bpe_encoder *E, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                          int64_t n_texts, int window, int dim, int32_t *d_targets,
+                                          int32_t *d_contexts, int64_t *d_counts, int64_t cap, int64_t *needed) {
+    return sgc_text(E, kind, d_units, d_off, n_texts, false, window, dim, d_targets, d_contexts, d_counts, cap, true,
+                    needed);
+}
+
+int bpe_skipgram_counts_utf8_batch(bpe_encoder *E, int kind, const uint8_t *bytes, const int64_t *off,
+                                   int64_t n_texts, int window, int dim, int32_t *targets, int32_t *contexts,
+                                   int64_t *counts, int64_t cap, int64_t *needed) {
+    return sgc_text(E, kind, bytes, off, n_texts, true, window, dim, targets, contexts, counts, cap, false, needed);
+}
+
+int bpe_skipgram_counts_utf8_batch_device(bpe_encoder *E, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                          int64_t n_texts, int window, int dim, int32_t *d_targets,
+                                          int32_t *d_contexts, int64_t *d_counts, int64_t cap, int64_t *needed) {
+    return sgc_text(E, kind, d_bytes, d_off, n_texts, true, window, dim, d_targets, d_contexts, d_counts, cap, true,
+                    needed);
+}
+
+int bpe_encoder_get_skipgram_counts_stats(bpe_encoder *E, bpe_skipgram_counts_stats *out) {
+    if (!E || !out) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    *out = E->sgc.st;
+    return BPE_OK;
+}
+
+int bpe_encoder_reset_skipgram_counts_stats(bpe_encoder *E) {
+    if (!E) return bpe_fail(BPE_ERR_ARG, "bpe native: null argument");
+    E->sgc.st = bpe_skipgram_counts_stats{};
     return BPE_OK;
 }
 

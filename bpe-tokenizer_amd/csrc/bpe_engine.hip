@@ -18,6 +18,7 @@
 #include "bpe_utf8.hip.h"     // text as UTF-8: bytes -> units in front of the ingest (bpe_add_utf8_batch)
 #include "bpe_lines.hip.h"    // lines as samples: texts -> samples in front of the ingest (bpe_add_lines_batch)
 #include "bpe_skipgram.hip.h" // skip-gram pairs behind the export (bpe_export_skipgram)
+#include "bpe_skipgram_counts.hip.h" // ... and their counts (bpe_export_skipgram_counts)
 #include "bpe_tools.h"
 
 namespace bpe_step {
@@ -257,6 +258,7 @@ struct bpe_ctx {
     Utf8State *u8 = nullptr;
     LinesState *ln = nullptr;
     SgState *sg = nullptr;    // skip-gram pairs of exported samples (made by its first call)
+    SgcState *sgc = nullptr;  // ... and their counts
 };
 
 void ingest_free(bpe_ctx *c);
@@ -2878,6 +2880,10 @@ int bpe_destroy(bpe_ctx *c) {
         sg_free(*c->sg);
         delete c->sg;
     }
+    if (c->sgc) {
+        sgc_free(*c->sgc);
+        delete c->sgc;
+    }
     void *ptrs[] = {c->d_ids, c->d_tmp, c->d_len16, c->d_partials, c->d_spill, c->d_hot,
                     c->d_total, c->d_sums, c->d_carry, c->d_outoff, c->d_res, c->d_cand,
                     c->d_heavy, c->d_cold_flags, c->cold.slots, c->cold.dkeys, c->cold.dcounts,
@@ -4880,6 +4886,26 @@ int skipgram_kind(int kind) {
     return fail(BPE_ERR_ARG, "bpe native: a skip-gram export takes BPE_EXPORT_IDS or BPE_EXPORT_VECTORS");
 }
 
+// The samples' values through the export into its scratch, as J's batch: what the pairs are expanded
+// and counted from.  The caller holds an ExportSync.
+int skipgram_values(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                    SgCall &J) {
+    ExportState *X;
+    int rc = export_state(c, &X);
+    if (rc) return rc;
+    X->st.calls++;
+    if ((rc = export_prepare(c, X, kind, idx, n, tvi, n_index))) return rc;
+    const int64_t n_vals = X->needed;
+    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, exp_align((size_t)std::max<int64_t>(n_vals, 1) * 4)))) return rc;
+    if ((rc = export_emit(c, X, kind, X->d_vals))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = export_timing(X))) return rc;
+    X->st.samples += n;
+    X->st.values += n_vals;
+    J.d_vals = reinterpret_cast<const int32_t *>(X->d_vals), J.d_off = X->d_off, J.n_texts = n;
+    return BPE_OK;
+}
+
 int export_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
                     int window, int32_t *targets, int32_t *contexts, int64_t cap, int64_t *pair_off,
                     int64_t *needed_out, bool dev) {
@@ -4891,21 +4917,11 @@ int export_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const i
     if ((rc = skipgram_state(c, &S))) return rc;
     S->st.calls++;
     if ((rc = sg_check_window(window)) || (rc = skipgram_kind(kind))) return rc;
-    ExportState *X;
-    if ((rc = export_state(c, &X))) return rc;
-    X->st.calls++;
     hipStream_t s = c->stream;
     ExportSync guard{s};
-    if ((rc = export_prepare(c, X, kind, idx, n, tvi, n_index))) return rc;
-    const int64_t n_vals = X->needed;
-    if ((rc = export_grow(c, &X->d_vals, &X->vals_bytes, exp_align((size_t)std::max<int64_t>(n_vals, 1) * 4)))) return rc;
-    if ((rc = export_emit(c, X, kind, X->d_vals))) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((rc = export_timing(X))) return rc;
-    X->st.samples += n;
-    X->st.values += n_vals;
     SgCall J;
-    J.d_vals = reinterpret_cast<const int32_t *>(X->d_vals), J.d_off = X->d_off, J.n_texts = n, J.window = window;
+    J.window = window;
+    if ((rc = skipgram_values(c, kind, idx, n, tvi, n_index, J))) return rc;
     if (!dev) return sg_host_form(*S, s, J, targets, contexts, cap, pair_off);
     J.d_t = cap ? targets : nullptr, J.d_c = cap ? contexts : nullptr, J.d_poff = pair_off, J.cap = cap;
     return sg_device_form(*S, s, J, needed_out);
@@ -4930,6 +4946,60 @@ int multi_skipgram(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const in
     J.window = window;
     if ((rc = sg_stage_host(*S, t->stream, vals.data(), off.data(), n, J))) return rc;
     return sg_host_form(*S, t->stream, J, targets, contexts, cap, pair_off);
+}
+
+// ---- skip-gram pair counts of corpus samples (bpe_export_skipgram_counts): the same export, then
+// bpe_skipgram_counts.hip.h on the context's stream --------------------------------------------------
+int skipgram_counts_state(bpe_ctx *c, SgState **S, SgcState **C) {
+    if (!c->sgc) c->sgc = new SgcState();
+    *C = c->sgc;
+    return skipgram_state(c, S);
+}
+
+int export_skipgram_counts(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                           int window, int dim, int32_t *targets, int32_t *contexts, int64_t *counts, int64_t cap,
+                           int64_t *needed, bool dev) {
+    if (!c || !sgc_outputs_ok(targets, contexts, counts, cap, needed))
+        return fail(BPE_ERR_ARG, "bpe native: bad export_skipgram_counts arguments");
+    *needed = 0;
+    int rc = set_device(c);
+    if (rc) return rc;
+    SgState *S;
+    SgcState *C;
+    if ((rc = skipgram_counts_state(c, &S, &C))) return rc;
+    C->st.calls++;
+    if ((rc = sg_check_window(window)) || (rc = sgc_check_dim(dim)) || (rc = skipgram_kind(kind))) return rc;
+    hipStream_t s = c->stream;
+    ExportSync guard{s};
+    SgCall J;
+    J.window = window;
+    if ((rc = skipgram_values(c, kind, idx, n, tvi, n_index, J))) return rc;
+    if (!dev) return sgc_host_form(*S, *C, s, J, dim, targets, contexts, counts, cap, needed);
+    return sgc_device_form(*S, *C, s, J, dim, targets, contexts, counts, cap, needed);
+}
+
+// A multi-device context: the samples through its host export, shard by shard, counted on its first
+// shard's device.
+int multi_skipgram_counts(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *tvi, int32_t n_index,
+                          int window, int dim, int32_t *targets, int32_t *contexts, int64_t *counts, int64_t cap,
+                          int64_t *needed) {
+    *needed = 0;
+    bpe_ctx *t = multi_first_shard(c->multi);
+    int rc = set_device(t);
+    if (rc) return rc;
+    SgState *S;
+    SgcState *C;
+    if ((rc = skipgram_counts_state(t, &S, &C))) return rc;
+    C->st.calls++;
+    if ((rc = sg_check_window(window)) || (rc = sgc_check_dim(dim)) || (rc = skipgram_kind(kind))) return rc;
+    std::vector<int64_t> off;
+    std::vector<int32_t> vals;
+    if ((rc = multi_export_values(c->multi, kind, idx, n, tvi, n_index, vals, off))) return rc;
+    if ((rc = set_device(t))) return rc;
+    SgCall J;
+    J.window = window;
+    if ((rc = sg_stage_host(*S, t->stream, vals.data(), off.data(), n, J))) return rc;
+    return sgc_host_form(*S, *C, t->stream, J, dim, targets, contexts, counts, cap, needed);
 }
 
 }  // namespace
@@ -5026,6 +5096,41 @@ int bpe_reset_skipgram_stats(bpe_ctx *c) {
     if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
     bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
     if (t->sg) t->sg->st = bpe_skipgram_stats{};
+    return BPE_OK;
+}
+
+int bpe_export_skipgram_counts(bpe_ctx *c, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                               int32_t n_index, int window, int dim, int32_t *targets, int32_t *contexts,
+                               int64_t *counts, int64_t cap, int64_t *needed) {
+    if (c && c->multi && n >= 0 && sgc_outputs_ok(targets, contexts, counts, cap, needed))
+        return multi_skipgram_counts(c, kind, idx, n, to_vector_index, n_index, window, dim, targets, contexts, counts,
+                                     cap, needed);
+    return export_skipgram_counts(c, kind, idx, n, to_vector_index, n_index, window, dim, targets, contexts, counts, cap,
+                                  needed, false);
+}
+
+int bpe_export_skipgram_counts_device(bpe_ctx *c, int kind, const int64_t *idx, int64_t n,
+                                      const int32_t *to_vector_index, int32_t n_index, int window, int dim,
+                                      int32_t *d_targets, int32_t *d_contexts, int64_t *d_counts, int64_t cap,
+                                      int64_t *needed) {
+    if (c && c->multi)
+        return fail(BPE_ERR_ARG, "bpe native: the device form of an export on a multi-device context "
+                                 "(its shards sit on different devices: take the host form)");
+    return export_skipgram_counts(c, kind, idx, n, to_vector_index, n_index, window, dim, d_targets, d_contexts,
+                                  d_counts, cap, needed, true);
+}
+
+int bpe_get_skipgram_counts_stats(bpe_ctx *c, bpe_skipgram_counts_stats *out) {
+    if (!c || !out) return fail(BPE_ERR_ARG, "bpe native: null argument");
+    const bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    *out = t->sgc ? t->sgc->st : bpe_skipgram_counts_stats{};
+    return BPE_OK;
+}
+
+int bpe_reset_skipgram_counts_stats(bpe_ctx *c) {
+    if (!c) return fail(BPE_ERR_ARG, "bpe native: null context");
+    bpe_ctx *t = c->multi ? multi_first_shard(c->multi) : c;
+    if (t->sgc) t->sgc->st = bpe_skipgram_counts_stats{};
     return BPE_OK;
 }
 

@@ -31,6 +31,8 @@ export declare function fileContentToCorpus(content: string | Buffer): string
 export type CorpusHelperName = 'linesToCorpus' | 'linesTrimmedToCorpus' | 'fileContentToCorpus'
 /** two planes of vector indices and one pair offset per text, plus the total */
 export type SkipGramPairs = { targets: Int32Array; contexts: Int32Array; offsets: Float64Array }
+/** every distinct (target, context) pair in ascending order with its count (exact to 2^53) */
+export type SkipGramCounts = { targets: Int32Array; contexts: Int32Array; counts: Float64Array }
 export declare function linesToCorpus(text: string): string[]
 export declare function linesTrimmedToCorpus(text: string): string[]
 export declare class BPETokenizer {
@@ -133,6 +135,14 @@ export declare class BPETokenizer {
   skipGramBatch(texts: string[], window?: number): SkipGramPairs
   skipGramBatchUtf8(buffers: Array<Buffer | Uint8Array>, window?: number): SkipGramPairs
   corpusToSkipGramBatch(indices?: number[] | null, window?: number): SkipGramPairs
+  /**
+   * skip-gram pair counts on the GPU: every distinct pair of skipGramBatch / skipGramBatchUtf8 /
+   * corpusToSkipGramBatch with the number of times it occurs, without the pairs being made.  Errors
+   * and the JS route are those of the pair methods.
+   */
+  skipGramCountsBatch(texts: string[], window?: number): SkipGramCounts
+  skipGramCountsBatchUtf8(buffers: Array<Buffer | Uint8Array>, window?: number): SkipGramCounts
+  corpusToSkipGramCounts(indices?: number[] | null, window?: number): SkipGramCounts
   restoreMerge(compactMerge: CompactMerge): void
 }
 export declare function compactMerge(merge: MergeToken): CompactMerge

@@ -38,6 +38,10 @@ const {
   expandSkipGram,
   skipGramTextsMaybeOnDevice,
   corpusSkipGramOnDevice,
+  skipGramCountsDim,
+  countSkipGram,
+  skipGramCountsMaybeOnDevice,
+  corpusSkipGramCountsOnDevice,
   decodeVectorsUtf8OnDevice,
   loadNativeUtf8,
   loadNativeLines,
@@ -268,6 +272,22 @@ class BPETokenizer {
     let out = corpusSkipGramOnDevice(this, this.engine(), indices, window)
     if (out) return out
     return expandSkipGram(this.corpusToVectorBatch(indices), window)
+  }
+
+  /**
+   * @description the trained corpus as skip-gram pair counts, on the GPU (bpe_export_skipgram_counts):
+   * every distinct (target, context) pair of `this.corpusToSkipGramBatch(indices, window)` with the
+   * number of times it occurs, in ascending (target, context) order, as
+   * `{targets: Int32Array, contexts: Int32Array, counts: Float64Array}` (exact to 2^53).  Without the
+   * addon (or with BPE_ENCODE_DEVICE=0) the pairs are counted in JS, with the same results.
+   */
+  corpusToSkipGramCounts(indices, window) {
+    window = skipGramWindow(window)
+    if (!this._engine) return countSkipGram([], window, 1)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let out = corpusSkipGramCountsOnDevice(this, this.engine(), indices, window)
+    if (out) return out
+    return countSkipGram(this.corpusToVectorBatch(indices), window, skipGramCountsDim(this))
   }
 
   set corpus_in_code(samples) {
@@ -783,6 +803,35 @@ class BPETokenizer {
     let out = skipGramTextsMaybeOnDevice(this, this.merge_tokens, tokenTriple, buffers, window, true)
     if (out) return out
     return expandSkipGram(this.encodeToVectorBatchUtf8(buffers), window)
+  }
+
+  /**
+   * @description skip-gram pair counts of many texts at once on the GPU
+   * (bpe_skipgram_counts_text_batch): every distinct (target, context) pair of
+   * `this.skipGramBatch(texts, window)` with the number of times it occurs, in ascending (target,
+   * context) order, as `{targets: Int32Array, contexts: Int32Array, counts: Float64Array}` (exact to
+   * 2^53); the pairs themselves are never made.  The errors are encodeToVectorBatch's; when the device
+   * cannot take the call, its vectors are counted in JS, with the same results.
+   */
+  skipGramCountsBatch(texts, window) {
+    window = skipGramWindow(window)
+    if (texts.length === 0) return countSkipGram([], window, 1)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    if (texts.every(t => typeof t === 'string')) {
+      let out = skipGramCountsMaybeOnDevice(this, this.merge_tokens, tokenTriple, texts, window, false)
+      if (out) return out
+    }
+    return countSkipGram(this.encodeToVectorBatch(texts), window, skipGramCountsDim(this))
+  }
+
+  /** @description skipGramCountsBatch for UTF-8 bytes (bpe_skipgram_counts_utf8_batch) */
+  skipGramCountsBatchUtf8(buffers, window) {
+    window = skipGramWindow(window)
+    if (buffers.length === 0) return countSkipGram([], window, 1)
+    if (!this.to_vector_index) this.compactVectorIndex()
+    let out = skipGramCountsMaybeOnDevice(this, this.merge_tokens, tokenTriple, buffers, window, true)
+    if (out) return out
+    return countSkipGram(this.encodeToVectorBatchUtf8(buffers), window, skipGramCountsDim(this))
   }
 
   /** core.ts:447-453 */

@@ -84,6 +84,15 @@ function loadNativeSkipGram() {
   return nativeSkipGram
 }
 
+// the skip-gram counts addon (addon/bpe_skipgram_counts_napi.node: skipGramCountsTextBatch and
+// skipGramCountsUtf8Batch on a text encoder handle, exportSkipGramCounts on an engine handle)
+let nativeSkipGramCounts = null
+function loadNativeSkipGramCounts() {
+  if (!nativeSkipGramCounts)
+    nativeSkipGramCounts = require(path.join(__dirname, '..', 'addon', 'bpe_skipgram_counts_napi.node'))
+  return nativeSkipGramCounts
+}
+
 let nativeText = null
 function loadNativeText() {
   if (!nativeText) nativeText = require(path.join(__dirname, '..', 'addon', 'bpe_text_napi.node'))
@@ -678,6 +687,100 @@ function corpusSkipGramOnDevice(owner, engine, indices, window) {
   }
 }
 
+/** the `dim` of an owner's pair counts: its vectors are indices below it */
+function skipGramCountsDim(owner) {
+  let dim = 1
+  owner.to_vector_index.forEach(v => {
+    if (v + 1 > dim) dim = v + 1
+  })
+  return dim
+}
+
+/**
+ * Vectors (one array per text) -> every distinct (target, context) pair of expandSkipGram with the
+ * number of times it occurs, in ascending (target, context) order, in JS.  What the device forms
+ * compute; the route of a call the device cannot take.
+ */
+function countSkipGram(vectors, window, dim) {
+  let { targets, contexts } = expandSkipGram(vectors, window)
+  let cells = new Map()
+  for (let p = 0; p < targets.length; p++) {
+    let key = targets[p] * dim + contexts[p]
+    cells.set(key, (cells.get(key) || 0) + 1)
+  }
+  let keys = Float64Array.from(cells.keys()).sort()
+  let out = {
+    targets: new Int32Array(keys.length),
+    contexts: new Int32Array(keys.length),
+    counts: new Float64Array(keys.length),
+  }
+  keys.forEach((key, u) => {
+    out.targets[u] = Math.floor(key / dim)
+    out.contexts[u] = key % dim
+    out.counts[u] = cells.get(key)
+  })
+  return out
+}
+
+/**
+ * skipGramTextsMaybeOnDevice for the counts (bpe_skipgram_counts_text_batch / _utf8_batch) ->
+ * {targets, contexts, counts}, or null when the device cannot take the call.
+ */
+function skipGramCountsMaybeOnDevice(owner, list, tripleOf, texts, window, utf8) {
+  if (ENCODE_DEVICE === '0') return null
+  if (
+    ENCODE_DEVICE !== '1' &&
+    (owner._tenc_failed === true || (owner._tenc_failed && owner._tenc_failed === list))
+  )
+    return null
+  try {
+    let addon = loadNativeSkipGramCounts()
+    let enc = syncTextEncoder(owner, list, tripleOf)
+    let [data, off] = utf8 ? buffersToBytes(texts) : textsToUnits(texts)
+    let dim = skipGramCountsDim(owner)
+    let res = utf8
+      ? addon.skipGramCountsUtf8Batch(enc, data, off, window, dim, 1)
+      : addon.skipGramCountsTextBatch(enc, data, off, window, dim, 1)
+    return { targets: res[0], contexts: res[1], counts: res[2] }
+  } catch (e) {
+    let msg = String((e && e.message) || e)
+    let m = /^unknown token, char: U\+([0-9A-F]+) \(text \d+, unit \d+\)$/.exec(msg)
+    if (m) throw new Error('unknown token, char: ' + JSON.stringify(String.fromCodePoint(parseInt(m[1], 16))))
+    m = /^unknown token index: (-?\d+) \(text \d+, position \d+\)$/.exec(msg)
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    if (ENCODE_DEVICE === '1') throw e
+    return null
+  }
+}
+
+/**
+ * corpusSkipGramOnDevice for the counts (bpe_export_skipgram_counts) -> {targets, contexts, counts},
+ * or null when there is no addon to ask.
+ */
+function corpusSkipGramCountsOnDevice(owner, engine, indices, window) {
+  if (!exportAddon()) return null
+  let addon
+  try {
+    addon = loadNativeSkipGramCounts()
+  } catch (e) {
+    if (ENCODE_DEVICE === '1') throw e
+    return null
+  }
+  let index = new Int32Array(owner.to_vector_index.length).fill(-1)
+  owner.to_vector_index.forEach((v, i) => {
+    index[i] = v
+  })
+  try {
+    let dim = skipGramCountsDim(owner)
+    let res = addon.exportSkipGramCounts(engine, EXPORT_VECTORS, exportIndices(indices), index, window, dim)
+    return { targets: res[0], contexts: res[1], counts: res[2] }
+  } catch (e) {
+    let m = /^unknown token index: (\d+) \(sample \d+, position \d+\)$/.exec(String(e && e.message))
+    if (m) throw new Error(`unknown token index: ${m[1]}`)
+    throw e
+  }
+}
+
 /** engine ids -> code point string (code = index + 1, core.ts:149) */
 function idsToCode(ids, begin, end) {
   let parts = []
@@ -744,4 +847,9 @@ module.exports = {
   expandSkipGram,
   skipGramTextsMaybeOnDevice,
   corpusSkipGramOnDevice,
+  loadNativeSkipGramCounts,
+  skipGramCountsDim,
+  countSkipGram,
+  skipGramCountsMaybeOnDevice,
+  corpusSkipGramCountsOnDevice,
 }

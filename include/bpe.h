@@ -1060,6 +1060,91 @@ int bpe_encoder_reset_skipgram_stats(bpe_encoder *enc);
 int bpe_get_skipgram_stats(bpe_ctx *ctx, bpe_skipgram_stats *out);
 int bpe_reset_skipgram_stats(bpe_ctx *ctx);
 
+/* ---- skip-gram pair counts -------------------------------------------------------------------------
+ * What the model those pairs feed needs of them (example/skip-gram.ts: one-hot -> linear -> linear ->
+ * softmax): over any set of pairs its loss is -sum C[t,c] log p(c | t), with C[t,c] the number of times
+ * the pair (t, c) occurs.  A step, an epoch, PPMI/SVD or GloVe need the counts, not the pairs: at most
+ * dim^2 cells whatever the batch, where the planes of the pair forms run to gigabytes.  The counts are
+ * made on the device and the pairs are never written anywhere.
+ *
+ * For a batch of texts, a window w in [1, BPE_SKIPGRAM_MAX_WINDOW] and a dimension `dim`: the multiset of
+ * (target, context) pairs the rule above emits (pairs never cross texts), as every distinct pair with
+ * its count in ascending (target, context) order: targets[U] and contexts[U] int32, counts[U] int64.
+ * sum counts == P, the pairs the pair forms would write; C[x,y] == C[y,x].  The order is fixed, so the
+ * output is bit-identical between runs and routes.
+ *
+ * Values must lie in [0, dim), 1 <= dim <= BPE_SKIPGRAM_COUNTS_MAX_DIM.  A value outside gives BPE_ERR_ARG
+ * and `skip-gram counts value V outside [0, dim) (text K, position I)`, the smallest such position of
+ * the batch, with nothing written.  A bad window, a dim out of range, decreasing or negative offsets:
+ * BPE_ERR_ARG with nothing written, as for the pair forms.
+ *
+ * Capacity and sizing follow bpe_encoder_skipgram: *needed (a host int64, in every form) is U; when U
+ * exceeds `cap` (the elements each plane holds) no plane element is written and BPE_ERR_ARG comes back;
+ * NULL planes with cap 0 are the sizing call.  The `_device` forms take and fill buffers on the owner's
+ * device (4-byte aligned values, targets and contexts, 8-byte aligned offsets and counts), run on the
+ * owner's stream and synchronise before returning.  The host forms are the device forms plus the copies.
+ * The planes reach the caller only after the range check and the capacity check.
+ *
+ * bpe_encoder_skipgram_counts takes values and offsets as bpe_encoder_skipgram does.
+ * bpe_skipgram_counts_text_batch and bpe_skipgram_counts_utf8_batch sit behind
+ * bpe_encode_text_batch_device / bpe_encode_utf8_batch_device into the encoder's scratch, exactly as the
+ * pair forms do; the encoder's errors and long-text mode are its own.
+ * bpe_export_skipgram_counts sits behind bpe_export_samples_device (kind BPE_EXPORT_IDS or
+ * BPE_EXPORT_VECTORS with to_vector_index; idx NULL for every sample) and keeps the export's read-only
+ * guarantee: a bpe_merge_until after it gives the merges it would have given without it.  A multi-device
+ * context takes the host form shard by shard and counts on its first shard's device; the device form
+ * refuses it with BPE_ERR_ARG.
+ *
+ * bpe_skipgram_counts_stats: `calls` counts every call (sizing and failed ones too); the other fields
+ * count the calls that passed their checks and wrote their planes: texts, values read, P, U, the keys
+ * that bypassed the LDS table for their global cell, and the HIP-event time of the kernels and the
+ * clearing of the accumulator (the encode's and the export's stay in their own stats).  A multi-device
+ * context reports its first shard's.
+ * The count kernel works on tiles of BPE_SKIPGRAM_COUNTS_TILE positions with an LDS table of
+ * BPE_SKIPGRAM_COUNTS_SLOTS slots (csrc/bpe_skipgram_counts.hip.h; exported for the tests, which place
+ * texts around the first and fill a tile past the second). */
+#define BPE_SKIPGRAM_COUNTS_MAX_DIM 16384
+#define BPE_SKIPGRAM_COUNTS_TILE 2048
+#define BPE_SKIPGRAM_COUNTS_SLOTS 4096
+typedef struct {
+    int64_t calls;            /* pair-count calls */
+    int64_t texts;            /* texts of the calls that wrote their planes */
+    int64_t values_in;        /* ... their values */
+    int64_t pairs_counted;    /* ... P: the pairs the pair forms would have written */
+    int64_t distinct_out;     /* ... U: the distinct pairs written */
+    int64_t lds_overflow;     /* ... keys that went past the LDS table to their global cell */
+    double kernel_ms;         /* HIP-event time of the kernels */
+} bpe_skipgram_counts_stats;
+int bpe_encoder_skipgram_counts(bpe_encoder *enc, const int32_t *vals, const int64_t *off, int64_t n_texts, int window,
+                                int dim, int32_t *targets, int32_t *contexts, int64_t *counts, int64_t cap,
+                                int64_t *needed);
+int bpe_encoder_skipgram_counts_device(bpe_encoder *enc, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                       int window, int dim, int32_t *d_targets, int32_t *d_contexts, int64_t *d_counts,
+                                       int64_t cap, int64_t *needed);
+int bpe_skipgram_counts_text_batch(bpe_encoder *enc, int kind, const uint16_t *units, const int64_t *off,
+                                   int64_t n_texts, int window, int dim, int32_t *targets, int32_t *contexts,
+                                   int64_t *counts, int64_t cap, int64_t *needed);
+int bpe_skipgram_counts_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                          int64_t n_texts, int window, int dim, int32_t *d_targets,
+                                          int32_t *d_contexts, int64_t *d_counts, int64_t cap, int64_t *needed);
+int bpe_skipgram_counts_utf8_batch(bpe_encoder *enc, int kind, const uint8_t *bytes, const int64_t *off,
+                                   int64_t n_texts, int window, int dim, int32_t *targets, int32_t *contexts,
+                                   int64_t *counts, int64_t cap, int64_t *needed);
+int bpe_skipgram_counts_utf8_batch_device(bpe_encoder *enc, int kind, const uint8_t *d_bytes, const int64_t *d_off,
+                                          int64_t n_texts, int window, int dim, int32_t *d_targets,
+                                          int32_t *d_contexts, int64_t *d_counts, int64_t cap, int64_t *needed);
+int bpe_export_skipgram_counts(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n, const int32_t *to_vector_index,
+                               int32_t n_index, int window, int dim, int32_t *targets, int32_t *contexts,
+                               int64_t *counts, int64_t cap, int64_t *needed);
+int bpe_export_skipgram_counts_device(bpe_ctx *ctx, int kind, const int64_t *idx, int64_t n,
+                                      const int32_t *to_vector_index, int32_t n_index, int window, int dim,
+                                      int32_t *d_targets, int32_t *d_contexts, int64_t *d_counts, int64_t cap,
+                                      int64_t *needed);
+int bpe_encoder_get_skipgram_counts_stats(bpe_encoder *enc, bpe_skipgram_counts_stats *out);
+int bpe_encoder_reset_skipgram_counts_stats(bpe_encoder *enc);
+int bpe_get_skipgram_counts_stats(bpe_ctx *ctx, bpe_skipgram_counts_stats *out);
+int bpe_reset_skipgram_counts_stats(bpe_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
