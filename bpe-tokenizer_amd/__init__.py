@@ -73,6 +73,10 @@ C_API = [
     'bpe_skipgram_counts_text_batch_device', 'bpe_skipgram_counts_utf8_batch', 'bpe_skipgram_counts_utf8_batch_device',
     'bpe_export_skipgram_counts', 'bpe_export_skipgram_counts_device', 'bpe_encoder_get_skipgram_counts_stats',
     'bpe_encoder_reset_skipgram_counts_stats', 'bpe_get_skipgram_counts_stats', 'bpe_reset_skipgram_counts_stats',
+    'bpe_sgmodel_create', 'bpe_sgmodel_destroy', 'bpe_sgmodel_set_params', 'bpe_sgmodel_set_params_device',
+    'bpe_sgmodel_get_params', 'bpe_sgmodel_get_params_device', 'bpe_sgmodel_loss_grad', 'bpe_sgmodel_loss_grad_device',
+    'bpe_sgmodel_adam_step', 'bpe_sgmodel_adam_step_device', 'bpe_sgmodel_reset_optimizer', 'bpe_sgmodel_embed',
+    'bpe_sgmodel_embed_device', 'bpe_sgmodel_get_stats', 'bpe_sgmodel_reset_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -136,6 +140,8 @@ SKIPGRAM_SCAN_ROUND = 8192  # BPE_SKIPGRAM_SCAN_ROUND: texts per round of the sc
 SKIPGRAM_COUNTS_MAX_DIM = 16384  # BPE_SKIPGRAM_COUNTS_MAX_DIM: the largest `dim` of the skip-gram pair counts
 SKIPGRAM_COUNTS_TILE = 2048      # BPE_SKIPGRAM_COUNTS_TILE: positions per workgroup of the count kernel
 SKIPGRAM_COUNTS_SLOTS = 4096     # BPE_SKIPGRAM_COUNTS_SLOTS: slots of its LDS table
+SGM_MAX_EMBED = 256              # BPE_SGM_MAX_EMBED: the widest embedding of the skip-gram model
+SGM_TILE = 64                    # BPE_SGM_TILE: target rows / context columns per workgroup of its kernels
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
@@ -286,6 +292,15 @@ class SkipgramCountsStats(ctypes.Structure):
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
                 ('pairs_counted', ctypes.c_int64), ('distinct_out', ctypes.c_int64), ('lds_overflow', ctypes.c_int64),
                 ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramModelStats(ctypes.Structure):
+    """bpe_sgmodel_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('elements', ctypes.c_int64), ('pairs', ctypes.c_int64),
+                ('steps', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -514,6 +529,26 @@ def lib():
         'bpe_encoder_reset_skipgram_counts_stats': ([vp], ctypes.c_int),
         'bpe_get_skipgram_counts_stats': ([vp, ctypes.POINTER(SkipgramCountsStats)], ctypes.c_int),
         'bpe_reset_skipgram_counts_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_create': ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)], ctypes.c_int),
+        'bpe_sgmodel_destroy': ([vp], ctypes.c_int),
+        'bpe_sgmodel_set_params': ([vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_set_params_device': ([vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_get_params': ([vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_get_params_device': ([vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_loss_grad': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp],
+                                  ctypes.c_int),
+        'bpe_sgmodel_loss_grad_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), vp, vp, vp,
+                                          vp], ctypes.c_int),
+        'bpe_sgmodel_adam_step': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'bpe_sgmodel_adam_step_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)],
+                                         ctypes.c_int),
+        'bpe_sgmodel_reset_optimizer': ([vp], ctypes.c_int),
+        'bpe_sgmodel_embed': ([vp, vp, ctypes.c_int64, vp], ctypes.c_int),
+        'bpe_sgmodel_embed_device': ([vp, vp, ctypes.c_int64, vp], ctypes.c_int),
+        'bpe_sgmodel_get_stats': ([vp, ctypes.POINTER(SkipgramModelStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -2368,6 +2403,160 @@ class Decoder:
 
     def reset_stats(self):
         _check(lib().bpe_decoder_reset_stats(self._dec), 'bpe_decoder_reset_stats')
+
+
+class SkipgramModel:
+    """The reference's skip-gram model (example/skip-gram.ts: one-hot -> linear(dim, embed) ->
+    linear(embed, dim) -> softmax, Adam) trained from count planes on the device (bpe_sgmodel_*,
+    include/bpe.h; csrc/bpe_sgmodel.hip).  Parameters (Ein[dim][embed], b1[embed], Eout[dim][embed],
+    b2[dim], fp32) and the Adam state live in the model and start at zero.  The `_tensors` forms take and
+    return torch tensors on the model's device and copy nothing to the host.  No CPU fallback."""
+
+    def __init__(self, device=0, dim=1, embed=50):
+        p = ctypes.c_void_p()
+        _check(lib().bpe_sgmodel_create(int(device), int(dim), int(embed), ctypes.byref(p)), 'bpe_sgmodel_create')
+        self._m = p
+        self.device, self.dim, self.width = int(device), int(dim), int(embed)   # (`embed` is the method)
+
+    def close(self):
+        if self._m:
+            lib().bpe_sgmodel_destroy(self._m)
+            self._m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _shapes(self):
+        return [(self.dim, self.width), (self.width,), (self.dim, self.width), (self.dim,)]
+
+    @staticmethod
+    def _given(shapes):
+        """(dim, embed) of four arrays shaped like a model's parameters (the library compares them with its own)."""
+        dim, embed = shapes[0] if len(shapes[0]) == 2 else (-1, -1)
+        if list(shapes) != [(dim, embed), (embed,), (dim, embed), (dim,)]:
+            raise BpeError('skip-gram model parameters of shapes %s are no (Ein, b1, Eout, b2)' % (list(shapes),), ERR_ARG)
+        return dim, embed
+
+    def set_params(self, Ein, b1, Eout, b2):
+        """Copies the four arrays in; their shapes must be the model's (else BpeError, nothing changed)."""
+        a = [np.ascontiguousarray(x, dtype=np.float32) for x in (Ein, b1, Eout, b2)]
+        dim, embed = self._given([x.shape for x in a])
+        _check(lib().bpe_sgmodel_set_params(self._m, *[x.ctypes.data for x in a], dim, embed), 'bpe_sgmodel_set_params')
+
+    def get_params(self):
+        """-> (Ein, b1, Eout, b2) numpy float32."""
+        a = [np.empty(s, np.float32) for s in self._shapes()]
+        _check(lib().bpe_sgmodel_get_params(self._m, *[x.ctypes.data for x in a], self.dim, self.width),
+               'bpe_sgmodel_get_params')
+        return tuple(a)
+
+    def _device_params(self, what, tensors):
+        import torch
+        for x in tensors:
+            if x.dtype != torch.float32 or not x.is_cuda or x.device.index != self.device or not x.is_contiguous():
+                raise BpeError('%s takes contiguous float32 tensors on the model\'s device' % what, ERR_ARG)
+        dim, embed = self._given([tuple(x.shape) for x in tensors])
+        torch.cuda.synchronize(torch.device('cuda', self.device))   # (the model runs on a stream of its own)
+        return [x.data_ptr() for x in tensors] + [dim, embed]
+
+    def set_params_tensors(self, Ein, b1, Eout, b2):
+        _check(lib().bpe_sgmodel_set_params_device(self._m, *self._device_params('set_params_tensors', (Ein, b1, Eout, b2))),
+               'bpe_sgmodel_set_params_device')
+
+    def get_params_tensors(self):
+        import torch
+        a = [torch.empty(s, dtype=torch.float32, device=torch.device('cuda', self.device)) for s in self._shapes()]
+        _check(lib().bpe_sgmodel_get_params_device(self._m, *self._device_params('get_params_tensors', a)),
+               'bpe_sgmodel_get_params_device')
+        return tuple(a)
+
+    @staticmethod
+    def _planes(targets, contexts, counts):
+        t, c = _i32(targets), _i32(contexts)
+        k = np.ascontiguousarray(counts, dtype=np.int64)
+        if not (t.ndim == c.ndim == k.ndim == 1 and t.size == c.size == k.size):
+            raise BpeError('skip-gram model planes must be three vectors of one length', ERR_ARG)
+        return t, c, k
+
+    def _planes_tensors(self, what, targets, contexts, counts):
+        import torch
+        for x, dt in ((targets, torch.int32), (contexts, torch.int32), (counts, torch.int64)):
+            if x.dtype != dt or not x.is_cuda or x.device.index != self.device or not x.is_contiguous() or x.dim() != 1:
+                raise BpeError('%s takes contiguous (int32, int32, int64) vectors on the model\'s device' % what, ERR_ARG)
+        if not targets.numel() == contexts.numel() == counts.numel():
+            raise BpeError('skip-gram model planes must be three vectors of one length', ERR_ARG)
+        torch.cuda.synchronize(torch.device('cuda', self.device))
+        n = targets.numel()
+        return [x.data_ptr() if n else None for x in (targets, contexts, counts)] + [n]
+
+    def loss_grad(self, targets, contexts, counts):
+        """-> (loss, dEin, db1, dEout, db2) of the count planes (bpe_sgmodel_loss_grad)."""
+        t, c, k = self._planes(targets, contexts, counts)
+        g = [np.empty(s, np.float32) for s in self._shapes()]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_loss_grad(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, ctypes.byref(loss),
+                                           *[x.ctypes.data for x in g]), 'bpe_sgmodel_loss_grad')
+        return (loss.value,) + tuple(g)
+
+    def loss_grad_tensors(self, targets, contexts, counts):
+        """Device form (bpe_sgmodel_loss_grad_device): planes as torch tensors on the model's device,
+        e.g. what Encoder.skipgram_counts_*_tensors returns -> (loss, dEin, db1, dEout, db2) with the
+        gradients torch tensors there."""
+        import torch
+        args = self._planes_tensors('loss_grad_tensors', targets, contexts, counts)
+        g = [torch.empty(s, dtype=torch.float32, device=targets.device) for s in self._shapes()]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_loss_grad_device(self._m, *args, ctypes.byref(loss), *[x.data_ptr() for x in g]),
+               'bpe_sgmodel_loss_grad_device')
+        return (loss.value,) + tuple(g)
+
+    def adam_step(self, targets, contexts, counts, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        """One step of Adam on the count planes (bpe_sgmodel_adam_step) -> the loss before the update."""
+        t, c, k = self._planes(targets, contexts, counts)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_adam_step(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, lr, beta1, beta2,
+                                           eps, ctypes.byref(loss)), 'bpe_sgmodel_adam_step')
+        return loss.value
+
+    def adam_step_tensors(self, targets, contexts, counts, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+        """Device form (bpe_sgmodel_adam_step_device)."""
+        args = self._planes_tensors('adam_step_tensors', targets, contexts, counts)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_adam_step_device(self._m, *args, lr, beta1, beta2, eps, ctypes.byref(loss)),
+               'bpe_sgmodel_adam_step_device')
+        return loss.value
+
+    def reset_optimizer(self):
+        _check(lib().bpe_sgmodel_reset_optimizer(self._m), 'bpe_sgmodel_reset_optimizer')
+
+    def embed(self, ids):
+        """-> float32 [len(ids)][embed]: Ein[id] + b1, the hidden layer of each id (bpe_sgmodel_embed)."""
+        ids = _i32(ids).reshape(-1)
+        out = np.empty((ids.size, self.width), np.float32)
+        _check(lib().bpe_sgmodel_embed(self._m, ids.ctypes.data, ids.size, out.ctypes.data), 'bpe_sgmodel_embed')
+        return out
+
+    def embed_tensors(self, ids):
+        """Device form (bpe_sgmodel_embed_device): ids a torch int32 vector on the model's device."""
+        import torch
+        if ids.dtype != torch.int32 or not ids.is_cuda or ids.device.index != self.device or not ids.is_contiguous():
+            raise BpeError('embed_tensors takes a contiguous int32 tensor on the model\'s device', ERR_ARG)
+        out = torch.empty((ids.numel(), self.width), dtype=torch.float32, device=ids.device)
+        torch.cuda.synchronize(ids.device)
+        _check(lib().bpe_sgmodel_embed_device(self._m, ids.data_ptr() if ids.numel() else None, ids.numel(),
+                                              out.data_ptr() if ids.numel() else None), 'bpe_sgmodel_embed_device')
+        return out
+
+    def stats(self):
+        s = SkipgramModelStats()
+        _check(lib().bpe_sgmodel_get_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_stats')
+        return s.as_dict()
+
+    def reset_stats(self):
+        _check(lib().bpe_sgmodel_reset_stats(self._m), 'bpe_sgmodel_reset_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

@@ -1145,6 +1145,78 @@ int bpe_encoder_reset_skipgram_counts_stats(bpe_encoder *enc);
 int bpe_get_skipgram_counts_stats(bpe_ctx *ctx, bpe_skipgram_counts_stats *out);
 int bpe_reset_skipgram_counts_stats(bpe_ctx *ctx);
 
+/* ---- skip-gram model --------------------------------------------------------------------------------
+ * The model those counts feed (example/skip-gram.ts: one-hot -> linear(V, E) -> linear(E, V) -> softmax,
+ * trained with Adam), one full-softmax step from the count planes on the device; no V x V matrix is
+ * ever written.  Parameters, all fp32 and row-major: Ein[V][E] (row t is column t of the first linear),
+ * b1[E], Eout[V][E] (row c is row c of the second linear), b2[V].  They and both Adam moments start at
+ * zero and live in the model, on its device.
+ *
+ * Planes of U elements as the count forms above emit them: targets and contexts int32 in [0, V), counts
+ * int64 >= 0, keys t * V + c strictly ascending.  C need not be symmetric: the counts of any subset of
+ * pairs will do.  With H_t = Ein[t] + b1, z[t,c] = H_t . Eout[c] + b2[c], lse_t = log sum_c exp z[t,c],
+ * n_t = sum_c C[t,c] and P = sum_t n_t (int64):
+ *   loss  = (1/P) (sum_t n_t lse_t - sum_(t,c) C[t,c] z[t,c])
+ *   G[t,c] = (n_t exp(z[t,c] - lse_t) - C[t,c]) / P
+ *   dEin = G Eout, db1 = its column sums, dEout = G^T H, db2 = the column sums of G.
+ * The loss and every gradient are 0 when P == 0 (U == 0 with NULL planes too).  The products are fp32
+ * matrix instructions; there are no floating-point atomics and every reduction has a fixed order, so
+ * the results are the same bytes on every run and in both forms.
+ *
+ * A plane element that breaks the rules gives BPE_ERR_ARG and a message naming the smallest such element:
+ * `skip-gram model target T outside [0, V) (element I)`, `... context C outside ...`, `skip-gram model
+ * count K is negative (element I)`, `skip-gram model pair (T, C) is given twice (element I)`,
+ * `skip-gram model pairs must ascend: (T, C) after (T', C') (element I)`; nothing is computed and neither
+ * the parameters nor the optimizer change.  dim outside [1, BPE_SKIPGRAM_COUNTS_MAX_DIM] or embed
+ * outside [1, BPE_SGM_MAX_EMBED] fails bpe_sgmodel_create with BPE_ERR_ARG.
+ *
+ * bpe_sgmodel_set_params / _get_params copy all four arrays; dim and embed are what the caller's arrays
+ * were sized for, and a mismatch is BPE_ERR_ARG with nothing changed.  bpe_sgmodel_loss_grad writes the
+ * loss (taken in double from the fp32 lse) and those gradients whose pointer is not NULL.
+ * bpe_sgmodel_adam_step does the same evaluation and then one step of Adam (Kingma & Ba, with bias
+ * correction) over all 2VE + V + E parameters; *loss is the loss before the update; the step counter and
+ * the moments are the model's, and bpe_sgmodel_reset_optimizer zeroes them.  bpe_sgmodel_embed writes
+ * out[i][0..E) = Ein[ids[i]] + b1; an id outside [0, V) is BPE_ERR_ARG (`skip-gram model id ...`).
+ * The `_device` forms take and fill buffers on the model's device, run on its stream and synchronise
+ * before returning; the host forms are the device forms plus the copies.
+ *
+ * The kernels work on blocks of BPE_SGM_TILE target rows and BPE_SGM_TILE context columns
+ * (csrc/bpe_sgmodel.hip; exported for the tests, which place sizes and count entries around it). */
+#define BPE_SGM_MAX_EMBED 256
+#define BPE_SGM_TILE 64
+typedef struct bpe_sgmodel bpe_sgmodel;
+typedef struct {
+    int64_t calls;      /* loss_grad and adam_step calls (failed ones too) */
+    int64_t elements;   /* U of the calls that passed their checks */
+    int64_t pairs;      /* ... their P */
+    int64_t steps;      /* Adam steps since creation or bpe_sgmodel_reset_optimizer */
+    double kernel_ms;   /* HIP-event time of the kernels */
+} bpe_sgmodel_stats;
+int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out);
+int bpe_sgmodel_destroy(bpe_sgmodel *m);
+int bpe_sgmodel_set_params(bpe_sgmodel *m, const float *Ein, const float *b1, const float *Eout, const float *b2,
+                           int64_t dim, int64_t embed);
+int bpe_sgmodel_set_params_device(bpe_sgmodel *m, const float *d_Ein, const float *d_b1, const float *d_Eout,
+                                  const float *d_b2, int64_t dim, int64_t embed);
+int bpe_sgmodel_get_params(bpe_sgmodel *m, float *Ein, float *b1, float *Eout, float *b2, int64_t dim, int64_t embed);
+int bpe_sgmodel_get_params_device(bpe_sgmodel *m, float *d_Ein, float *d_b1, float *d_Eout, float *d_b2, int64_t dim,
+                                  int64_t embed);
+int bpe_sgmodel_loss_grad(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                          int64_t U, double *loss, float *dEin, float *db1, float *dEout, float *db2);
+int bpe_sgmodel_loss_grad_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                 const int64_t *d_counts, int64_t U, double *loss, float *d_dEin, float *d_db1,
+                                 float *d_dEout, float *d_db2);
+int bpe_sgmodel_adam_step(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                          int64_t U, double lr, double beta1, double beta2, double eps, double *loss);
+int bpe_sgmodel_adam_step_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                 const int64_t *d_counts, int64_t U, double lr, double beta1, double beta2, double eps,
+                                 double *loss);
+int bpe_sgmodel_reset_optimizer(bpe_sgmodel *m);
+int bpe_sgmodel_embed(bpe_sgmodel *m, const int32_t *ids, int64_t n, float *out);
+int bpe_sgmodel_embed_device(bpe_sgmodel *m, const int32_t *d_ids, int64_t n, float *d_out);
+int bpe_sgmodel_get_stats(bpe_sgmodel *m, bpe_sgmodel_stats *out);
+int bpe_sgmodel_reset_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
