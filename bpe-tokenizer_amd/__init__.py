@@ -77,6 +77,9 @@ C_API = [
     'bpe_sgmodel_get_params', 'bpe_sgmodel_get_params_device', 'bpe_sgmodel_loss_grad', 'bpe_sgmodel_loss_grad_device',
     'bpe_sgmodel_adam_step', 'bpe_sgmodel_adam_step_device', 'bpe_sgmodel_reset_optimizer', 'bpe_sgmodel_embed',
     'bpe_sgmodel_embed_device', 'bpe_sgmodel_get_stats', 'bpe_sgmodel_reset_stats',
+    'bpe_sgmodel_neighbors', 'bpe_sgmodel_neighbors_device', 'bpe_sgmodel_neighbors_vectors',
+    'bpe_sgmodel_neighbors_vectors_device', 'bpe_sgmodel_predict', 'bpe_sgmodel_predict_device',
+    'bpe_sgmodel_get_query_stats', 'bpe_sgmodel_reset_query_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -142,6 +145,10 @@ SKIPGRAM_COUNTS_TILE = 2048      # BPE_SKIPGRAM_COUNTS_TILE: positions per workg
 SKIPGRAM_COUNTS_SLOTS = 4096     # BPE_SKIPGRAM_COUNTS_SLOTS: slots of its LDS table
 SGM_MAX_EMBED = 256              # BPE_SGM_MAX_EMBED: the widest embedding of the skip-gram model
 SGM_TILE = 64                    # BPE_SGM_TILE: target rows / context columns per workgroup of its kernels
+SGM_MAX_TOPK = 64                # BPE_SGM_MAX_TOPK: the largest k of its queries
+SGM_DOT = 0                      # BPE_SGM_DOT
+SGM_COSINE = 1                   # BPE_SGM_COSINE
+_SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
@@ -301,6 +308,15 @@ class SkipgramModelStats(ctypes.Structure):
     """bpe_sgmodel_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('elements', ctypes.c_int64), ('pairs', ctypes.c_int64),
                 ('steps', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramQueryStats(ctypes.Structure):
+    """bpe_sgmodel_query_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('queries', ctypes.c_int64), ('splits', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -549,6 +565,16 @@ def lib():
         'bpe_sgmodel_embed_device': ([vp, vp, ctypes.c_int64, vp], ctypes.c_int),
         'bpe_sgmodel_get_stats': ([vp, ctypes.POINTER(SkipgramModelStats)], ctypes.c_int),
         'bpe_sgmodel_reset_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_neighbors': ([vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_neighbors_device': ([vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_neighbors_vectors': ([vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp],
+                                          ctypes.c_int),
+        'bpe_sgmodel_neighbors_vectors_device': ([vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp,
+                                                  vp], ctypes.c_int),
+        'bpe_sgmodel_predict': ([vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_predict_device': ([vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_get_query_stats': ([vp, ctypes.POINTER(SkipgramQueryStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_query_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -2557,6 +2583,96 @@ class SkipgramModel:
 
     def reset_stats(self):
         _check(lib().bpe_sgmodel_reset_stats(self._m), 'bpe_sgmodel_reset_stats')
+
+    # ---- queries (include/bpe.h, "skip-gram model queries"; csrc/bpe_sgquery.hip.h) ----
+    @staticmethod
+    def _metric(metric):
+        """'dot' / 'cosine' or the library's number; the library refuses anything else (an unknown name goes as -1)."""
+        return _SGM_METRICS.get(metric, -1) if isinstance(metric, str) else int(metric)
+
+    def _query_tensor(self, what, x, dtype, dim):
+        import torch
+        if (x.dtype != getattr(torch, dtype) or not x.is_cuda or x.device.index != self.device or not x.is_contiguous()
+                or x.dim() != dim):
+            raise BpeError('%s takes a contiguous %s tensor of %d dimension(s) on the model\'s device' % (what, dtype, dim),
+                           ERR_ARG)
+        torch.cuda.synchronize(x.device)   # (the model runs on a stream of its own)
+        return x.data_ptr() if x.numel() else None
+
+    def _query_out(self, n, k, like=None):
+        """(ids[n][k], values[n][k], lse[n]) to fill: numpy, or torch tensors beside `like`."""
+        k = max(int(k), 0)
+        if like is None:
+            return np.empty((n, k), np.int32), np.empty((n, k), np.float32), np.empty(n, np.float32)
+        import torch
+        return (torch.empty((n, k), dtype=torch.int32, device=like.device),
+                torch.empty((n, k), dtype=torch.float32, device=like.device),
+                torch.empty(n, dtype=torch.float32, device=like.device))
+
+    def neighbors(self, ids, k=10, metric='cosine'):
+        """-> (ids[n][k] int32, scores[n][k] float32): the k tokens nearest to each id's row Ein[id] + b1 by
+        'cosine' or 'dot', the id itself excluded; by score descending, ties by id ascending; padded with
+        (-1, -inf) when dim - 1 < k (bpe_sgmodel_neighbors)."""
+        ids = _i32(ids).reshape(-1)
+        oi, ov, _ = self._query_out(ids.size, k)
+        _check(lib().bpe_sgmodel_neighbors(self._m, ids.ctypes.data, ids.size, int(k), self._metric(metric), oi.ctypes.data,
+                                           ov.ctypes.data), 'bpe_sgmodel_neighbors')
+        return oi, ov
+
+    def neighbors_tensors(self, ids, k=10, metric='cosine'):
+        """Device form (bpe_sgmodel_neighbors_device): ids a torch int32 vector on the model's device."""
+        p = self._query_tensor('neighbors_tensors', ids, 'int32', 1)
+        oi, ov, _ = self._query_out(ids.numel(), k, ids)
+        _check(lib().bpe_sgmodel_neighbors_device(self._m, p, ids.numel(), int(k), self._metric(metric), oi.data_ptr(),
+                                                  ov.data_ptr()), 'bpe_sgmodel_neighbors_device')
+        return oi, ov
+
+    def neighbors_vectors(self, q, k=10, metric='cosine'):
+        """The same for caller's rows q[n][embed] (a - b + c of an analogy, say); nothing is excluded
+        (bpe_sgmodel_neighbors_vectors)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2:
+            raise BpeError('neighbors_vectors takes rows [n][embed]', ERR_ARG)
+        oi, ov, _ = self._query_out(q.shape[0], k)
+        _check(lib().bpe_sgmodel_neighbors_vectors(self._m, q.ctypes.data, q.shape[0], q.shape[1], int(k),
+                                                   self._metric(metric), oi.ctypes.data, ov.ctypes.data),
+               'bpe_sgmodel_neighbors_vectors')
+        return oi, ov
+
+    def neighbors_vectors_tensors(self, q, k=10, metric='cosine'):
+        """Device form (bpe_sgmodel_neighbors_vectors_device): q a torch float32 [n][embed] on the model's device."""
+        p = self._query_tensor('neighbors_vectors_tensors', q, 'float32', 2)
+        oi, ov, _ = self._query_out(q.shape[0], k, q)
+        _check(lib().bpe_sgmodel_neighbors_vectors_device(self._m, p, q.shape[0], q.shape[1], int(k), self._metric(metric),
+                                                          oi.data_ptr(), ov.data_ptr()),
+               'bpe_sgmodel_neighbors_vectors_device')
+        return oi, ov
+
+    def predict(self, ids, k=10):
+        """-> (ids[n][k] int32, probs[n][k] float32, lse[n] float32): the k likeliest contexts of each target
+        id under the model's softmax, likeliest first, ties by id ascending; padded with (-1, 0) when dim < k
+        (bpe_sgmodel_predict)."""
+        ids = _i32(ids).reshape(-1)
+        oi, ov, ol = self._query_out(ids.size, k)
+        _check(lib().bpe_sgmodel_predict(self._m, ids.ctypes.data, ids.size, int(k), oi.ctypes.data, ov.ctypes.data,
+                                         ol.ctypes.data), 'bpe_sgmodel_predict')
+        return oi, ov, ol
+
+    def predict_tensors(self, ids, k=10):
+        """Device form (bpe_sgmodel_predict_device)."""
+        p = self._query_tensor('predict_tensors', ids, 'int32', 1)
+        oi, ov, ol = self._query_out(ids.numel(), k, ids)
+        _check(lib().bpe_sgmodel_predict_device(self._m, p, ids.numel(), int(k), oi.data_ptr(), ov.data_ptr(),
+                                                ol.data_ptr()), 'bpe_sgmodel_predict_device')
+        return oi, ov, ol
+
+    def query_stats(self):
+        s = SkipgramQueryStats()
+        _check(lib().bpe_sgmodel_get_query_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_query_stats')
+        return s.as_dict()
+
+    def reset_query_stats(self):
+        _check(lib().bpe_sgmodel_reset_query_stats(self._m), 'bpe_sgmodel_reset_query_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

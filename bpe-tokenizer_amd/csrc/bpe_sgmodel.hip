@@ -38,6 +38,7 @@
 //   k_sgm_reduce  db1 and the loss from the row blocks' partials, in block order;
 //   k_sgm_adam    Adam over the flat parameter array, 16 B per access;
 //   k_sgm_embed   rows Ein[id] + b1.
+// The queries of a trained model (nearest tokens, top contexts) are in bpe_sgquery.hip.h, included below.
 // No floating-point atomics; every reduction has a fixed order, so results are the same bytes on
 // every run and route.
 #include <hip/hip_runtime.h>
@@ -536,6 +537,11 @@ struct bpe_sgmodel {
     int64_t io_cap = 0;
     int64_t step = 0;
     bpe_sgmodel_stats stats = {};
+    // the queries (bpe_sgquery.hip.h): norms, partial lists and (max, sum) partials, grow-only
+    void *d_qs = nullptr;
+    int64_t qs_cap = 0;
+    int n_cus = 1;
+    bpe_sgmodel_query_stats qstats = {};
 };
 
 namespace {
@@ -735,6 +741,8 @@ int sgm_embed(bpe_sgmodel *M, const int32_t *d_ids, int64_t n, float *d_out) {
 
 }  // namespace
 
+#include "bpe_sgquery.hip.h"
+
 extern "C" {
 
 int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
@@ -790,6 +798,8 @@ int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
     }
     if (sgm_lds_attrs<64>() != hipSuccess || sgm_lds_attrs<128>() != hipSuccess || sgm_lds_attrs<256>() != hipSuccess)
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model LDS attribute"));
+    if (sgq_lds_attrs() != hipSuccess || hipDeviceGetAttribute(&M->n_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
+        return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model query attributes"));
     *out = M;
     return BPE_OK;
 }
@@ -800,7 +810,7 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     if (M->stream) (void)hipStreamSynchronize(M->stream);
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
-                    M->d_io})
+                    M->d_io, M->d_qs})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);

@@ -1217,6 +1217,56 @@ int bpe_sgmodel_embed_device(bpe_sgmodel *m, const int32_t *d_ids, int64_t n, fl
 int bpe_sgmodel_get_stats(bpe_sgmodel *m, bpe_sgmodel_stats *out);
 int bpe_sgmodel_reset_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model queries: nearest tokens, top contexts ----------------------------------------
+ * What a trained model is asked (the reference's example/skip-gram-test.ts looks tokens up in its net):
+ * a streamed n x V x E product with the top-k selection fused behind it, so the n x V score matrix is
+ * never written (csrc/bpe_sgquery.hip.h).  With X_v = fl32(Ein[v] + b1), the row bpe_sgmodel_embed
+ * returns, and all arithmetic in fp32 (parameters are assumed finite):
+ *   metric BPE_SGM_DOT     s(q, v) = q . X_v
+ *   metric BPE_SGM_COSINE  s(q, v) = fl(fl((q . X_v) r(q)) r(X_v)),  r(x) = 1 / |x|_2, and 0 for the zero
+ *                          vector (which therefore scores 0 against everything)
+ *   predict                z(t, c) = X_t . Eout[c] + b2[c], lse_t = log sum_c exp z(t, c),
+ *                          p(c | t) = exp(z(t, c) - lse_t), ordered by z
+ * bpe_sgmodel_neighbors takes ids: q = X_id, and candidate v = id itself is excluded.
+ * bpe_sgmodel_neighbors_vectors takes n rows of `embed` floats (a - b + c of an analogy, say) and
+ * excludes nothing.  bpe_sgmodel_predict takes target ids; out_lse (n floats) may be NULL.
+ *
+ * Every form writes k entries per query, out[i][0..k), by score descending, ties by id ascending: a
+ * total order, so the answer is unique given the fp32 scores.  1 <= k <= BPE_SGM_MAX_TOPK.  A query with
+ * fewer than k candidates (V - 1 for the id form of neighbors, V otherwise) has the rest padded: id -1,
+ * score -inf, probability 0.  A score is accumulated over e in one fixed order, so a query's ids and
+ * neighbour scores are the same bytes whatever else is in the batch, in both forms and on every run;
+ * lse and the probabilities are the same bytes for the same n, and may differ in the last place between
+ * batch sizes for which the host chooses different numbers of key splits.
+ *
+ * Errors are BPE_ERR_ARG with nothing written: an id outside [0, V) (`skip-gram model id D outside
+ * [0, V) (element I)`, the smallest such element), k outside [1, BPE_SGM_MAX_TOPK], an unknown metric,
+ * `embed` different from the model's.  n == 0 is BPE_OK and writes nothing.  The `_device` forms take
+ * and fill buffers on the model's device; the host forms are the device forms plus the copies. */
+#define BPE_SGM_MAX_TOPK 64
+#define BPE_SGM_DOT 0
+#define BPE_SGM_COSINE 1
+typedef struct {
+    int64_t calls;      /* query calls (failed ones too) */
+    int64_t queries;    /* n of the calls that passed their checks */
+    int64_t splits;     /* key splits of the last such call (chosen from n, V and the device) */
+    double kernel_ms;   /* HIP-event time of the kernels */
+} bpe_sgmodel_query_stats;
+int bpe_sgmodel_neighbors(bpe_sgmodel *m, const int32_t *ids, int64_t n, int k, int metric, int32_t *out_ids,
+                          float *out_scores);
+int bpe_sgmodel_neighbors_device(bpe_sgmodel *m, const int32_t *d_ids, int64_t n, int k, int metric, int32_t *d_out_ids,
+                                 float *d_out_scores);
+int bpe_sgmodel_neighbors_vectors(bpe_sgmodel *m, const float *q, int64_t n, int64_t embed, int k, int metric,
+                                  int32_t *out_ids, float *out_scores);
+int bpe_sgmodel_neighbors_vectors_device(bpe_sgmodel *m, const float *d_q, int64_t n, int64_t embed, int k, int metric,
+                                         int32_t *d_out_ids, float *d_out_scores);
+int bpe_sgmodel_predict(bpe_sgmodel *m, const int32_t *ids, int64_t n, int k, int32_t *out_ids, float *out_probs,
+                        float *out_lse);
+int bpe_sgmodel_predict_device(bpe_sgmodel *m, const int32_t *d_ids, int64_t n, int k, int32_t *d_out_ids,
+                               float *d_out_probs, float *d_out_lse);
+int bpe_sgmodel_get_query_stats(bpe_sgmodel *m, bpe_sgmodel_query_stats *out);
+int bpe_sgmodel_reset_query_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
