@@ -80,6 +80,8 @@ C_API = [
     'bpe_sgmodel_neighbors', 'bpe_sgmodel_neighbors_device', 'bpe_sgmodel_neighbors_vectors',
     'bpe_sgmodel_neighbors_vectors_device', 'bpe_sgmodel_predict', 'bpe_sgmodel_predict_device',
     'bpe_sgmodel_get_query_stats', 'bpe_sgmodel_reset_query_stats',
+    'bpe_sgmodel_sgns_loss_grad', 'bpe_sgmodel_sgns_loss_grad_device', 'bpe_sgmodel_sgns_adam_step',
+    'bpe_sgmodel_sgns_adam_step_device', 'bpe_sgmodel_get_sgns_stats', 'bpe_sgmodel_reset_sgns_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -148,6 +150,7 @@ SGM_TILE = 64                    # BPE_SGM_TILE: target rows / context columns p
 SGM_MAX_TOPK = 64                # BPE_SGM_MAX_TOPK: the largest k of its queries
 SGM_DOT = 0                      # BPE_SGM_DOT
 SGM_COSINE = 1                   # BPE_SGM_COSINE
+SGNS_ROWS = 32                   # BPE_SGNS_ROWS: rows a wave of the negative-sampling kernels owns
 _SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
@@ -317,6 +320,16 @@ class SkipgramQueryStats(ctypes.Structure):
     """bpe_sgmodel_query_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('queries', ctypes.c_int64), ('splits', ctypes.c_int64),
                 ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramSgnsStats(ctypes.Structure):
+    """bpe_sgmodel_sgns_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('elements', ctypes.c_int64), ('pairs', ctypes.c_int64),
+                ('negatives', ctypes.c_int64), ('kernel_ms', ctypes.c_double), ('transpose_ms', ctypes.c_double),
+                ('target_ms', ctypes.c_double), ('context_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -575,6 +588,18 @@ def lib():
         'bpe_sgmodel_predict_device': ([vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp], ctypes.c_int),
         'bpe_sgmodel_get_query_stats': ([vp, ctypes.POINTER(SkipgramQueryStats)], ctypes.c_int),
         'bpe_sgmodel_reset_query_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_sgns_loss_grad': ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_sgns_loss_grad_device': ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_double,
+                                               ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_sgns_adam_step': ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'bpe_sgmodel_sgns_adam_step_device': ([vp, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'bpe_sgmodel_get_sgns_stats': ([vp, ctypes.POINTER(SkipgramSgnsStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_sgns_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -2673,6 +2698,96 @@ class SkipgramModel:
 
     def reset_query_stats(self):
         _check(lib().bpe_sgmodel_reset_query_stats(self._m), 'bpe_sgmodel_reset_query_stats')
+
+    # ---- negative sampling (include/bpe.h, "skip-gram model, negative sampling"; csrc/bpe_sgns.hip.h) ----
+    @staticmethod
+    def _neg_set(neg_ids, neg_weights):
+        ids = _i32(neg_ids).reshape(-1)
+        w = None if neg_weights is None else np.ascontiguousarray(neg_weights, dtype=np.float32).reshape(-1)
+        if w is not None and w.size != ids.size:
+            raise BpeError('skip-gram model negative ids and weights must be two vectors of one length', ERR_ARG)
+        return [ids.ctypes.data if ids.size else None, w.ctypes.data if w is not None and w.size else None, ids.size], (ids, w)
+
+    def _neg_set_tensors(self, what, neg_ids, neg_weights):
+        import torch
+        for x, dt in ((neg_ids, torch.int32), (neg_weights, torch.float32)):
+            if x is not None and (x.dtype != dt or not x.is_cuda or x.device.index != self.device or not x.is_contiguous()
+                                  or x.dim() != 1):
+                raise BpeError('%s takes the negative set as contiguous (int32, float32) vectors on the model\'s device'
+                               % what, ERR_ARG)
+        if neg_weights is not None and neg_weights.numel() != neg_ids.numel():
+            raise BpeError('skip-gram model negative ids and weights must be two vectors of one length', ERR_ARG)
+        n = neg_ids.numel()
+        return [neg_ids.data_ptr() if n else None, neg_weights.data_ptr() if n and neg_weights is not None else None, n]
+
+    def sgns_loss_grad(self, targets, contexts, counts, neg_ids, neg_weights=None, neg_k=5.0):
+        """-> (loss, dEin, db1, dEout, db2) of skip-gram with negative sampling on the count planes: neg_ids a
+        strictly ascending set of ids shared by all targets, neg_weights their weights (None: 1/S each), neg_k
+        the weight of the negative term (bpe_sgmodel_sgns_loss_grad)."""
+        t, c, k = self._planes(targets, contexts, counts)
+        neg, _keep = self._neg_set(neg_ids, neg_weights)
+        g = [np.empty(s, np.float32) for s in self._shapes()]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_sgns_loss_grad(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, *neg,
+                                                float(neg_k), ctypes.byref(loss), *[x.ctypes.data for x in g]),
+               'bpe_sgmodel_sgns_loss_grad')
+        return (loss.value,) + tuple(g)
+
+    def sgns_loss_grad_tensors(self, targets, contexts, counts, neg_ids, neg_weights=None, neg_k=5.0):
+        """Device form (bpe_sgmodel_sgns_loss_grad_device): planes and the set as torch tensors on the model's device."""
+        import torch
+        neg = self._neg_set_tensors('sgns_loss_grad_tensors', neg_ids, neg_weights)
+        args = self._planes_tensors('sgns_loss_grad_tensors', targets, contexts, counts)
+        g = [torch.empty(s, dtype=torch.float32, device=targets.device) for s in self._shapes()]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_sgns_loss_grad_device(self._m, *args, *neg, float(neg_k), ctypes.byref(loss),
+                                                       *[x.data_ptr() for x in g]), 'bpe_sgmodel_sgns_loss_grad_device')
+        return (loss.value,) + tuple(g)
+
+    def sgns_adam_step(self, targets, contexts, counts, neg_ids, neg_weights=None, neg_k=5.0, lr=1e-3, beta1=0.9,
+                       beta2=0.999, eps=1e-8):
+        """One step of Adam on the negative-sampling gradients (bpe_sgmodel_sgns_adam_step) -> the loss before
+        the update.  The moments and the step counter are those of adam_step."""
+        t, c, k = self._planes(targets, contexts, counts)
+        neg, _keep = self._neg_set(neg_ids, neg_weights)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_sgns_adam_step(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, *neg,
+                                                float(neg_k), lr, beta1, beta2, eps, ctypes.byref(loss)),
+               'bpe_sgmodel_sgns_adam_step')
+        return loss.value
+
+    def sgns_adam_step_tensors(self, targets, contexts, counts, neg_ids, neg_weights=None, neg_k=5.0, lr=1e-3, beta1=0.9,
+                               beta2=0.999, eps=1e-8):
+        """Device form (bpe_sgmodel_sgns_adam_step_device)."""
+        neg = self._neg_set_tensors('sgns_adam_step_tensors', neg_ids, neg_weights)
+        args = self._planes_tensors('sgns_adam_step_tensors', targets, contexts, counts)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_sgns_adam_step_device(self._m, *args, *neg, float(neg_k), lr, beta1, beta2, eps,
+                                                       ctypes.byref(loss)), 'bpe_sgmodel_sgns_adam_step_device')
+        return loss.value
+
+    def noise(self, targets, contexts, counts, power=0.75):
+        """-> q float64 [dim]: the noise distribution of word2vec, the context column sums of the count planes
+        raised to `power` and normalised (all zeros when there are no counts).  Host plumbing."""
+        _, c, k = self._planes(targets, contexts, counts)
+        q = np.bincount(c, weights=k.astype(np.float64), minlength=self.dim)[:self.dim] ** power
+        return q / q.sum() if q.sum() > 0 else q
+
+    @staticmethod
+    def sample_negatives(q, S, seed=0):
+        """-> (ids int32, weights float32): S draws from q with replacement, as the unique ids ascending with
+        weight multiplicity / S, ready for sgns_*.  Host plumbing."""
+        draws = np.random.default_rng(seed).choice(len(q), size=int(S), p=np.asarray(q, np.float64))
+        ids, mult = np.unique(draws, return_counts=True)
+        return ids.astype(np.int32), (mult / float(S)).astype(np.float32)
+
+    def sgns_stats(self):
+        s = SkipgramSgnsStats()
+        _check(lib().bpe_sgmodel_get_sgns_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_sgns_stats')
+        return s.as_dict()
+
+    def reset_sgns_stats(self):
+        _check(lib().bpe_sgmodel_reset_sgns_stats(self._m), 'bpe_sgmodel_reset_sgns_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

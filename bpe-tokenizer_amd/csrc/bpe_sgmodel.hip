@@ -38,11 +38,13 @@
 //   k_sgm_reduce  db1 and the loss from the row blocks' partials, in block order;
 //   k_sgm_adam    Adam over the flat parameter array, 16 B per access;
 //   k_sgm_embed   rows Ein[id] + b1.
-// The queries of a trained model (nearest tokens, top contexts) are in bpe_sgquery.hip.h, included below.
+// The queries of a trained model (nearest tokens, top contexts) are in bpe_sgquery.hip.h, and the same
+// parameters trained with negative sampling instead of the full softmax in bpe_sgns.hip.h, both included below.
 // No floating-point atomics; every reduction has a fixed order, so results are the same bytes on
 // every run and route.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -542,6 +544,11 @@ struct bpe_sgmodel {
     int64_t qs_cap = 0;
     int n_cus = 1;
     bpe_sgmodel_query_stats qstats = {};
+    // negative sampling (bpe_sgns.hip.h): transposed planes and partials, grow-only
+    void *d_ns = nullptr;
+    int64_t ns_cap = 0;
+    hipEvent_t nev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bpe_sgmodel_sgns_stats nstats = {};
 };
 
 namespace {
@@ -583,10 +590,10 @@ int sgm_grow(void **buf, int64_t *cap, int64_t bytes) {
     return BPE_OK;
 }
 
-int sgm_time(bpe_sgmodel *M) {
+int sgm_time(bpe_sgmodel *M, double *acc) {
     float ms = 0.f;
     SGM_TRY(hipEventElapsedTime(&ms, M->ev0, M->ev1));
-    M->stats.kernel_ms += ms;
+    *acc += ms;
     return BPE_OK;
 }
 
@@ -613,11 +620,9 @@ int sgm_bad_element(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, cons
     return bpe_fail(BPE_ERR_ARG, msg);
 }
 
-// loss and gradients (into the model's gradient array) from device planes; *loss on the host
-int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const int64_t *d_k, int64_t U, double *loss) {
-    M->stats.calls++;
-    if (U < 0 || (U && (!d_t || !d_c || !d_k))) return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram model planes");
-    SGM_TRY(hipSetDevice(M->device));
+// the planes checked, rowptr, n_t and P (left in the header on the device too); the kernels' time onto *ms
+int sgm_index(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const int64_t *d_k, int64_t U, int64_t *P,
+              double *ms) {
     unsigned long long h[SGMH_WORDS] = {SGM_NONE, 0, 0, 0};
     SGM_TRY(hipMemcpyAsync(M->d_hdr, h, sizeof h, hipMemcpyHostToDevice, M->stream));
     SGM_TRY(hipEventRecord(M->ev0, M->stream));
@@ -630,9 +635,20 @@ int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
     SGM_TRY(hipEventRecord(M->ev1, M->stream));
     SGM_TRY(hipMemcpyAsync(h, M->d_hdr, sizeof h, hipMemcpyDeviceToHost, M->stream));
     SGM_TRY(hipStreamSynchronize(M->stream));
-    if (int rc = sgm_time(M)) return rc;
+    if (int rc = sgm_time(M, ms)) return rc;
     if (h[SGMH_ERR] != SGM_NONE) return sgm_bad_element(M, d_t, d_c, d_k, (int64_t)h[SGMH_ERR]);
-    const int64_t P = (int64_t)h[SGMH_P];
+    *P = (int64_t)h[SGMH_P];
+    return BPE_OK;
+}
+
+// loss and gradients (into the model's gradient array) from device planes; *loss on the host
+int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const int64_t *d_k, int64_t U, double *loss) {
+    M->stats.calls++;
+    if (U < 0 || (U && (!d_t || !d_c || !d_k))) return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram model planes");
+    SGM_TRY(hipSetDevice(M->device));
+    int64_t P = 0;
+    if (int rc = sgm_index(M, d_t, d_c, d_k, U, &P, &M->stats.kernel_ms)) return rc;
+    unsigned long long h[SGMH_WORDS];
     SGM_TRY(hipEventRecord(M->ev0, M->stream));
     if (P == 0) {
         SGM_TRY(hipMemsetAsync(M->d_g, 0, (size_t)M->n4 * 16, M->stream));
@@ -647,7 +663,7 @@ int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
     SGM_TRY(hipEventRecord(M->ev1, M->stream));
     SGM_TRY(hipMemcpyAsync(h, M->d_hdr, sizeof h, hipMemcpyDeviceToHost, M->stream));
     SGM_TRY(hipStreamSynchronize(M->stream));
-    if (int rc = sgm_time(M)) return rc;
+    if (int rc = sgm_time(M, &M->stats.kernel_ms)) return rc;
     double L = 0.0;
     std::memcpy(&L, &h[SGMH_LOSS], 8);
     if (loss) *loss = P ? L : 0.0;
@@ -656,7 +672,7 @@ int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
     return BPE_OK;
 }
 
-int sgm_adam(bpe_sgmodel *M, double lr, double beta1, double beta2, double eps) {
+int sgm_adam(bpe_sgmodel *M, double lr, double beta1, double beta2, double eps, double *ms) {
     M->step++;
     const double c1 = 1.0 / (1.0 - std::pow(beta1, (double)M->step));
     const double c2 = 1.0 / (1.0 - std::pow(beta2, (double)M->step));
@@ -667,7 +683,7 @@ int sgm_adam(bpe_sgmodel *M, double lr, double beta1, double beta2, double eps) 
     SGM_TRY(hipGetLastError());
     SGM_TRY(hipEventRecord(M->ev1, M->stream));
     SGM_TRY(hipStreamSynchronize(M->stream));
-    return sgm_time(M);
+    return sgm_time(M, ms);
 }
 
 // the planes of a host form, in the model's scratch
@@ -742,6 +758,7 @@ int sgm_embed(bpe_sgmodel *M, const int32_t *d_ids, int64_t n, float *d_out) {
 }  // namespace
 
 #include "bpe_sgquery.hip.h"
+#include "bpe_sgns.hip.h"
 
 extern "C" {
 
@@ -780,7 +797,9 @@ int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
     };
     if (hipSetDevice(device) != hipSuccess ||
         hipStreamCreateWithFlags(&M->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&M->ev0) != hipSuccess || hipEventCreate(&M->ev1) != hipSuccess)
+        hipEventCreate(&M->ev0) != hipSuccess || hipEventCreate(&M->ev1) != hipSuccess ||
+        hipEventCreate(&M->nev[0]) != hipSuccess || hipEventCreate(&M->nev[1]) != hipSuccess ||
+        hipEventCreate(&M->nev[2]) != hipSuccess || hipEventCreate(&M->nev[3]) != hipSuccess)
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model stream/events"));
     const size_t flat = (size_t)M->n4 * 16;
     bool ok = true;
@@ -800,6 +819,8 @@ int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model LDS attribute"));
     if (sgq_lds_attrs() != hipSuccess || hipDeviceGetAttribute(&M->n_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
         return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model query attributes"));
+    if (sgn_lds_attrs_all() != hipSuccess)
+        return bail(bpe_fail(BPE_ERR_HIP, "bpe native: skip-gram model negative-sampling LDS attribute"));
     *out = M;
     return BPE_OK;
 }
@@ -810,10 +831,12 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     if (M->stream) (void)hipStreamSynchronize(M->stream);
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
-                    M->d_io, M->d_qs})
+                    M->d_io, M->d_qs, M->d_ns})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
+    for (hipEvent_t e : M->nev)
+        if (e) (void)hipEventDestroy(e);
     if (M->stream) (void)hipStreamDestroy(M->stream);
     delete M;
     return BPE_OK;
@@ -865,7 +888,7 @@ int bpe_sgmodel_adam_step_device(bpe_sgmodel *M, const int32_t *d_targets, const
     if (!(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1))
         return bpe_fail(BPE_ERR_ARG, "bpe native: skip-gram model betas outside [0, 1)");
     if (int rc = sgm_forward(M, d_targets, d_contexts, d_counts, U, loss)) return rc;
-    return sgm_adam(M, lr, beta1, beta2, eps);
+    return sgm_adam(M, lr, beta1, beta2, eps, &M->stats.kernel_ms);
 }
 
 int bpe_sgmodel_adam_step(bpe_sgmodel *M, const int32_t *targets, const int32_t *contexts, const int64_t *counts,

@@ -1267,6 +1267,60 @@ int bpe_sgmodel_predict_device(bpe_sgmodel *m, const int32_t *d_ids, int64_t n, 
 int bpe_sgmodel_get_query_stats(bpe_sgmodel *m, bpe_sgmodel_query_stats *out);
 int bpe_sgmodel_reset_query_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model, negative sampling -------------------------------------------------------------
+ * The same parameters, embed and queries trained with negative sampling (SGNS) instead of the full
+ * softmax: a step costs about (32 U + 4 V S) E flops for U count cells and S negatives, not 4 V^2 E
+ * (csrc/bpe_sgns.hip.h).  Planes as above.  The negatives are one set shared by all targets of a step:
+ * neg_ids[S] int32, strictly ascending, in [0, V), 0 <= S <= V; neg_weights[S] fp32, finite and >= 0
+ * (NULL: 1 / S each); neg_k >= 0, a finite double.  With ls(x) = log sigma(x) and W_c = w_s where
+ * c = a_s, else 0:
+ *   loss   = -(1/P) [ sum_(t,c) C[t,c] ls(z[t,c]) + neg_k sum_t n_t sum_s w_s ls(-z[t,a_s]) ]
+ *   G[t,c] =  (1/P) [ C[t,c] (sigma(z[t,c]) - 1) + neg_k n_t W_c sigma(z[t,c]) ]
+ *   dEin = G Eout, db1 = its column sums, dEout = G^T H, db2 = the column sums of G.
+ * S draws of a noise distribution with w = multiplicity / S is sampled SGNS with shared negatives; all
+ * ids with w = q_c is the exact expected objective.  S == 0 or neg_k == 0 is the positive term alone;
+ * everything is 0 when P == 0.  sigma and ls are evaluated in fp32 from e = exp(-|z|) in forms that do
+ * not cancel; loss partials accumulate in double.  No floating-point atomics and every sum in a fixed
+ * order: the same bytes on every run and in both forms (the transposed planes the context side needs are
+ * rebuilt with integers on every call; nothing of the caller's planes is remembered).
+ *
+ * Errors are BPE_ERR_ARG, nothing is computed and neither the parameters nor the optimizer change: the
+ * plane messages above, `skip-gram model negatives S outside [0, V]`, `skip-gram model neg_k K is
+ * negative or not finite`, and for the smallest offending element of the set `skip-gram model negative
+ * id D outside [0, V) (element I)`, `skip-gram model negative ids must ascend: D after D' (element I)`,
+ * `skip-gram model negative weight W is negative or not finite (element I)`.
+ *
+ * bpe_sgmodel_sgns_adam_step takes the same Adam step as bpe_sgmodel_adam_step on these gradients: the
+ * moments and the step counter are the model's, shared by both.  A wave of the kernels owns
+ * BPE_SGNS_ROWS rows (exported for the tests). */
+#define BPE_SGNS_ROWS 32
+typedef struct {
+    int64_t calls;         /* sgns_loss_grad and sgns_adam_step calls (failed ones too) */
+    int64_t elements;      /* U of the calls that passed their checks */
+    int64_t pairs;         /* ... their P */
+    int64_t negatives;     /* ... their S (0 where neg_k == 0 or P == 0) */
+    double kernel_ms;      /* HIP-event time of all kernels, Adam included */
+    double transpose_ms;   /* of which: building the transposed planes */
+    double target_ms;      /* ... dEin, db1 and the loss */
+    double context_ms;     /* ... dEout and db2 */
+} bpe_sgmodel_sgns_stats;
+int bpe_sgmodel_sgns_loss_grad(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                               int64_t U, const int32_t *neg_ids, const float *neg_weights, int64_t S, double neg_k,
+                               double *loss, float *dEin, float *db1, float *dEout, float *db2);
+int bpe_sgmodel_sgns_loss_grad_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                      const int64_t *d_counts, int64_t U, const int32_t *d_neg_ids,
+                                      const float *d_neg_weights, int64_t S, double neg_k, double *loss, float *d_dEin,
+                                      float *d_db1, float *d_dEout, float *d_db2);
+int bpe_sgmodel_sgns_adam_step(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                               int64_t U, const int32_t *neg_ids, const float *neg_weights, int64_t S, double neg_k,
+                               double lr, double beta1, double beta2, double eps, double *loss);
+int bpe_sgmodel_sgns_adam_step_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                      const int64_t *d_counts, int64_t U, const int32_t *d_neg_ids,
+                                      const float *d_neg_weights, int64_t S, double neg_k, double lr, double beta1,
+                                      double beta2, double eps, double *loss);
+int bpe_sgmodel_get_sgns_stats(bpe_sgmodel *m, bpe_sgmodel_sgns_stats *out);
+int bpe_sgmodel_reset_sgns_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
