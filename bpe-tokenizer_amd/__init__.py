@@ -188,6 +188,7 @@ class Stats(ctypes.Structure):
         ('delta_passes', ctypes.c_int64), ('delta_chunks', ctypes.c_int64),
         ('digest_passes', ctypes.c_int64), ('digest_hits', ctypes.c_int64),
         ('digest_builds', ctypes.c_int64), ('digest_scans', ctypes.c_int64),
+        ('site_chunks', ctypes.c_int64),
     ]
 
     def as_dict(self):

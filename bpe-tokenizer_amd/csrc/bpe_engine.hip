@@ -31,7 +31,8 @@ hipError_t launch_step_loop_table(unsigned grid, hipStream_t s, int32_t *ids, in
 hipError_t launch_apply_loop(unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, void *ctl, void *sums,
                              unsigned long long *replaced, uint32_t *site_list, uint32_t *site_n,
-                             uint32_t *plane, void *lists, uint32_t *rows);
+                             unsigned long long *table, uint32_t *plane, void *lists,
+                             uint32_t *rows);
 hipError_t launch_digest_build(hipStream_t s, const int32_t *ids, int64_t n_chunks, uint32_t *plane);
 hipError_t launch_step_table(int merge, unsigned grid, hipStream_t s, int32_t *ids, int64_t n_chunks,
                              int64_t cpr, int R, const void *carry, int32_t ma, int32_t mb,
@@ -181,8 +182,9 @@ struct bpe_ctx {
     // device-resident mergeUntil loop: control block + merge log (pinned host mirrors)
     LoopCtl *d_ctl = nullptr, *h_ctl = nullptr;
     long long *d_log = nullptr, *h_log = nullptr;
-    // the delta form of the table-state loop: the chunks a pass rewrote, a segment of cpr entries
-    // per region (d_sites, sites_cap entries) and each region's count (d_site_n)
+    // the delta form of the table-state loop: the rewritten chunks a pass listed for the site
+    // kernel, a segment of cpr entries per region (d_sites, sites_cap entries), and each region's
+    // counts (d_site_n: [r] listed, [R + r] rewritten)
     uint32_t *d_sites = nullptr, *d_site_n = nullptr;
     int64_t sites_cap = 0;
     // the digest plane of the delta form's stream: one byte per slot of d_ids (digest_cap bytes).
@@ -705,6 +707,10 @@ constexpr unsigned REDUCE_ROWS_GRID = 4 * INCR_RLIM / 2 / RR_COLS;
 constexpr unsigned REDUCE_TABLE_GRID = HIST_WORDS / REDUCE_WORDS_PER_BLOCK;
 unsigned runs_grid(const bpe_ctx *c) { return (c->R + 255) / 256; }
 unsigned regions_grid(const bpe_ctx *c) { return (c->R + 3) / 4; }   // (one wave per region)
+// (k_runs_loop: the stitch's workgroups, and a wave per SITE_RPW regions for the listed chunks)
+unsigned stitch_sites_grid(const bpe_ctx *c) {
+    return std::max(runs_grid(c), (unsigned)(c->R + SITE_REGIONS_PER_WG - 1) / SITE_REGIONS_PER_WG);
+}
 
 // (The code object lays the kernel templates out in the order the unit first names them: named
 // here in the order they have always had, rearranging the host code below moves no device code.)
@@ -758,12 +764,11 @@ int enqueue_stitch_reduce(bpe_ctx *c, const Pass &p) {
             k_runs<MODE_TABLE><<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
                                                             c->cold, c->d_heavy, p.ctl);
         else {
-            // either form's stitch in one launch; after the apply-only stream the sites' deltas
-            // into the table (after a full pass k_site_delta returns at once)
-            k_runs_loop<<<runs_grid(c), 256, 0, s>>>(c->d_sums, c->R, c->d_carry, c->d_spill,
-                                                     c->cold, c->d_heavy, p.ctl, c->d_site_n);
-            k_site_delta<<<c->R, 256, 0, s>>>(c->d_ids, c->n_chunks, c->cpr, c->R, c->d_sites,
-                                              c->d_site_n, c->d_hot, p.ctl);
+            // either form's stitch in one launch, and with it, after the apply-only stream, the
+            // deltas of the listed chunks' sites into the table
+            k_runs_loop<<<stitch_sites_grid(c), 256, 0, s>>>(
+                c->d_sums, c->R, c->d_carry, c->d_spill, c->cold, c->d_heavy, p.ctl, c->d_ids,
+                c->n_chunks, c->cpr, c->d_sites, c->d_site_n, c->d_hot);
         }
         // (after a delta iteration it sums nothing: the scan of the table alone.  A rank: this
         // shard's table, replacement count and largest bin into the exchange buffer, no best key)
@@ -846,10 +851,10 @@ int enqueue_loop_invalidate(bpe_ctx *c, const Pass &p) {
 }
 
 // MODE_TABLE with p.delta: the launch list is fixed and holds both forms of the iteration, the
-// full pass and the delta form (k_apply_loop streams the merge in without counting and lists the
-// rewritten chunks, k_runs_loop stitches either form, k_site_delta adds the sites' deltas to the
-// table, and k_reduce_table then only scans it); the kernels of the form the decision did not
-// take return on LoopCtl::delta.
+// full pass and the delta form (k_apply_loop streams the merge in without counting, adds the
+// table deltas of the plain sites and lists the chunks holding other sites, k_runs_loop stitches
+// either form and adds the listed chunks' deltas, and k_reduce_table then only scans the table);
+// the kernels of the form the decision did not take return on LoopCtl::delta.
 int enqueue_loop_pass(bpe_ctx *c, const Pass &p) {
     int rc;
     hipStream_t s = c->stream;
@@ -871,7 +876,8 @@ int enqueue_loop_pass(bpe_ctx *c, const Pass &p) {
         if (p.delta)
             HIP_TRY(bpe_step::launch_apply_loop(c->G, s, c->d_ids, c->n_chunks, c->cpr, c->R,
                                                 c->d_carry, c->d_ctl, c->d_sums, rep, c->d_sites,
-                                                c->d_site_n, c->d_digest, c->d_lists, c->d_rows));
+                                                c->d_site_n, c->d_hot, c->d_digest, c->d_lists,
+                                                c->d_rows));
     }
     HIP_TRY(hipGetLastError());
     // (span kind 2, the incr_* statistics: the single context's maintained passes only)
@@ -1452,6 +1458,7 @@ void loop_stats(bpe_ctx *c, const LoopCtl *h) {
     c->stats.loop_host += h->n_host;
     c->stats.delta_passes += h->n_delta;
     c->stats.delta_chunks += (int64_t)h->delta_chunks;
+    c->stats.site_chunks += (int64_t)h->site_chunks;
     c->stats.digest_passes += h->n_digest;
     c->stats.digest_hits += (int64_t)h->digest_hits;
     c->stats.digest_scans += h->n_scan;
@@ -2809,7 +2816,7 @@ int bpe_create(bpe_ctx **out, int device) {
     if ((rc = dev_alloc(&c->d_ctl, 1))) return bail(rc);
     if ((rc = dev_alloc(&c->d_ticket, TICKET_WORDS))) return bail(rc);
     if ((rc = dev_alloc(&c->d_brec, COLD_GRID))) return bail(rc);
-    if ((rc = dev_alloc(&c->d_site_n, MAX_REGIONS))) return bail(rc);
+    if ((rc = dev_alloc(&c->d_site_n, 2 * MAX_REGIONS))) return bail(rc);
     if ((rc = dev_alloc(&c->d_lists, 1))) return bail(rc);
     // (no pair cached, no row to apply from, no block keys)
     if (hipMemset(c->d_lists, 0, sizeof(DigestLists)) != hipSuccess ||

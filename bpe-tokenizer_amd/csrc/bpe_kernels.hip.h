@@ -1,7 +1,7 @@
 // bpe_kernels.hip.h — CDNA4 (gfx950) kernels of the BPE merge-training hot path: everything the
 // engine launches.  The constants, the layout structs, the streaming pass and the digest stream
 // are in bpe_pass.hip.h (the part csrc/bpe_step.hip compiles with its own flags); this header adds
-// the delta form's site kernel, the stitch and the reduces, the selection and the decision, and
+// the delta form's site walk, the stitch and the reduces, the selection and the decision, and
 // the kernels of ingest, compaction and read-back.
 #pragma once
 #include "bpe_pass.hip.h"
@@ -59,7 +59,7 @@ __device__ __forceinline__ int32_t live_next(const int32_t *ids, int64_t n_chunk
 //    chain's last site (n = the c's up to and including this one);
 //  - right, only when y != c (the next site's left side covers that adjacency): removed (b, y),
 //    or, y == b, one (b, b) less iff the M' b's that follow are odd in number; added (c, y).
-// The pair (a, b) itself loses W, once for the whole merge (k_site_delta).
+// The pair (a, b) itself loses W, once for the whole merge (k_runs_loop).
 __device__ void site_deltas(const int32_t *ids, int64_t n_chunks, const Cursor &p, int32_t a,
                             int32_t b, int32_t c, unsigned long long *table) {
     auto add = [&](int32_t x, int32_t y, long long d) {
@@ -99,49 +99,52 @@ __device__ void site_deltas(const int32_t *ids, int64_t n_chunks, const Cursor &
     }
 }
 
-// After a delta iteration's apply-only stream, on the consistent post-merge corpus: one workgroup
-// per region, one wave per listed chunk (k_apply_loop's site list), every token c of the chunk a
-// site (a site across two chunks lists both; the chunk holding the c owns it).  The deltas go
+// The site share of k_runs_loop, after a delta iteration's apply-only stream, on the consistent
+// post-merge corpus: a wave takes the listed chunks of SITE_RPW regions (k_apply_loop's site list),
+// one chunk at a time.  Every token c of the chunk is a site (a site across two chunks lists the
+// chunk holding the c, which owns it); the plain ones had their deltas from the stream
+// (plain_site, the same test on the same slots), the others get site_deltas here.  The deltas go
 // into the u64 table with 64-bit atomic adds (negative ones as two's complement), bins from
-// table_index: hot bins and sketch buckets alike.  The bin of (a, b) loses W; a hot bin must have
-// held exactly W, a sketch bucket at least W (it sums every pair it holds), else LOOP_ERROR.
-__global__ void __launch_bounds__(256)
-k_site_delta(const int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
-             const uint32_t *__restrict__ site_list, const uint32_t *__restrict__ site_n,
-             unsigned long long *__restrict__ table, LoopCtl *ctl) {
-    if (ctl->status != LOOP_RUN || !ctl->delta) return;
-    const int32_t a = ctl->a, b = ctl->b, c = ctl->c;
-    const unsigned long long W = (unsigned long long)ctl->w;
-    const int r = blockIdx.x;
-    if (r >= R) return;
-    if (r == 0 && threadIdx.x == 0) {
-        const int bin = table_index(a, b);
-        const unsigned long long old = atomicAdd(&table[bin], 0ull - W);
-        if (bin < HOT_BINS ? old != W : old < W) {
-            ctl->status = LOOP_ERROR;
-            ctl->err = 3;
-            ctl->err_got = old;
-            ctl->err_want = W;
-        }
-    }
+// table_index: hot bins and sketch buckets alike.
+constexpr int SITE_RPW = 4;
+constexpr int SITE_REGIONS_PER_WG = 4 * SITE_RPW;   // (workgroups of 256 threads)
+
+__device__ __forceinline__ void sites_body(const int32_t *__restrict__ ids, int64_t n_chunks,
+                                           int64_t cpr, int R,
+                                           const uint32_t *__restrict__ site_list,
+                                           const uint32_t *__restrict__ site_n,
+                                           unsigned long long *__restrict__ table, int32_t a,
+                                           int32_t b, int32_t c) {
     const int lane = threadIdx.x & 63;
-    const uint32_t n = min(site_n[r], (uint32_t)cpr);
-    const uint32_t *seg = site_list + (int64_t)r * cpr;
-    for (uint32_t i = threadIdx.x >> 6; i < n; i += 4) {
-        const int64_t q = seg[i];
-        if (q >= n_chunks) continue;
-        const int4 v = reinterpret_cast<const int4 *>(ids)[q * (CHUNK / 4) + lane];
-        const int32_t l3 = bcast(v.w, 63);
-        Cursor p;
-        p.q = q;
-        p.len = l3 >= SEP ? CHUNK : ((LEN_TAG - l3) & 255);
-        const int32_t t[4] = {v.x, v.y, v.z, v.w};
+    const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    for (int r0 = gw * SITE_RPW; r0 < R; r0 += (int)gridDim.x * SITE_REGIONS_PER_WG) {
+        // (the counts of the wave's regions in one round trip)
+        const uint32_t cnt =
+            lane < SITE_RPW && r0 + lane < R ? min(site_n[r0 + lane], (uint32_t)cpr) : 0u;
+        if (__ballot(cnt != 0u) == 0ull) continue;
+        for (int j = 0; j < SITE_RPW; ++j) {
+            const uint32_t n = (uint32_t)bcast((int32_t)cnt, j);
+            const uint32_t *seg = site_list + (int64_t)(r0 + j) * cpr;
+            for (uint32_t i = 0; i < n; ++i) {
+                const int64_t q = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)seg[i]);
+                if (q >= n_chunks) continue;
+                const int4 v = reinterpret_cast<const int4 *>(ids)[q * (CHUNK / 4) + lane];
+                const int32_t l3 = bcast(v.w, 63);
+                Cursor p;
+                p.q = q;
+                p.len = l3 >= SEP ? CHUNK : ((LEN_TAG - l3) & 255);
+                const int32_t t[4] = {v.x, v.y, v.z, v.w};
+                const int32_t lf = from_prev(t[3], NONE), rt = from_next(t[0], NONE);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (t[e] == c) {
-                p.k = 4 * lane + e;
-                site_deltas(ids, n_chunks, p, a, b, c, table);
+                for (int e = 0; e < 4; ++e) {
+                    const int32_t x = e == 0 ? lf : t[e > 0 ? e - 1 : 0];
+                    const int32_t y = e == 3 ? rt : t[e < 3 ? e + 1 : 0];
+                    p.k = 4 * lane + e;
+                    if (t[e] == c && !plain_site(p.k, p.len, x, y, a, b, c))
+                        site_deltas(ids, n_chunks, p, a, b, c, table);
+                }
             }
+        }
     }
 }
 
@@ -170,14 +173,20 @@ __device__ __forceinline__ void runs_body(const RegionSum *__restrict__ s, int R
                                           int32_t ma, int32_t mb, int32_t mc,
                                           unsigned long long *hot, unsigned long long *delta,
                                           const uint32_t *__restrict__ site_n = nullptr,
+                                          unsigned long long *n_rewritten = nullptr,
                                           unsigned long long *n_listed = nullptr) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (site_n && !loop_off(ctl)) {
-        // the delta form's statistic: chunks listed by the pass, one atomic per wave
-        unsigned n = r < R ? site_n[r] : 0u;
+        // the delta form's statistics: chunks the pass rewrote (site_n[R + r]) and those of them
+        // it listed (site_n[r]), one atomic each per wave
+        unsigned n = r < R ? site_n[R + r] : 0u, l = r < R ? site_n[r] : 0u;
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d);
-        if ((threadIdx.x & 63) == 0 && n) atomicAdd(n_listed, (unsigned long long)n);
+        for (int d = 32; d >= 1; d >>= 1) {
+            n += __shfl_xor(n, d);
+            l += __shfl_xor(l, d);
+        }
+        if ((threadIdx.x & 63) == 0 && n) atomicAdd(n_rewritten, (unsigned long long)n);
+        if ((threadIdx.x & 63) == 0 && l) atomicAdd(n_listed, (unsigned long long)l);
     }
     if (r >= R) return;
     // the region and its two neighbours, loaded together before anything else (the loop's state
@@ -285,17 +294,43 @@ __global__ void k_runs(const RegionSum *__restrict__ s, int R, RegionCarry *__re
 }
 
 // The table state's stitch when the delta form is allowed, one launch for either form of the
-// iteration: after a full pass k_runs<MODE_TABLE>; after the apply-only stream the carries alone
-// (k_runs<MODE_NONE>) and the count of the chunks it listed (LoopCtl::delta_chunks).
-__global__ void k_runs_loop(const RegionSum *__restrict__ s, int R, RegionCarry *__restrict__ carry,
-                            unsigned long long *__restrict__ spill, ColdTable ct,
-                            const uint32_t *__restrict__ heavy, LoopCtl *ctl,
-                            const uint32_t *__restrict__ site_n) {
-    if (ctl->delta)
-        runs_body<MODE_NONE>(s, R, carry, nullptr, ct, nullptr, ctl, -1, -1, -1, nullptr, nullptr,
-                             site_n, &ctl->delta_chunks);
-    else
-        runs_body<MODE_TABLE>(s, R, carry, spill, ct, heavy, ctl, -1, -1, -1, nullptr, nullptr);
+// iteration.  After a full pass: k_runs<MODE_TABLE>, by the first ceil(R / 256) workgroups; the
+// others return.  After the apply-only stream those workgroups rebuild the carries alone
+// (k_runs<MODE_NONE>) and sum the chunks it rewrote and listed (LoopCtl::delta_chunks,
+// site_chunks), and every workgroup of the grid then takes its regions' listed chunks
+// (sites_body): the two parts share nothing but the finished stream.  The bin of (a, b) loses W,
+// once for the whole merge; a hot bin must have held exactly W, a sketch bucket at least W (it
+// sums every pair it holds), else LOOP_ERROR.  (No plain site's delta addresses the pair (a, b).)
+__global__ void __launch_bounds__(256)
+k_runs_loop(const RegionSum *__restrict__ s, int R, RegionCarry *__restrict__ carry,
+            unsigned long long *__restrict__ spill, ColdTable ct,
+            const uint32_t *__restrict__ heavy, LoopCtl *ctl, const int32_t *__restrict__ ids,
+            int64_t n_chunks, int64_t cpr, const uint32_t *__restrict__ site_list,
+            const uint32_t *__restrict__ site_n, unsigned long long *__restrict__ table) {
+    // (both words loaded before either is tested: one memory latency)
+    const int32_t status = ctl->status, delta = ctl->delta;
+    if (status != LOOP_RUN) return;
+    if ((int)(blockIdx.x * blockDim.x) < R) {
+        if (delta)
+            runs_body<MODE_NONE>(s, R, carry, nullptr, ct, nullptr, ctl, -1, -1, -1, nullptr,
+                                 nullptr, site_n, &ctl->delta_chunks, &ctl->site_chunks);
+        else
+            runs_body<MODE_TABLE>(s, R, carry, spill, ct, heavy, ctl, -1, -1, -1, nullptr, nullptr);
+    }
+    if (!delta) return;
+    const int32_t a = ctl->a, b = ctl->b, c = ctl->c;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const unsigned long long W = (unsigned long long)ctl->w;
+        const int bin = table_index(a, b);
+        const unsigned long long old = atomicAdd(&table[bin], 0ull - W);
+        if (bin < HOT_BINS ? old != W : old < W) {
+            ctl->status = LOOP_ERROR;
+            ctl->err = 3;
+            ctl->err_got = old;
+            ctl->err_want = W;
+        }
+    }
+    sites_body(ids, n_chunks, cpr, R, site_list, site_n, table, a, b, c);
 }
 
 // Sums the per-workgroup 16-bit LDS partials and the spill table into the u64 table (hot bins
@@ -331,7 +366,7 @@ k_reduce_table(const uint32_t *__restrict__ partials, int G, unsigned long long 
                unsigned long long *__restrict__ bkey = nullptr) {
     __shared__ uint32_t s_sum[REDUCE_GROUPS][32][8];
     // A delta iteration of the device loop (LoopCtl::delta, uniform over the grid): the table is
-    // already current (k_site_delta), so nothing is summed or written; the block only scans its
+    // already current (the sites' deltas), so nothing is summed or written; the block only scans its
     // 256 bins for the best hot key and the largest bin, as after a reduce.  (Both words loaded
     // before either is tested: one memory latency.)
     const int32_t status = ctl ? ctl->status : LOOP_RUN;

@@ -219,7 +219,7 @@ struct LoopCtl {
     int32_t n_unscreened;   // decisions that set it, in this batch
     // The delta form of a table-state iteration (single-context loop): the merge is applied by an
     // apply-only stream (k_apply_loop) that lists the chunks it rewrites, and the table is kept by
-    // the deltas of the merge's sites (k_site_delta) instead of a recount.  Set by the decision
+    // the deltas of the merge's sites (plain_deltas, site_deltas) instead of a recount.  Set by the decision
     // for a merge of two distinct ids in fewer than 1/16 of the chunks, when the host allows it
     // (allow_delta: the table state, BPE_DELTA != 0); every kernel of the form not taken returns
     // at once.  err 3: the table's bin of (a, b) did not hold W.
@@ -232,7 +232,8 @@ struct LoopCtl {
     // the full form (the full pass rewrites chunks without the plane): stale for the rest of the
     // batch.
     int32_t digest_ok;
-    unsigned long long delta_chunks;   // chunks listed by the delta iterations of this batch
+    unsigned long long delta_chunks;   // chunks rewritten by the delta iterations of this batch
+    unsigned long long site_chunks;    // ... of which listed for the site kernel (plain_site)
     unsigned long long digest_hits;    // chunks the digest stream took to the exact path
     int32_t n_digest;       // delta iterations on the plane, in this batch
     int32_t n_scan;         // ... of which streamed the plane (the others took a cached hit list)
@@ -1306,11 +1307,45 @@ struct Apply {
     int32_t match;       // it is an `a` matched with the chunk's first live token
     uint32_t n_match;
     // SITES (the delta form's apply-only stream): the region's segment of the site list, the
-    // entries written so far, and the region's first chunk (entries are corpus chunk indices)
+    // chunks rewritten so far and those of them listed (a chunk holding a site that is not plain,
+    // plain_site), the region's first chunk (entries are corpus chunk indices), and the u64 pair
+    // table the plain sites' deltas go to
     uint32_t *sites;
     uint32_t n_sites;
+    uint32_t n_listed;
     uint32_t c0;
+    unsigned long long *table;
 };
+
+// A plain site of the merge (a, b) -> c, a != b: the token c at live slot k of a post-merge chunk of
+// len live slots, x and y the slots before and after it.  Both neighbours lie in the chunk (a site
+// completed across a chunk or region edge holds the chunk's last live slot, so none is plain), x
+// ends no run of a and no chain of c, y starts no run of b and is no site itself.  Its table deltas
+// then need no walk (plain_deltas); every other site is site_deltas' (bpe_kernels.hip.h).  The
+// stream that rewrites the chunk and the site kernel both decide by this predicate alone: a site
+// is counted by exactly one of them.
+__device__ __forceinline__ bool plain_site(int k, int len, int32_t x, int32_t y, int32_t a,
+                                           int32_t b, int32_t c) {
+    return (k > 0) & (k < len - 1) & (x != a) & (x != c) & (y != b) & (y != c);
+}
+
+// The deltas of a plain site: before the merge it read x a b y (SEP ends a sample: that side has no
+// pair).  Adds that return nothing; negative ones as two's complement.
+__device__ __forceinline__ void plain_deltas(unsigned long long *table, int32_t x, int32_t y,
+                                             int32_t a, int32_t b, int32_t c) {
+    auto add = [&](int32_t p, int32_t q, unsigned long long d) {
+        __hip_atomic_fetch_add(&table[table_index(p, q)], d, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if (x >= 0) {
+        add(x, a, ~0ull);
+        add(x, c, 1ull);
+    }
+    if (y >= 0) {
+        add(b, y, ~0ull);
+        add(c, y, 1ull);
+    }
+}
 
 // What a k_step pass does before counting: nothing, a merge of two distinct ids, or an X X merge
 // (the only kind whose matches depend on run parity, so the only one carrying that code).
@@ -1324,7 +1359,8 @@ __device__ __forceinline__ void tag_tail(int32_t (&y)[4], int total, int32_t las
 // Applies the merge (a, b) -> c to one pre-merge chunk (w.len > 0) at chunk index c of the region,
 // in place: nxt = the first pre-merge live token after it (the next region's first for the last
 // chunk).  A touched chunk is re-packed and written back.
-// SITES: every chunk written back is appended to the wave's own segment of the site list.
+// SITES: the plain sites of a chunk written back add their deltas to the pair table; a chunk
+// holding any other site is appended to the wave's own segment of the site list.
 template <int MERGE, bool PREP = false, bool SITES = false>
 __device__ __forceinline__ void apply_chunk(Chunk &w, int32_t nxt, int32_t ma, int32_t mb,
                                             int32_t mc,
@@ -1424,14 +1460,39 @@ __device__ __forceinline__ void apply_chunk(Chunk &w, int32_t nxt, int32_t ma, i
 #pragma unroll
         for (int e = 0; e < 4; ++e) w.t[e] = y[e];
         tag_tail(y, total, last);
-        __builtin_amdgcn_raw_buffer_store_b128(
-            __builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned,
-                               make_uint4((unsigned)y[0], (unsigned)y[1], (unsigned)y[2], (unsigned)y[3])),
-            rs, lane * 16, c * (CHUNK * 4), 0);
+        const auto out = __builtin_bit_cast(
+            __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned,
+            make_uint4((unsigned)y[0], (unsigned)y[1], (unsigned)y[2], (unsigned)y[3]));
+        __builtin_amdgcn_raw_buffer_store_b128(out, rs, lane * 16, c * (CHUNK * 4), 0);
+        // The store reads its four data registers for a while after it issues.  With the chunk's
+        // offset in a scalar register the compiler assumes no wait is needed and may reuse them in
+        // the very next instruction; on gfx950 a write that close reached memory in the last
+        // quarter of each row of 16 lanes (the site code's first DPP move, in one chunk in ten).
+        // The registers stay live up to the wait, so nothing writes them before it.
+        asm volatile("s_nop 3" : : "v"(out) : "memory");
         ap.n_match += (uint32_t)(__popcll(M0) + __popcll(M1) + __popcll(M2) + __popcll(M3));
         if (SITES) {
+            // Every c of the repacked chunk is a site (c is a fresh id; dead slots are negative).
+            // The plain ones get their deltas here, neighbours from the registers; the chunk is
+            // listed for the site kernel only when it holds another kind.
+            const int32_t lf = from_prev(w.t[3], NONE), rt = from_next(w.t[0], NONE);
+            bool other = false;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int32_t x = e == 0 ? lf : w.t[e > 0 ? e - 1 : 0];
+                const int32_t yy = e == 3 ? rt : w.t[e < 3 ? e + 1 : 0];
+                if (w.t[e] == mc) {
+                    if (plain_site(4 * lane + e, total, x, yy, ma, mb, mc))
+                        plain_deltas(ap.table, x, yy, ma, mb, mc);
+                    else
+                        other = true;
+                }
+            }
             // (a chunk is rewritten at most once per pass, so the segment of cpr entries holds)
-            if (lane == 0) ap.sites[ap.n_sites] = ap.c0 + (uint32_t)c;
+            if (__ballot(other) != 0ull) {
+                if (lane == 0) ap.sites[ap.n_listed] = ap.c0 + (uint32_t)c;
+                ++ap.n_listed;
+            }
             ++ap.n_sites;
         }
         w.len = total;
@@ -1460,8 +1521,10 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
                                           unsigned long long *__restrict__ hot_g = nullptr,
                                           unsigned long long *__restrict__ delta = nullptr,
                                           uint32_t *__restrict__ site_list = nullptr,
-                                          uint32_t *__restrict__ site_n = nullptr) {
-    // (SITES: site_list holds a segment of cpr entries per region, site_n the entries written)
+                                          uint32_t *__restrict__ site_n = nullptr,
+                                          unsigned long long *site_table = nullptr) {
+    // (SITES: site_list holds a segment of cpr entries per region; site_n[r] the entries written
+    // and site_n[R + r] the chunks rewritten; site_table the u64 pair table of the plain sites)
     // (MODE_INCR: `spill` holds the rows' spill, 4 * INCR_RLIM u64; hot_g the maintained table;
     // delta: a sharded rank's delta rows, which then take the touched pairs instead of the tables)
     unsigned long long *rspill = spill;
@@ -1526,7 +1589,9 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
         ap.n_match = 0;
         ap.sites = SITES ? site_list + c0 : nullptr;
         ap.n_sites = 0;
+        ap.n_listed = 0;
         ap.c0 = (uint32_t)c0;
+        ap.table = SITES ? site_table : nullptr;
         // the region through a range-checked buffer descriptor (loads past its end return 0 and
         // are never consumed)
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -1693,7 +1758,10 @@ __device__ __forceinline__ void step_body(uint32_t *hist, int32_t *__restrict__ 
             o.trail_odd = s.par ^ 1;   // trail run length = offset of the last token + 1
             sums[r] = o;
             if (MERGE && ap.n_match) atomicAdd(replaced, (unsigned long long)ap.n_match);
-            if (SITES) site_n[r] = ap.n_sites;
+            if (SITES) {
+                site_n[r] = ap.n_listed;
+                site_n[R + r] = ap.n_sites;
+            }
         }
     }
     if (MODE == MODE_TABLE || MODE == MODE_FUSED) {
@@ -1996,7 +2064,8 @@ __device__ __forceinline__ RegionSum region_resum(const __amdgpu_buffer_rsrc_t r
 // table is the workgroup's: every wave zeroes a part, wave 0 derives the candidates, sets their
 // entries and publishes the set of slots in use (wg_acc[3]); waves without a region take part
 // up to the second barrier and leave.
-// A rewritten chunk's digests are stored with it and the chunk is listed for k_site_delta.  The
+// A rewritten chunk's digests are stored with it, its plain sites' deltas go to the table at once
+// and the chunk is listed for the site kernel when it holds another kind (apply_chunk).  The
 // region's sums are left as the last pass wrote them unless a chunk was rewritten; then n_live
 // loses the removed slots and the edge fields are read again (region_resum).
 // A scan (use < 0) streams the plane once and answers the first two conditions for up to `ncand`
@@ -2011,6 +2080,7 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
                                             unsigned long long *__restrict__ replaced,
                                             uint32_t *__restrict__ site_list,
                                             uint32_t *__restrict__ site_n,
+                                            unsigned long long *site_table,
                                             unsigned long long *__restrict__ n_hits,
                                             DigestLists *__restrict__ dl,
                                             uint32_t *__restrict__ rows, int ncand, int use,
@@ -2101,7 +2171,9 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
     ap.n_match = 0;
     ap.sites = site_list + c0;
     ap.n_sites = 0;
+    ap.n_listed = 0;
     ap.c0 = (uint32_t)c0;
+    ap.table = site_table;
     Prep pp;
     pp.ok = 0;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -2322,7 +2394,8 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
         if (lane == 0) sums[r] = o;
     }
     if (lane == 0) {
-        site_n[r] = ap.n_sites;
+        site_n[r] = ap.n_listed;
+        site_n[R + r] = ap.n_sites;
         // The two counters go through the workgroup (wg_acc: replaced, hits, waves done, and the
         // scan's candidate slots; zero at the start): a list iteration's waves all end within microseconds of each other, and
         // thousands of atomics on one address would then be the launch's critical path.  The
@@ -2342,7 +2415,8 @@ __device__ __forceinline__ void digest_body(int32_t *__restrict__ ids, uint32_t 
 
 // The delta form's apply-only stream: the merge in the LoopCtl applied as by k_apply<MERGE_XY> (no
 // LDS table, no slab, no pair counted; the region sums kept, so k_runs<MODE_NONE> rebuilds the
-// carries and a full pass can follow), every rewritten chunk listed for k_site_delta.  With a
+// carries and a full pass can follow), the deltas of the plain sites added to the u64 table as
+// their chunks are rewritten and the chunks holding other sites listed for k_runs_loop.  With a
 // fresh digest plane (LoopCtl::digest_ok) the sites are found through it (digest_body), else by
 // streaming the int32 slots: one launch, a uniform branch between the two bodies.
 __global__ void __launch_bounds__(WG)
@@ -2350,8 +2424,8 @@ k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
              const RegionCarry *__restrict__ carry, LoopCtl *__restrict__ ctl,
              RegionSum *__restrict__ sums, unsigned long long *__restrict__ replaced,
              uint32_t *__restrict__ site_list, uint32_t *__restrict__ site_n,
-             uint32_t *__restrict__ plane, DigestLists *__restrict__ dl,
-             uint32_t *__restrict__ rows) {
+             unsigned long long *table, uint32_t *__restrict__ plane,
+             DigestLists *__restrict__ dl, uint32_t *__restrict__ rows) {
     if (ctl->status != LOOP_RUN || !ctl->delta) return;
     if (ctl->digest_ok) {
         // (from the decided pair's cached row when the decision found one, DigestLists::use; else
@@ -2362,12 +2436,12 @@ k_apply_loop(int32_t *__restrict__ ids, int64_t n_chunks, int64_t cpr, int R,
         if (threadIdx.x < 4) wg_acc[threadIdx.x] = 0;
         __syncthreads();
         digest_body(ids, plane, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, sums, replaced,
-                    site_list, site_n, &ctl->digest_hits, dl, rows, ctl->digest_cand, dl->use, wg_acc,
+                    site_list, site_n, table, &ctl->digest_hits, dl, rows, ctl->digest_cand, dl->use, wg_acc,
                     dg_table);
     } else
         step_body<MERGE_XY, MODE_NONE, true, true, true>(
             nullptr, ids, n_chunks, cpr, R, carry, ctl->a, ctl->b, ctl->c, nullptr, nullptr,
-            ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n);
+            ColdTable{}, nullptr, sums, replaced, nullptr, nullptr, site_list, site_n, table);
 }
 
 }  // namespace bpe

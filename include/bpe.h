@@ -345,7 +345,7 @@ typedef struct {
     int64_t delta_passes;     /* device loop, table state: iterations in the delta form (an apply-only
                                  stream, then the table kept by the deltas of the merge's sites
                                  instead of a recount; BPE_DELTA=0 turns the form off) */
-    int64_t delta_chunks;     /* ... and the rewritten chunks those streams listed for the site kernel */
+    int64_t delta_chunks;     /* ... and the chunks those streams rewrote */
     int64_t digest_passes;    /* ... of the delta iterations, those whose stream read the digest plane
                                  (one byte per slot) instead of the int32 slots; BPE_DIGEST=0 keeps
                                  the int32 stream everywhere */
@@ -355,6 +355,10 @@ typedef struct {
     int64_t digest_scans;     /* ... of the digest_passes, those that streamed the plane (and filled the
                                  hit lists of up to BPE_DIGEST_CAND pairs); the others applied their
                                  merge from a cached list */
+    int64_t site_chunks;      /* ... of the delta_chunks, those listed for the site kernel: the stream
+                                 itself adds the table deltas of a plain site (both neighbours in its
+                                 chunk, neither an a or c before it nor a b or c after it); a chunk
+                                 is listed only when it holds a site that is not plain */
 } bpe_stats;
 
 int bpe_stats_enable(bpe_ctx *ctx, int on);
