@@ -82,6 +82,7 @@ C_API = [
     'bpe_sgmodel_get_query_stats', 'bpe_sgmodel_reset_query_stats',
     'bpe_sgmodel_sgns_loss_grad', 'bpe_sgmodel_sgns_loss_grad_device', 'bpe_sgmodel_sgns_adam_step',
     'bpe_sgmodel_sgns_adam_step_device', 'bpe_sgmodel_get_sgns_stats', 'bpe_sgmodel_reset_sgns_stats',
+    'bpe_sgmodel_set_counts_form', 'bpe_sgmodel_get_dense_stats', 'bpe_sgmodel_reset_dense_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -151,7 +152,11 @@ SGM_MAX_TOPK = 64                # BPE_SGM_MAX_TOPK: the largest k of its querie
 SGM_DOT = 0                      # BPE_SGM_DOT
 SGM_COSINE = 1                   # BPE_SGM_COSINE
 SGNS_ROWS = 32                   # BPE_SGNS_ROWS: rows a wave of the negative-sampling kernels owns
+SGM_FORM_CSR, SGM_FORM_DENSE, SGM_FORM_AUTO = 0, 1, 2   # BPE_SGM_FORM_*: how the training steps read the counts
+SGM_MAX_SPLITS = 256             # BPE_SGM_MAX_SPLITS: the most splits of the dense form's streamed axis
+SGM_DENSE_THETA = 1 / 64         # BPE_SGM_DENSE_THETA: 'auto' runs the dense form from this density U / dim^2 on
 _SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
+_SGM_FORMS = {'csr': SGM_FORM_CSR, 'dense': SGM_FORM_DENSE, 'auto': SGM_FORM_AUTO}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
                 LINES_TRIM: LINES_TRIM, LINES_KEEP: LINES_KEEP, LINES_FILE: LINES_FILE}
 
@@ -331,6 +336,15 @@ class SkipgramSgnsStats(ctypes.Structure):
     _fields_ = [('calls', ctypes.c_int64), ('elements', ctypes.c_int64), ('pairs', ctypes.c_int64),
                 ('negatives', ctypes.c_int64), ('kernel_ms', ctypes.c_double), ('transpose_ms', ctypes.c_double),
                 ('target_ms', ctypes.c_double), ('context_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramDenseStats(ctypes.Structure):
+    """bpe_sgmodel_dense_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('dense_calls', ctypes.c_int64), ('last_form', ctypes.c_int64),
+                ('last_splits', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -601,6 +615,9 @@ def lib():
                                                ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         'bpe_sgmodel_get_sgns_stats': ([vp, ctypes.POINTER(SkipgramSgnsStats)], ctypes.c_int),
         'bpe_sgmodel_reset_sgns_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_set_counts_form': ([vp, ctypes.c_int, ctypes.c_int], ctypes.c_int),
+        'bpe_sgmodel_get_dense_stats': ([vp, ctypes.POINTER(SkipgramDenseStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_dense_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -2789,6 +2806,25 @@ class SkipgramModel:
 
     def reset_sgns_stats(self):
         _check(lib().bpe_sgmodel_reset_sgns_stats(self._m), 'bpe_sgmodel_reset_sgns_stats')
+
+    # ---- dense counts (include/bpe.h, "skip-gram model, dense counts"; csrc/bpe_sgdense.hip.h) ----
+    def set_counts_form(self, form='csr', splits=0):
+        """How all eight training calls read the counts from here on: 'csr' (the default), 'dense' (a dim x dim
+        fp32 tile source, for matrices where most cells are nonzero) or 'auto' (dense from a density of
+        SGM_DENSE_THETA on).  splits: 0 chooses, 1..SGM_MAX_SPLITS forces (bpe_sgmodel_set_counts_form; the
+        library refuses anything else, and an unknown name goes as -1)."""
+        form = _SGM_FORMS.get(form, -1) if isinstance(form, str) else int(form)
+        _check(lib().bpe_sgmodel_set_counts_form(self._m, form, int(splits)), 'bpe_sgmodel_set_counts_form')
+
+    def dense_stats(self):
+        s = SkipgramDenseStats()
+        _check(lib().bpe_sgmodel_get_dense_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_dense_stats')
+        d = s.as_dict()
+        d['last_form'] = {v: k for k, v in _SGM_FORMS.items()}[d['last_form']]
+        return d
+
+    def reset_dense_stats(self):
+        _check(lib().bpe_sgmodel_reset_dense_stats(self._m), 'bpe_sgmodel_reset_dense_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

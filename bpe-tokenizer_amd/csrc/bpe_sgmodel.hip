@@ -40,6 +40,8 @@
 //   k_sgm_embed   rows Ein[id] + b1.
 // The queries of a trained model (nearest tokens, top contexts) are in bpe_sgquery.hip.h, and the same
 // parameters trained with negative sampling instead of the full softmax in bpe_sgns.hip.h, both included below.
+// bpe_sgdense.hip.h, included with them, is the second form of both training steps: the counts as a dense
+// V x V tile source instead of CSR entries, chosen per model by bpe_sgmodel_set_counts_form.
 // No floating-point atomics; every reduction has a fixed order, so results are the same bytes on
 // every run and route.
 #include <hip/hip_runtime.h>
@@ -549,6 +551,12 @@ struct bpe_sgmodel {
     int64_t ns_cap = 0;
     hipEvent_t nev[4] = {nullptr, nullptr, nullptr, nullptr};
     bpe_sgmodel_sgns_stats nstats = {};
+    // the dense-count form (bpe_sgdense.hip.h): W and omega, allocated on the first dense call; partials, grow-only
+    int form = BPE_SGM_FORM_CSR, form_splits = 0;
+    float *d_W = nullptr;
+    void *d_ds = nullptr;
+    int64_t ds_cap = 0;
+    bpe_sgmodel_dense_stats dstats = {};
 };
 
 namespace {
@@ -641,18 +649,29 @@ int sgm_index(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const int6
     return BPE_OK;
 }
 
+// the dense-count form (bpe_sgdense.hip.h)
+bool sgd_wanted(const bpe_sgmodel *M, int64_t U);
+int sgd_run(bpe_sgmodel *M, bool sgns, const int32_t *d_t, const int32_t *d_c, const int64_t *d_k, int64_t U,
+            const int32_t *d_ids, const float *d_w, int S, double neg_k);
+
 // loss and gradients (into the model's gradient array) from device planes; *loss on the host
 int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const int64_t *d_k, int64_t U, double *loss) {
     M->stats.calls++;
+    M->dstats.calls++;
     if (U < 0 || (U && (!d_t || !d_c || !d_k))) return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram model planes");
     SGM_TRY(hipSetDevice(M->device));
     int64_t P = 0;
     if (int rc = sgm_index(M, d_t, d_c, d_k, U, &P, &M->stats.kernel_ms)) return rc;
     unsigned long long h[SGMH_WORDS];
+    const bool dense = P && sgd_wanted(M, U);
     SGM_TRY(hipEventRecord(M->ev0, M->stream));
     if (P == 0) {
         SGM_TRY(hipMemsetAsync(M->d_g, 0, (size_t)M->n4 * 16, M->stream));
+    } else if (dense) {
+        if (int rc = sgd_run(M, false, d_t, d_c, d_k, U, nullptr, nullptr, 0, 0.0)) return rc;
     } else {
+        M->dstats.last_form = BPE_SGM_FORM_CSR;
+        M->dstats.last_splits = 0;
         switch (M->EP) {
             case 64: sgm_launch<64>(M, d_c, d_k); break;
             case 128: sgm_launch<128>(M, d_c, d_k); break;
@@ -663,7 +682,10 @@ int sgm_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
     SGM_TRY(hipEventRecord(M->ev1, M->stream));
     SGM_TRY(hipMemcpyAsync(h, M->d_hdr, sizeof h, hipMemcpyDeviceToHost, M->stream));
     SGM_TRY(hipStreamSynchronize(M->stream));
-    if (int rc = sgm_time(M, &M->stats.kernel_ms)) return rc;
+    double ms = 0.0;
+    if (int rc = sgm_time(M, &ms)) return rc;
+    M->stats.kernel_ms += ms;
+    if (dense) M->dstats.kernel_ms += ms;
     double L = 0.0;
     std::memcpy(&L, &h[SGMH_LOSS], 8);
     if (loss) *loss = P ? L : 0.0;
@@ -759,6 +781,7 @@ int sgm_embed(bpe_sgmodel *M, const int32_t *d_ids, int64_t n, float *d_out) {
 
 #include "bpe_sgquery.hip.h"
 #include "bpe_sgns.hip.h"
+#include "bpe_sgdense.hip.h"
 
 extern "C" {
 
@@ -831,7 +854,7 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     if (M->stream) (void)hipStreamSynchronize(M->stream);
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
-                    M->d_io, M->d_qs, M->d_ns})
+                    M->d_io, M->d_qs, M->d_ns, (void *)M->d_W, M->d_ds})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);

@@ -477,6 +477,7 @@ int sgn_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
                 const int32_t *d_ids, const float *d_w, int64_t S, double neg_k, double *loss) {
     bpe_sgmodel_sgns_stats &st = M->nstats;
     st.calls++;
+    M->dstats.calls++;
     char msg[128];
     if (U < 0 || (U && (!d_t || !d_c || !d_k))) return bpe_fail(BPE_ERR_ARG, "bpe native: bad skip-gram model planes");
     if (S < 0 || S > M->V) {
@@ -511,6 +512,21 @@ int sgn_forward(bpe_sgmodel *M, const int32_t *d_t, const int32_t *d_c, const in
     const int V = M->V, E = M->E;
     const int Sn = neg_k > 0 ? (int)S : 0;   // (k = 0: the positive term alone)
     st.negatives += Sn;
+    if (sgd_wanted(M, U)) {   // the dense-count form (bpe_sgdense.hip.h): no transposed planes
+        SGM_TRY(hipEventRecord(M->ev0, M->stream));
+        if (int rc = sgd_run(M, true, d_t, d_c, d_k, U, d_ids, d_w, Sn, neg_k)) return rc;
+        SGM_TRY(hipEventRecord(M->ev1, M->stream));
+        SGM_TRY(hipMemcpyAsync(h, M->d_hdr, sizeof h, hipMemcpyDeviceToHost, M->stream));
+        SGM_TRY(hipStreamSynchronize(M->stream));
+        double ms = 0.0;
+        if (int rc = sgm_time(M, &ms)) return rc;
+        st.kernel_ms += ms;
+        M->dstats.kernel_ms += ms;
+        if (loss) std::memcpy(loss, &h[SGMH_LOSS], 8);
+        return BPE_OK;
+    }
+    M->dstats.last_form = BPE_SGM_FORM_CSR;
+    M->dstats.last_splits = 0;
     const int nb = (V + SGN_ROWS - 1) / SGN_ROWS;
     const int rpc = (V + SGN_MAX_CHUNKS - 1) / SGN_MAX_CHUNKS, n_chunks = (V + rpc - 1) / rpc;
     int splits = 1, bps = nb;

@@ -1325,6 +1325,46 @@ int bpe_sgmodel_sgns_adam_step_device(bpe_sgmodel *m, const int32_t *d_targets, 
 int bpe_sgmodel_get_sgns_stats(bpe_sgmodel *m, bpe_sgmodel_sgns_stats *out);
 int bpe_sgmodel_reset_sgns_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model, dense counts -------------------------------------------------------------------
+ * A second form of the count input to both training steps, chosen per model.  The rules, the inputs, the
+ * checks, the messages and the outputs of bpe_sgmodel_loss_grad / _adam_step and of the _sgns_ calls are
+ * those above, in the host and the `_device` forms alike; a failed call still computes and updates
+ * nothing.  Only the way G is formed and multiplied changes (csrc/bpe_sgdense.hip.h):
+ *   BPE_SGM_FORM_CSR    the default: the count planes walked as CSR entries, the kernels above, untouched;
+ *   BPE_SGM_FORM_DENSE  the checked planes scattered into W[Vp][Vp] = fl32(C[t,c] / P), fp32, Vp = V rounded
+ *                       up to 64, and G formed tile by tile as plain V x V x E products over W.  For a
+ *                       window co-occurrence matrix over a small vocabulary, where most cells are nonzero;
+ *   BPE_SGM_FORM_AUTO   dense when U >= BPE_SGM_DENSE_THETA * V^2, CSR otherwise (the measured crossover,
+ *                       DESIGN.md §3r).
+ * W is the model's, allocated on its first dense call (4 Vp^2 bytes: no more than the planes themselves
+ * from a density of 1/4 on), zeroed and refilled on every call; nothing of the caller's planes is
+ * remembered.  z and G are still never written.
+ *
+ * `splits` is how many ways the streamed axis of the tile loop is cut: 0 chooses from the shape and the
+ * device's compute units, as the queries do; 1..BPE_SGM_MAX_SPLITS forces that many, clamped to the number
+ * of BPE_SGM_TILE-wide tiles of V so that no split is without one (for the tests, which run both shapes of
+ * the reduction at small sizes).  An unknown form or splits outside [0, BPE_SGM_MAX_SPLITS] is BPE_ERR_ARG
+ * and changes nothing.
+ *
+ * Determinism: no floating-point atomics and every sum in a fixed order, so for a given form and split
+ * count a second call and the other route return the same bytes.  The bytes may differ between the forms,
+ * and between split counts (so, under splits == 0, between devices with different numbers of compute units). */
+#define BPE_SGM_FORM_CSR 0
+#define BPE_SGM_FORM_DENSE 1
+#define BPE_SGM_FORM_AUTO 2
+#define BPE_SGM_MAX_SPLITS 256
+#define BPE_SGM_DENSE_THETA 0.015625 /* 1/64: the smallest measured density at which dense won at both sizes, both rules */
+typedef struct {
+    int64_t calls;         /* training calls of either rule, in any form (failed ones too) */
+    int64_t dense_calls;   /* ... of which ran the dense kernels */
+    int64_t last_form;     /* what the last call that reached its kernels ran: BPE_SGM_FORM_CSR or _DENSE */
+    int64_t last_splits;   /* its splits (0 for BPE_SGM_FORM_CSR) */
+    double kernel_ms;      /* HIP-event time of the dense calls' kernels, from zeroing W to the last sum */
+} bpe_sgmodel_dense_stats;
+int bpe_sgmodel_set_counts_form(bpe_sgmodel *m, int form, int splits);
+int bpe_sgmodel_get_dense_stats(bpe_sgmodel *m, bpe_sgmodel_dense_stats *out);
+int bpe_sgmodel_reset_dense_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif

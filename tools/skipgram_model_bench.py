@@ -13,7 +13,10 @@ profiles/skipgram_model_bench.jsonl:
   - the dense torch step in the same run: C as a V x V fp32 matrix, `matmul`, `log_softmax`, autograd and
     torch.optim.Adam, timed by device events, and its loss beside the model's.
 
-Usage: tools/skipgram_model_bench.py [--texts 20000] [--reps 10] [--cells 2000000]
+--form csr | dense | auto is the model's count form (bpe_sgmodel_set_counts_form) and the records' `form`; the
+records of another form than csr are appended to profiles/skipgram_dense_bench.jsonl instead.
+
+Usage: tools/skipgram_model_bench.py [--texts 20000] [--reps 10] [--cells 2000000] [--form csr]
 """
 import argparse
 import importlib
@@ -46,12 +49,13 @@ def event_ms(fn, reps):
     return out
 
 
-def measure(name, V, E, planes, reps, dev):
+def measure(name, V, E, planes, reps, dev, form='csr'):
     t, c, k = planes
     rng = np.random.default_rng(3)
     a = float(np.sqrt(1.0 / E))
     par = [rng.uniform(-a, a, s).astype(np.float32) for s in ((V, E), (E,), (V, E), (V,))]
     m = pkg.SkipgramModel(0, V, E)
+    m.set_counts_form(form)
     m.set_params(*par)
     first = m.adam_step_tensors(t, c, k, **ADAM)   # warm-up
     k_ms, call_ms = [], []
@@ -86,7 +90,7 @@ def measure(name, V, E, planes, reps, dev):
         mm_ms = event_ms(lambda: torch.matmul(H, Eo.T), reps)
     flop = 2.0 * V * V * E
     return {'what': 'skip-gram model: one adam_step from device count planes, beside the dense torch step',
-            'workload': name, 'V': V, 'E': E, 'U': int(t.numel()), 'P': st['pairs'],
+            'workload': name, 'form': form, 'V': V, 'E': E, 'U': int(t.numel()), 'P': st['pairs'],
             'kernel_ms': round(min(k_ms), 3), 'kernel_ms_worst': round(max(k_ms), 3),
             'adam_step_call_ms': round(min(call_ms), 3), 'adam_step_call_ms_worst': round(max(call_ms), 3),
             'products_tflops_over_kernel_time': round(4 * flop / (min(k_ms) * 1e-3) / 1e12, 3),
@@ -103,8 +107,10 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--merges', type=int, default=100)
     ap.add_argument('--cells', type=int, default=2000000)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'skipgram_model_bench.jsonl'))
+    ap.add_argument('--form', choices=['csr', 'dense', 'auto'], default='csr')
+    ap.add_argument('--out')
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'skipgram_model_bench.jsonl' if a.form == 'csr' else 'skipgram_dense_bench.jsonl')
     if not torch.cuda.is_available():
         sys.exit('skipgram_model_bench needs a HIP device')
     dev = torch.device('cuda', 0)
@@ -127,16 +133,16 @@ def main():
     vec = np.ascontiguousarray((ids.astype(np.int64) * 197 + np.roll(ids, 1)) % V, np.int32)
     planes = enc.skipgram_counts_tensors(torch.from_numpy(vec).to(dev), torch.from_numpy(ioff).to(dev), 2, V)
     enc.close()
-    lines = [measure('bench_batch_counts', V, 50, planes, a.reps, dev)]
+    lines = [measure('bench_batch_counts', V, 50, planes, a.reps, dev, a.form)]
     print(json.dumps(lines[-1]), flush=True)
 
     V = pkg.SKIPGRAM_COUNTS_MAX_DIM
     keys = torch.unique(torch.randint(0, V * V, (a.cells,), device=dev, generator=torch.Generator(dev).manual_seed(9)))
     planes = ((keys // V).int(), (keys % V).int(), (keys * 2654435761 % 8 + 1))
-    lines.append(measure('synthetic_counts', V, 64, planes, a.reps, dev))
+    lines.append(measure('synthetic_counts', V, 64, planes, a.reps, dev, a.form))
     print(json.dumps(lines[-1]), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, 'w') as f:
+    with open(a.out, 'w' if a.form == 'csr' else 'a') as f:
         f.write('\n'.join(json.dumps(r) for r in lines) + '\n')
 
 

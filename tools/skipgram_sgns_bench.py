@@ -15,7 +15,10 @@ one JSON line, printed and written to profiles/skipgram_sgns_bench.jsonl:
     and torch.optim.Adam, timed by device events;
   - the first-step loss of the SGNS kernels and of torch.
 
-Usage: tools/skipgram_sgns_bench.py [--texts 20000] [--reps 10] [--cells 2000000] [--negatives 256 1024]
+--form csr | dense | auto is the model's count form (bpe_sgmodel_set_counts_form, both steps) and the records'
+`form`; the records of another form than csr are appended to profiles/skipgram_dense_bench.jsonl instead.
+
+Usage: tools/skipgram_sgns_bench.py [--texts 20000] [--reps 10] [--cells 2000000] [--negatives 256 1024] [--form csr]
 """
 import argparse
 import importlib
@@ -48,12 +51,13 @@ def timed_steps(step, stats, reset, reps):
     return first, per, call_ms
 
 
-def measure(name, V, E, planes, S, reps, dev):
+def measure(name, V, E, planes, S, reps, dev, form='csr'):
     t, c, k = planes
     rng = np.random.default_rng(3)
     a = float(np.sqrt(1.0 / E))
     par = [rng.uniform(-a, a, s).astype(np.float32) for s in ((V, E), (E,), (V, E), (V,))]
     m = pkg.SkipgramModel(0, V, E)
+    m.set_counts_form(form)
     q = m.noise(t.cpu().numpy(), c.cpu().numpy(), k.cpu().numpy())
     ids, w = m.sample_negatives(q, S, seed=11)
     d_ids, d_w = torch.from_numpy(ids).to(dev), torch.from_numpy(w).to(dev)
@@ -95,7 +99,7 @@ def measure(name, V, E, planes, S, reps, dev):
         if i:
             t_ms.append(e0.elapsed_time(e1))
     return {'what': 'skip-gram model: one sgns_adam_step from device count planes, beside adam_step and torch',
-            'workload': name, 'V': V, 'E': E, 'U': int(t.numel()), 'P': best['pairs'], 'draws': S,
+            'workload': name, 'form': form, 'V': V, 'E': E, 'U': int(t.numel()), 'P': best['pairs'], 'draws': S,
             'S': int(ids.size), 'neg_k': KAPPA,
             'kernel_ms': round(best['kernel_ms'], 3), 'kernel_ms_worst': round(max(s['kernel_ms'] for s in per), 3),
             'transpose_ms': round(best['transpose_ms'], 3), 'target_ms': round(best['target_ms'], 3),
@@ -117,8 +121,10 @@ def main():
     ap.add_argument('--merges', type=int, default=100)
     ap.add_argument('--cells', type=int, default=2000000)
     ap.add_argument('--negatives', type=int, nargs='+', default=[256, 1024])
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'skipgram_sgns_bench.jsonl'))
+    ap.add_argument('--form', choices=['csr', 'dense', 'auto'], default='csr')
+    ap.add_argument('--out')
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'skipgram_sgns_bench.jsonl' if a.form == 'csr' else 'skipgram_dense_bench.jsonl')
     if not torch.cuda.is_available():
         sys.exit('skipgram_sgns_bench needs a HIP device')
     dev = torch.device('cuda', 0)
@@ -145,10 +151,10 @@ def main():
     lines = []
     for name, V, E, planes in (('bench_batch_counts', V, 50, small), ('synthetic_counts', Vb, 64, big)):
         for S in a.negatives:
-            lines.append(measure(name, V, E, planes, S, a.reps, dev))
+            lines.append(measure(name, V, E, planes, S, a.reps, dev, a.form))
             print(json.dumps(lines[-1]), flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, 'w') as f:
+    with open(a.out, 'w' if a.form == 'csr' else 'a') as f:
         f.write('\n'.join(json.dumps(r) for r in lines) + '\n')
 
 
