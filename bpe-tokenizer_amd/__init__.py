@@ -83,6 +83,10 @@ C_API = [
     'bpe_sgmodel_sgns_loss_grad', 'bpe_sgmodel_sgns_loss_grad_device', 'bpe_sgmodel_sgns_adam_step',
     'bpe_sgmodel_sgns_adam_step_device', 'bpe_sgmodel_get_sgns_stats', 'bpe_sgmodel_reset_sgns_stats',
     'bpe_sgmodel_set_counts_form', 'bpe_sgmodel_get_dense_stats', 'bpe_sgmodel_reset_dense_stats',
+    'bpe_sgmodel_glove_loss_grad', 'bpe_sgmodel_glove_loss_grad_device', 'bpe_sgmodel_glove_adam_step',
+    'bpe_sgmodel_glove_adam_step_device', 'bpe_sgmodel_set_target_bias', 'bpe_sgmodel_set_target_bias_device',
+    'bpe_sgmodel_get_target_bias', 'bpe_sgmodel_get_target_bias_device', 'bpe_sgmodel_get_glove_stats',
+    'bpe_sgmodel_reset_glove_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -155,6 +159,7 @@ SGNS_ROWS = 32                   # BPE_SGNS_ROWS: rows a wave of the negative-sa
 SGM_FORM_CSR, SGM_FORM_DENSE, SGM_FORM_AUTO = 0, 1, 2   # BPE_SGM_FORM_*: how the training steps read the counts
 SGM_MAX_SPLITS = 256             # BPE_SGM_MAX_SPLITS: the most splits of the dense form's streamed axis
 SGM_DENSE_THETA = 1 / 64         # BPE_SGM_DENSE_THETA: 'auto' runs the dense form from this density U / dim^2 on
+GLOVE_RUN = 64                   # BPE_GLOVE_RUN: cells of a run, the unit of work of the GloVe kernels
 _SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
 _SGM_FORMS = {'csr': SGM_FORM_CSR, 'dense': SGM_FORM_DENSE, 'auto': SGM_FORM_AUTO}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
@@ -345,6 +350,16 @@ class SkipgramDenseStats(ctypes.Structure):
     """bpe_sgmodel_dense_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('dense_calls', ctypes.c_int64), ('last_form', ctypes.c_int64),
                 ('last_splits', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramGloveStats(ctypes.Structure):
+    """bpe_sgmodel_glove_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('elements', ctypes.c_int64), ('cells', ctypes.c_int64),
+                ('runs', ctypes.c_int64), ('carry_records', ctypes.c_int64), ('transpose_ms', ctypes.c_double),
+                ('target_ms', ctypes.c_double), ('context_ms', ctypes.c_double), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -618,6 +633,22 @@ def lib():
         'bpe_sgmodel_set_counts_form': ([vp, ctypes.c_int, ctypes.c_int], ctypes.c_int),
         'bpe_sgmodel_get_dense_stats': ([vp, ctypes.POINTER(SkipgramDenseStats)], ctypes.c_int),
         'bpe_sgmodel_reset_dense_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_glove_loss_grad': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                         ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_glove_loss_grad_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                                ctypes.POINTER(ctypes.c_double), vp, vp, vp, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_glove_adam_step': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'bpe_sgmodel_glove_adam_step_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        'bpe_sgmodel_set_target_bias': ([vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_set_target_bias_device': ([vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_get_target_bias': ([vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_get_target_bias_device': ([vp, vp, ctypes.c_int64], ctypes.c_int),
+        'bpe_sgmodel_get_glove_stats': ([vp, ctypes.POINTER(SkipgramGloveStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_glove_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -2825,6 +2856,81 @@ class SkipgramModel:
 
     def reset_dense_stats(self):
         _check(lib().bpe_sgmodel_reset_dense_stats(self._m), 'bpe_sgmodel_reset_dense_stats')
+
+    # ---- GloVe (include/bpe.h, "skip-gram model, GloVe"; csrc/bpe_glove.hip.h) ----
+    def set_target_bias(self, bt):
+        """Copies the target bias bt[dim] in (GloVe's fifth parameter array; zero at creation)."""
+        bt = np.ascontiguousarray(bt, dtype=np.float32).reshape(-1)
+        _check(lib().bpe_sgmodel_set_target_bias(self._m, bt.ctypes.data, bt.size), 'bpe_sgmodel_set_target_bias')
+
+    def get_target_bias(self):
+        """-> bt numpy float32 [dim]."""
+        bt = np.empty(self.dim, np.float32)
+        _check(lib().bpe_sgmodel_get_target_bias(self._m, bt.ctypes.data, bt.size), 'bpe_sgmodel_get_target_bias')
+        return bt
+
+    def set_target_bias_tensors(self, bt):
+        import torch
+        if bt.dtype != torch.float32 or not bt.is_cuda or bt.device.index != self.device or not bt.is_contiguous() or bt.dim() != 1:
+            raise BpeError('set_target_bias_tensors takes a contiguous float32 vector on the model\'s device', ERR_ARG)
+        torch.cuda.synchronize(bt.device)   # (the model runs on a stream of its own)
+        _check(lib().bpe_sgmodel_set_target_bias_device(self._m, bt.data_ptr(), bt.numel()), 'bpe_sgmodel_set_target_bias_device')
+
+    def get_target_bias_tensors(self):
+        import torch
+        bt = torch.empty(self.dim, dtype=torch.float32, device=torch.device('cuda', self.device))
+        torch.cuda.synchronize(bt.device)
+        _check(lib().bpe_sgmodel_get_target_bias_device(self._m, bt.data_ptr(), bt.numel()), 'bpe_sgmodel_get_target_bias_device')
+        return bt
+
+    def glove_loss_grad(self, targets, contexts, counts, x_max=100.0, alpha=0.75):
+        """-> (loss, dEin, db1, dEout, db2, dbt) of GloVe's weighted least squares on the cells of the count
+        planes, f = min(1, (C / x_max)^alpha) (bpe_sgmodel_glove_loss_grad)."""
+        t, c, k = self._planes(targets, contexts, counts)
+        g = [np.empty(s, np.float32) for s in self._shapes() + [(self.dim,)]]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_glove_loss_grad(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, float(x_max),
+                                                 float(alpha), ctypes.byref(loss), *[x.ctypes.data for x in g]),
+               'bpe_sgmodel_glove_loss_grad')
+        return (loss.value,) + tuple(g)
+
+    def glove_loss_grad_tensors(self, targets, contexts, counts, x_max=100.0, alpha=0.75):
+        """Device form (bpe_sgmodel_glove_loss_grad_device): planes as torch tensors on the model's device."""
+        import torch
+        args = self._planes_tensors('glove_loss_grad_tensors', targets, contexts, counts)
+        g = [torch.empty(s, dtype=torch.float32, device=targets.device) for s in self._shapes() + [(self.dim,)]]
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_glove_loss_grad_device(self._m, *args, float(x_max), float(alpha), ctypes.byref(loss),
+                                                        *[x.data_ptr() for x in g]), 'bpe_sgmodel_glove_loss_grad_device')
+        return (loss.value,) + tuple(g)
+
+    def glove_adam_step(self, targets, contexts, counts, x_max=100.0, alpha=0.75, lr=1e-3, beta1=0.9, beta2=0.999,
+                        eps=1e-8):
+        """One step of Adam on the GloVe gradients, the target bias included (bpe_sgmodel_glove_adam_step) -> the
+        loss before the update.  The step counter is that of adam_step."""
+        t, c, k = self._planes(targets, contexts, counts)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_glove_adam_step(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, float(x_max),
+                                                 float(alpha), lr, beta1, beta2, eps, ctypes.byref(loss)),
+               'bpe_sgmodel_glove_adam_step')
+        return loss.value
+
+    def glove_adam_step_tensors(self, targets, contexts, counts, x_max=100.0, alpha=0.75, lr=1e-3, beta1=0.9, beta2=0.999,
+                                eps=1e-8):
+        """Device form (bpe_sgmodel_glove_adam_step_device)."""
+        args = self._planes_tensors('glove_adam_step_tensors', targets, contexts, counts)
+        loss = ctypes.c_double()
+        _check(lib().bpe_sgmodel_glove_adam_step_device(self._m, *args, float(x_max), float(alpha), lr, beta1, beta2, eps,
+                                                        ctypes.byref(loss)), 'bpe_sgmodel_glove_adam_step_device')
+        return loss.value
+
+    def glove_stats(self):
+        s = SkipgramGloveStats()
+        _check(lib().bpe_sgmodel_get_glove_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_glove_stats')
+        return s.as_dict()
+
+    def reset_glove_stats(self):
+        _check(lib().bpe_sgmodel_reset_glove_stats(self._m), 'bpe_sgmodel_reset_glove_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

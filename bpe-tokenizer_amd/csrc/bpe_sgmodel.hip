@@ -557,6 +557,13 @@ struct bpe_sgmodel {
     void *d_ds = nullptr;
     int64_t ds_cap = 0;
     bpe_sgmodel_dense_stats dstats = {};
+    // GloVe (bpe_glove.hip.h): the target bias bt[V] with its gradient and Adam moments (bt4 float4s each), in
+    // buffers of their own beside the flat array; the call's scratch, grow-only
+    int64_t bt4 = 0;
+    float *d_bt = nullptr, *d_gbt = nullptr, *d_mbt = nullptr, *d_vbt = nullptr;
+    void *d_gs = nullptr;
+    int64_t gs_cap = 0;
+    bpe_sgmodel_glove_stats gstats = {};
 };
 
 namespace {
@@ -814,6 +821,7 @@ int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
     M->o_b2 = 2 * VE + embed;
     M->n_params = 2 * VE + embed + dim;
     M->n4 = (M->n_params + 3) / 4;
+    M->bt4 = ((int64_t)dim + 3) / 4;
     auto bail = [&](int rc) {
         bpe_sgmodel_destroy(M);
         return rc;
@@ -828,6 +836,9 @@ int bpe_sgmodel_create(int device, int dim, int embed, bpe_sgmodel **out) {
     bool ok = true;
     for (float **p : {&M->d_p, &M->d_g, &M->d_m, &M->d_v})
         ok = ok && hipMalloc((void **)p, flat) == hipSuccess && hipMemset(*p, 0, flat) == hipSuccess;
+    for (float **p : {&M->d_bt, &M->d_gbt, &M->d_mbt, &M->d_vbt})
+        ok = ok && hipMalloc((void **)p, (size_t)M->bt4 * 16) == hipSuccess &&
+             hipMemset(*p, 0, (size_t)M->bt4 * 16) == hipSuccess;
     ok = ok && hipMalloc((void **)&M->d_rowptr, (size_t)(dim + 1) * 8) == hipSuccess &&
          hipMalloc((void **)&M->d_nt, (size_t)dim * 8) == hipSuccess &&
          hipMalloc((void **)&M->d_lse, (size_t)dim * 4) == hipSuccess &&
@@ -854,7 +865,8 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     if (M->stream) (void)hipStreamSynchronize(M->stream);
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
-                    M->d_io, M->d_qs, M->d_ns, (void *)M->d_W, M->d_ds})
+                    M->d_io, M->d_qs, M->d_ns, (void *)M->d_W, M->d_ds, (void *)M->d_bt, (void *)M->d_gbt,
+                    (void *)M->d_mbt, (void *)M->d_vbt, M->d_gs})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
@@ -930,6 +942,8 @@ int bpe_sgmodel_reset_optimizer(bpe_sgmodel *M) {
     SGM_TRY(hipSetDevice(M->device));
     SGM_TRY(hipMemsetAsync(M->d_m, 0, (size_t)M->n4 * 16, M->stream));
     SGM_TRY(hipMemsetAsync(M->d_v, 0, (size_t)M->n4 * 16, M->stream));
+    SGM_TRY(hipMemsetAsync(M->d_mbt, 0, (size_t)M->bt4 * 16, M->stream));
+    SGM_TRY(hipMemsetAsync(M->d_vbt, 0, (size_t)M->bt4 * 16, M->stream));
     SGM_TRY(hipStreamSynchronize(M->stream));
     M->step = 0;
     return BPE_OK;
@@ -970,3 +984,5 @@ int bpe_sgmodel_reset_stats(bpe_sgmodel *M) {
 }
 
 }  // extern "C"
+
+#include "bpe_glove.hip.h"

@@ -1365,6 +1365,64 @@ int bpe_sgmodel_set_counts_form(bpe_sgmodel *m, int form, int splits);
 int bpe_sgmodel_get_dense_stats(bpe_sgmodel *m, bpe_sgmodel_dense_stats *out);
 int bpe_sgmodel_reset_dense_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model, GloVe ---------------------------------------------------------------------------
+ * The same parameters, embed and queries trained with GloVe's weighted least squares on the log counts
+ * (Pennington, Socher & Manning 2014): the only objective whose work is exactly the nonzero cells, with
+ * no V x V softmax and no V x S negative block (csrc/bpe_glove.hip.h).  Planes, checks and messages as
+ * above.  The model has one more parameter array for it, the target bias bt[V], fp32, zero at creation,
+ * with Adam moments of its own beside the flat array; no other call reads or writes it, except that
+ * bpe_sgmodel_reset_optimizer zeroes its moments too.  x_max is finite and > 0 (GloVe's 100), alpha
+ * finite and >= 0 (GloVe's 0.75).  The cells are the elements with C > 0, N of them:
+ *   z(t,c) = H_t . Eout[c] + b2[c] + bt[t],  l(t,c) = fl32(log C[t,c]),  f(t,c) = fl32(min(1, (C/x_max)^alpha)),
+ *   r = z - l,  loss = (1/(2N)) sum f r^2,  G[t,c] = (1/N) f r on the cells and 0 elsewhere,
+ *   dEin = G Eout, db1 = its column sums, dbt[t] = sum_c G[t,c], dEout = G^T H, db2[c] = sum_t G[t,c].
+ * l and f are taken in double from the int64 count; z, r and G are fp32; a run's loss terms add in fp32
+ * within one group of at most four cells and in double from there on.  Everything is 0 when N == 0.
+ * Elements with C == 0 contribute nothing, not a bit: the kernels run over the cells alone.  No
+ * floating-point atomics and every sum in a fixed order: the same bytes on every run and in both forms.
+ * The kernels cut the cells into runs of BPE_GLOVE_RUN (exported for the tests).
+ *
+ * bpe_sgmodel_set_counts_form does not apply: these calls always read the planes as entries, and they
+ * do not touch the dense statistics.
+ *
+ * Errors are BPE_ERR_ARG, nothing is computed and neither the parameters nor the optimizer change: the
+ * plane messages above, `skip-gram model x_max X is not positive or not finite`, `skip-gram model alpha
+ * A is negative or not finite`, and from the target-bias calls `skip-gram model target bias of D given
+ * to a model of V`.
+ *
+ * bpe_sgmodel_glove_adam_step takes the Adam step of bpe_sgmodel_adam_step over all five arrays, with the
+ * model's one step counter and the same bias corrections.  NULL outputs are skipped. */
+#define BPE_GLOVE_RUN 64
+typedef struct {
+    int64_t calls;           /* glove_loss_grad and glove_adam_step calls (failed ones too) */
+    int64_t elements;        /* U of the calls that passed their checks */
+    int64_t cells;           /* ... their N */
+    int64_t runs;            /* ... the runs their cells were cut into */
+    int64_t carry_records;   /* ... the carry records of both walks (two per run and side) */
+    double transpose_ms;     /* HIP-event time of: counting the cells, the transposed planes */
+    double target_ms;        /* ... dEin, db1, dbt and the loss */
+    double context_ms;       /* ... dEout and db2 */
+    double kernel_ms;        /* ... all kernels, Adam included */
+} bpe_sgmodel_glove_stats;
+int bpe_sgmodel_glove_loss_grad(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                                int64_t U, double x_max, double alpha, double *loss, float *dEin, float *db1,
+                                float *dEout, float *db2, float *dbt);
+int bpe_sgmodel_glove_loss_grad_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                       const int64_t *d_counts, int64_t U, double x_max, double alpha, double *loss,
+                                       float *d_dEin, float *d_db1, float *d_dEout, float *d_db2, float *d_dbt);
+int bpe_sgmodel_glove_adam_step(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                                int64_t U, double x_max, double alpha, double lr, double beta1, double beta2, double eps,
+                                double *loss);
+int bpe_sgmodel_glove_adam_step_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                       const int64_t *d_counts, int64_t U, double x_max, double alpha, double lr,
+                                       double beta1, double beta2, double eps, double *loss);
+int bpe_sgmodel_set_target_bias(bpe_sgmodel *m, const float *bt, int64_t dim);
+int bpe_sgmodel_set_target_bias_device(bpe_sgmodel *m, const float *d_bt, int64_t dim);
+int bpe_sgmodel_get_target_bias(bpe_sgmodel *m, float *bt, int64_t dim);
+int bpe_sgmodel_get_target_bias_device(bpe_sgmodel *m, float *d_bt, int64_t dim);
+int bpe_sgmodel_get_glove_stats(bpe_sgmodel *m, bpe_sgmodel_glove_stats *out);
+int bpe_sgmodel_reset_glove_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
