@@ -87,6 +87,8 @@ C_API = [
     'bpe_sgmodel_glove_adam_step_device', 'bpe_sgmodel_set_target_bias', 'bpe_sgmodel_set_target_bias_device',
     'bpe_sgmodel_get_target_bias', 'bpe_sgmodel_get_target_bias_device', 'bpe_sgmodel_get_glove_stats',
     'bpe_sgmodel_reset_glove_stats',
+    'bpe_encode_dropout_batch', 'bpe_encode_dropout_text_batch', 'bpe_encode_dropout_text_batch_device',
+    'bpe_encoder_get_dropout_stats', 'bpe_encoder_reset_dropout_stats',
 ]
 HOT_BINS = 65536
 # bpe_debug_global (include/bpe_tools.h): the info words in order (BPE_GLOBAL_INFO_*)
@@ -299,6 +301,16 @@ class LinesStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DropoutStats(ctypes.Structure):
+    """bpe_dropout_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('samples', ctypes.c_int64),
+                ('tokens_in', ctypes.c_int64), ('tokens_out', ctypes.c_int64), ('steps', ctypes.c_int64),
+                ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SkipgramStats(ctypes.Structure):
     """bpe_skipgram_stats (include/bpe.h)."""
     _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values_in', ctypes.c_int64),
@@ -454,6 +466,15 @@ def lib():
         'bpe_encoder_set_long_texts': ([vp, ctypes.c_int], ctypes.c_int),
         'bpe_encoder_get_split_stats': ([vp, ctypes.POINTER(SplitStats)], ctypes.c_int),
         'bpe_encoder_reset_split_stats': ([vp], ctypes.c_int),
+        'bpe_encode_dropout_batch': ([vp, i32p, i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_uint64,
+                                      ctypes.c_int64, i32p, i64p], ctypes.c_int),
+        'bpe_encode_dropout_text_batch': ([vp, ctypes.c_int, vp, i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                           ctypes.c_uint64, ctypes.c_int64, vp, ctypes.c_int64, i64p], ctypes.c_int),
+        'bpe_encode_dropout_text_batch_device': ([vp, ctypes.c_int, vp, vp, ctypes.c_int64, ctypes.c_int32,
+                                                  ctypes.c_double, ctypes.c_uint64, ctypes.c_int64, vp, ctypes.c_int64,
+                                                  vp, i64p], ctypes.c_int),
+        'bpe_encoder_get_dropout_stats': ([vp, ctypes.POINTER(DropoutStats)], ctypes.c_int),
+        'bpe_encoder_reset_dropout_stats': ([vp], ctypes.c_int),
         'bpe_decoder_create': ([ctypes.POINTER(vp), ctypes.c_int], ctypes.c_int),
         'bpe_decoder_destroy': ([vp], ctypes.c_int),
         'bpe_decoder_clear': ([vp], ctypes.c_int),
@@ -1764,6 +1785,102 @@ class Encoder:
 
     def reset_text_stats(self):
         _check(lib().bpe_encoder_reset_text_stats(self._enc), 'bpe_encoder_reset_text_stats')
+
+    # encoding with dropout (include/bpe.h "encoding with dropout"): `samples` segmentations per text ----
+    @staticmethod
+    def _dropout_args(p, samples, seed, text_base):
+        return int(samples), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(text_base)
+
+    @staticmethod
+    def _per_text(out, oo, n, samples):
+        return [[out[oo[k * samples + s]:oo[k * samples + s + 1]].copy() for s in range(samples)] for k in range(n)]
+
+    def encode_dropout_flat(self, ids, off, p, samples=1, seed=0, text_base=0):
+        """Flat form: texts ids[off[k]:off[k+1]] -> (ids_out, out_off); result k * samples + s is
+        sample s of text k, text k being text text_base + k of the data set."""
+        ids = _i32(ids)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        total = int(off[-1] - off[0]) if n > 0 else 0
+        out = np.zeros(max(total * max(int(samples), 1), 1), dtype=np.int32)
+        out_off = np.zeros(max(n * max(int(samples), 1) + 1, 1), dtype=np.int64)
+        src = ids if ids.size else np.zeros(1, np.int32)
+        i32p, i64p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
+        _check(lib().bpe_encode_dropout_batch(self._enc, src.ctypes.data_as(i32p), off.ctypes.data_as(i64p), n,
+                                              *self._dropout_args(p, samples, seed, text_base),
+                                              out.ctypes.data_as(i32p), out_off.ctypes.data_as(i64p)),
+               'bpe_encode_dropout_batch')
+        return out[:out_off[-1]], out_off
+
+    def encode_dropout(self, texts, p, samples=1, seed=0, text_base=0):
+        """texts: a list of id sequences -> per text, a list of `samples` encoded int32 arrays."""
+        off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in texts], out=off[1:])
+        ids = np.concatenate([np.asarray(t, dtype=np.int32) for t in texts]) if texts and off[-1] \
+            else np.zeros(0, np.int32)
+        out, oo = self.encode_dropout_flat(ids, off, p, samples, seed, text_base)
+        return self._per_text(out, oo, len(texts), int(samples))
+
+    def encode_text_dropout_flat(self, units, off, p, samples=1, seed=0, text_base=0, kind='vectors'):
+        """Flat form: texts units[off[k]:off[k+1]] (UTF-16 units) -> (values int32, out_off int64)."""
+        kind = self._KINDS[kind]
+        units = np.ascontiguousarray(units, dtype=np.uint16).ravel()
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        total = max(int(off[-1] - off[0]), 0) if n > 0 else 0
+        out = np.zeros(max(total * max(int(samples), 1), 1), dtype=np.int32)
+        out_off = np.zeros(max(n * max(int(samples), 1) + 1, 1), dtype=np.int64)
+        src = units if units.size else np.zeros(1, np.uint16)
+        _check(lib().bpe_encode_dropout_text_batch(self._enc, kind, src.ctypes.data,
+                                                   off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n,
+                                                   *self._dropout_args(p, samples, seed, text_base),
+                                                   out.ctypes.data, out.size,
+                                                   out_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
+               'bpe_encode_dropout_text_batch')
+        return out[:out_off[-1]], out_off
+
+    def encode_text_dropout(self, texts, p, samples=1, seed=0, text_base=0, kind='vectors'):
+        """texts: a list of str -> per text, a list of `samples` int32 arrays of vector indices (or
+        token ids, kind='ids')."""
+        parts = [_units(t) for t in texts]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in parts], out=off[1:])
+        units = np.concatenate(parts).astype(np.uint16) if parts and off[-1] else np.zeros(0, np.uint16)
+        out, oo = self.encode_text_dropout_flat(units, off, p, samples, seed, text_base, kind)
+        return self._per_text(out, oo, len(parts), int(samples))
+
+    def encode_text_dropout_tensors(self, units, off, p, samples=1, seed=0, text_base=0, kind='vectors'):
+        """Device form (bpe_encode_dropout_text_batch_device): units a torch int16 or uint16 tensor and
+        off a torch int64 tensor on the encoder's device -> (int32 tensor of the values, int64 tensor of
+        n_texts * samples + 1 offsets), both on that device."""
+        import torch
+        kind = self._KINDS[kind]
+        if units.dtype not in (torch.int16, getattr(torch, 'uint16', torch.int16)) or off.dtype != torch.int64:
+            raise BpeError('encode_text_dropout_tensors takes int16 or uint16 units and int64 offsets', ERR_ARG)
+        if not (units.is_cuda and off.is_cuda and units.device.index == self.device
+                and off.device.index == self.device):
+            raise BpeError('encode_text_dropout_tensors takes tensors on the encoder\'s device', ERR_ARG)
+        units, off = units.contiguous(), off.contiguous()
+        n, s_ = off.numel() - 1, max(int(samples), 1)
+        vals = torch.empty(max(units.numel() * s_, 1), dtype=torch.int32, device=units.device)
+        out_off = torch.zeros(n * s_ + 1, dtype=torch.int64, device=units.device)
+        torch.cuda.synchronize(units.device)   # (the encoder runs on a stream of its own)
+        need = ctypes.c_int64()
+        up = units.data_ptr() if units.numel() else None
+        _check(lib().bpe_encode_dropout_text_batch_device(self._enc, kind, up, off.data_ptr(), n,
+                                                          *self._dropout_args(p, samples, seed, text_base),
+                                                          vals.data_ptr(), vals.numel(), out_off.data_ptr(),
+                                                          ctypes.byref(need)),
+               'bpe_encode_dropout_text_batch_device')
+        return vals[:need.value], out_off
+
+    def dropout_stats(self):
+        s = DropoutStats()
+        _check(lib().bpe_encoder_get_dropout_stats(self._enc, ctypes.byref(s)), 'bpe_encoder_get_dropout_stats')
+        return s.as_dict()
+
+    def reset_dropout_stats(self):
+        _check(lib().bpe_encoder_reset_dropout_stats(self._enc), 'bpe_encoder_reset_dropout_stats')
 
 
     # text as UTF-8 (include/bpe.h "text as UTF-8"): bytes in, transcoded on the device -----------------

@@ -485,6 +485,7 @@ struct bpe_encoder {
     hipEvent_t g_in[2] = {nullptr, nullptr}, g_k0[2] = {nullptr, nullptr}, g_k1[2] = {nullptr, nullptr};
     std::vector<int32_t> abc;                 // the merges, in rank order
     bool greedy_ok = true;                    // the rank-greedy form equals the replay (above)
+    bool pair_twice = false;                  // a pair stands in the list twice (no dropout form: bpe_dropout.hip.h)
     std::vector<uint8_t> is_input;            // ids used as a or b by the merges so far
     int32_t vocab = 0;                        // 1 + the largest id of the merges
     // rank table (host copy; uploaded when dirty)
@@ -530,6 +531,9 @@ struct bpe_encoder {
     size_t d_win_n = 0, d_cut_n = 0;
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;
     bpe_split_stats sst{};
+    // encoding with dropout (bpe_dropout.hip.h): its step counter (made by the first such call) and numbers
+    unsigned long long *d_drop_steps = nullptr;
+    bpe_dropout_stats dst{};
 };
 
 namespace {
@@ -543,8 +547,10 @@ void table_insert(bpe_encoder *E, uint32_t key, uint32_t rank) {
             s = ((unsigned long long)key << 32) | (rank << 16) | E->c_of[rank];
             return;
         }
-        if ((uint32_t)(s >> 32) == key) return;   // a repeated pair: its first rank wins (the
-                                                  // later replaceAll finds nothing left)
+        if ((uint32_t)(s >> 32) == key) {   // a repeated pair: its first rank wins (the later
+            E->pair_twice = true;           // replaceAll finds nothing left)
+            return;
+        }
         h = (h + 1) & mask;
     }
 }
@@ -1660,6 +1666,8 @@ int text_run(bpe_encoder *E, int kind, const uint16_t *units, const int64_t *off
 
 }  // namespace
 
+#include "bpe_dropout.hip.h"   // encoding with dropout: k_encode_drop and its routes (bpe_encode_dropout_batch)
+
 int encoder_device(bpe_encoder *E, int *device) {
     if (!E || !device) return bpe_fail(BPE_ERR_ARG, "bpe native: null encoder");
     *device = E->device;
@@ -1773,6 +1781,7 @@ int bpe_encoder_destroy(bpe_encoder *E) {
     if (E->d_slots) (void)hipFree(E->d_slots);
     if (E->d_limg) (void)hipFree(E->d_limg);
     if (E->d_steps) (void)hipFree(E->d_steps);
+    if (E->d_drop_steps) (void)hipFree(E->d_drop_steps);
     if (E->d_ends) (void)hipFree(E->d_ends);
     if (E->d_cut_slots) (void)hipFree(E->d_cut_slots);
     if (E->d_win) (void)hipFree(E->d_win);
@@ -1809,6 +1818,7 @@ int bpe_encoder_clear(bpe_encoder *E) {
     E->cut_slots.clear();
     E->split_ok = true;
     E->greedy_ok = true;
+    E->pair_twice = false;
     E->vocab = 0;
     table_rebuild(E, 10);
     E->dirty = true;

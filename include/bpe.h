@@ -508,6 +508,58 @@ int bpe_encode_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_u
 int bpe_encoder_get_text_stats(bpe_encoder *enc, bpe_text_stats *out);
 int bpe_encoder_reset_text_stats(bpe_encoder *enc);
 
+/* ---- encoding with dropout ---------------------------------------------------------------------
+ * BPE-dropout (Provilkov et al. 2020): `samples` sampled segmentations of every text of a batch, on
+ * the device (csrc/bpe_dropout.hip.h; the arithmetic is csrc/bpe_dropout_rule.h, mod 2^64):
+ *   mix64(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   stream(seed, t, s, S) = mix64(seed + 0x9E3779B97F4A7C15 * (t * S + s + 1))
+ *   coin(stream, i, r)    = mix64(stream ^ ((i << 16) | r)) >> 32
+ *   dropped(stream, i, r) = coin(stream, i, r) < thr,     thr = (uint64_t)(p * 4294967296.0)
+ * with t = text_base + k the text's global index (a data set cut into calls gets the segmentations
+ * of a single call), s the sample, r the merge's rank in the list and i the position in the text,
+ * before any merge, of the first input token of the site's left token.  A text is encoded as
+ * encodeToCode does (core.ts:404-406) with one change: for every merge r in list order the text is
+ * scanned left to right; at q, if (tok[q], tok[q + 1]) == (a_r, b_r) and the site is not dropped,
+ * the two become c_r (which starts where a_r did) and the scan goes on behind it; otherwise it goes
+ * on at q + 1.  p = 0 gives bpe_encode_batch's output `samples` times, p = 1 the input.
+ *
+ * Result k * samples + s is sample s of text k: the calls write the results back to back and
+ * n_texts * samples + 1 offsets (the first 0); samples * (off[n_texts] - off[0]) values always
+ * suffice.  samples < 1, text_base < 0, or p outside [0, 1] or NaN give BPE_ERR_ARG.
+ * The text forms take bpe_encode_text_batch's arguments, run its front end and make its checks,
+ * with its messages in its order (places relative to the text; a hole's position is the one in its
+ * sample).  There is no UTF-8 form of its own: bpe_encoder_utf8_to_utf16_device in front of
+ * bpe_encode_dropout_text_batch_device covers it.
+ * Texts of up to BPE_ENCODE_LDS_TOKENS tokens go to the kernel; longer ones under BPE_LONG_SPLIT are
+ * cut as bpe_encode_batch cuts them (a boundary no merge can cross stays uncrossable when merges
+ * are dropped) and i stays relative to the text.  What has no dropout form fails the whole call
+ * with BPE_ERR_STATE, nothing written, and the message
+ *   bpe native: no dropout form for text K: REASON
+ * for the first such text: a long text on the replay route, a long text with no safe boundary
+ * within BPE_ENCODE_LDS_TOKENS tokens, and every text (K = 0) under a merge list the rank-greedy
+ * form cannot take or one that holds a pair twice (its second rank would have a coin of its own). */
+typedef struct {
+    int64_t calls;            /* dropout calls */
+    int64_t texts;            /* texts of the calls that succeeded */
+    int64_t samples;          /* ... their results (texts x samples) */
+    int64_t tokens_in;        /* ... their ids in (once per text) */
+    int64_t tokens_out;       /* ... their ids out (all samples) */
+    int64_t steps;            /* greedy steps of the dropout kernel, all results */
+    double kernel_ms;         /* HIP-event time of the dropout kernel (per call: launch to end) */
+} bpe_dropout_stats;
+int bpe_encode_dropout_batch(bpe_encoder *enc, const int32_t *ids, const int64_t *off, int64_t n_texts,
+                             int32_t samples, double p, uint64_t seed, int64_t text_base, int32_t *ids_out,
+                             int64_t *out_off);
+int bpe_encode_dropout_text_batch(bpe_encoder *enc, int kind, const uint16_t *units, const int64_t *off,
+                                  int64_t n_texts, int32_t samples, double p, uint64_t seed, int64_t text_base,
+                                  int32_t *vals_out, int64_t vals_cap, int64_t *out_off);
+int bpe_encode_dropout_text_batch_device(bpe_encoder *enc, int kind, const uint16_t *d_units, const int64_t *d_off,
+                                         int64_t n_texts, int32_t samples, double p, uint64_t seed,
+                                         int64_t text_base, int32_t *d_vals_out, int64_t vals_cap,
+                                         int64_t *d_out_off, int64_t *needed);
+int bpe_encoder_get_dropout_stats(bpe_encoder *enc, bpe_dropout_stats *out);
+int bpe_encoder_reset_dropout_stats(bpe_encoder *enc);
+
 /* ---- corpus from text --------------------------------------------------------------------------
  * addToCorpus (core.ts:182-207) for a batch of UTF-16 texts, on the device: the call leaves the
  * context exactly as `for (t of texts) addToCorpus(t)` would.  Chars follow bpe_encode_text_batch's
