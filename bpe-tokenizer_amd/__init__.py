@@ -87,6 +87,8 @@ C_API = [
     'bpe_sgmodel_glove_adam_step_device', 'bpe_sgmodel_set_target_bias', 'bpe_sgmodel_set_target_bias_device',
     'bpe_sgmodel_get_target_bias', 'bpe_sgmodel_get_target_bias_device', 'bpe_sgmodel_get_glove_stats',
     'bpe_sgmodel_reset_glove_stats',
+    'bpe_sgmodel_ppmi', 'bpe_sgmodel_ppmi_device', 'bpe_sgmodel_ppmi_svd', 'bpe_sgmodel_ppmi_svd_device',
+    'bpe_sgmodel_get_svd_stats', 'bpe_sgmodel_reset_svd_stats',
     'bpe_encode_dropout_batch', 'bpe_encode_dropout_text_batch', 'bpe_encode_dropout_text_batch_device',
     'bpe_encoder_get_dropout_stats', 'bpe_encoder_reset_dropout_stats',
 ]
@@ -162,6 +164,7 @@ SGM_FORM_CSR, SGM_FORM_DENSE, SGM_FORM_AUTO = 0, 1, 2   # BPE_SGM_FORM_*: how th
 SGM_MAX_SPLITS = 256             # BPE_SGM_MAX_SPLITS: the most splits of the dense form's streamed axis
 SGM_DENSE_THETA = 1 / 64         # BPE_SGM_DENSE_THETA: 'auto' runs the dense form from this density U / dim^2 on
 GLOVE_RUN = 64                   # BPE_GLOVE_RUN: cells of a run, the unit of work of the GloVe kernels
+SVD_MAX_L = 128                  # BPE_SVD_MAX_L: the widest subspace of ppmi_svd (embed + oversample, in sixteens)
 _SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
 _SGM_FORMS = {'csr': SGM_FORM_CSR, 'dense': SGM_FORM_DENSE, 'auto': SGM_FORM_AUTO}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
@@ -375,6 +378,25 @@ class SkipgramGloveStats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramSvdStats(ctypes.Structure):
+    """bpe_sgmodel_svd_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('cells', ctypes.c_int64), ('positive_cells', ctypes.c_int64),
+                ('L', ctypes.c_int64), ('dropped_columns', ctypes.c_int64), ('sweeps', ctypes.c_int64),
+                ('prep_ms', ctypes.c_double), ('spmm_ms', ctypes.c_double), ('gram_ms', ctypes.c_double),
+                ('chol_ms', ctypes.c_double), ('apply_ms', ctypes.c_double), ('eig_ms', ctypes.c_double),
+                ('finish_ms', ctypes.c_double), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramSvdOpts(ctypes.Structure):
+    """bpe_sgmodel_svd_opts (include/bpe.h)."""
+    _fields_ = [('shift', ctypes.c_double), ('cds', ctypes.c_double), ('gamma', ctypes.c_double),
+                ('oversample', ctypes.c_int32), ('power_iters', ctypes.c_int32), ('seed', ctypes.c_uint64),
+                ('omega', ctypes.c_void_p)]
 
 
 def build(force=False):
@@ -670,6 +692,13 @@ def lib():
         'bpe_sgmodel_get_target_bias_device': ([vp, vp, ctypes.c_int64], ctypes.c_int),
         'bpe_sgmodel_get_glove_stats': ([vp, ctypes.POINTER(SkipgramGloveStats)], ctypes.c_int),
         'bpe_sgmodel_reset_glove_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_ppmi': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double, vp], ctypes.c_int),
+        'bpe_sgmodel_ppmi_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.c_double, ctypes.c_double, vp], ctypes.c_int),
+        'bpe_sgmodel_ppmi_svd': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(SkipgramSvdOpts), vp], ctypes.c_int),
+        'bpe_sgmodel_ppmi_svd_device': ([vp, vp, vp, vp, ctypes.c_int64, ctypes.POINTER(SkipgramSvdOpts), vp],
+                                        ctypes.c_int),
+        'bpe_sgmodel_get_svd_stats': ([vp, ctypes.POINTER(SkipgramSvdStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_svd_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -3048,6 +3077,75 @@ class SkipgramModel:
 
     def reset_glove_stats(self):
         _check(lib().bpe_sgmodel_reset_glove_stats(self._m), 'bpe_sgmodel_reset_glove_stats')
+
+    # ---- PPMI and SVD (include/bpe.h, "skip-gram model, PPMI and SVD"; csrc/bpe_svd.hip.h) ----
+    def ppmi(self, targets, contexts, counts, shift=1.0, cds=1.0):
+        """-> float32 [len(counts)]: max(0, log C - log r_t - cds log k_c + log Z - log shift) of every element
+        of the planes, 0 where the count is 0 (bpe_sgmodel_ppmi).  The model does not change."""
+        t, c, k = self._planes(targets, contexts, counts)
+        out = np.empty(t.size, np.float32)
+        _check(lib().bpe_sgmodel_ppmi(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, float(shift),
+                                      float(cds), out.ctypes.data), 'bpe_sgmodel_ppmi')
+        return out
+
+    def ppmi_tensors(self, targets, contexts, counts, shift=1.0, cds=1.0):
+        """Device form (bpe_sgmodel_ppmi_device): planes as torch tensors on the model's device -> a tensor there."""
+        import torch
+        args = self._planes_tensors('ppmi_tensors', targets, contexts, counts)
+        out = torch.empty(args[3], dtype=torch.float32, device=targets.device)
+        _check(lib().bpe_sgmodel_ppmi_device(self._m, *args, float(shift), float(cds), out.data_ptr() if args[3] else None),
+               'bpe_sgmodel_ppmi_device')
+        return out
+
+    def _svd_opts(self, shift, cds, gamma, oversample, power_iters, seed, omega_ptr):
+        return SkipgramSvdOpts(float(shift), float(cds), float(gamma), int(oversample), int(power_iters),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, omega_ptr)
+
+    def _svd_omega_shape(self, shape, oversample):
+        L = (self.width + max(int(oversample), 0) + 15) // 16 * 16
+        if tuple(shape) != (self.dim, L):
+            raise BpeError('skip-gram model omega of shape %s is not (dim, L) = (%d, %d)' % (tuple(shape), self.dim, L),
+                           ERR_ARG)
+
+    def ppmi_svd(self, targets, contexts, counts, shift=1.0, cds=1.0, gamma=0.5, oversample=16, power_iters=4, seed=0,
+                 omega=None):
+        """The truncated SVD of the planes' PPMI matrix into the parameters: Ein = U Sigma^gamma, Eout = V
+        Sigma^(1 - gamma), b1 = b2 = 0, the optimizer reset (bpe_sgmodel_ppmi_svd) -> sigma, float64 [embed].
+        `omega`, float32 [dim][L] with L = embed + oversample rounded up to a multiple of 16, replaces the seeded
+        start matrix."""
+        t, c, k = self._planes(targets, contexts, counts)
+        if omega is not None:
+            omega = np.ascontiguousarray(omega, dtype=np.float32)
+            self._svd_omega_shape(omega.shape, oversample)
+        o = self._svd_opts(shift, cds, gamma, oversample, power_iters, seed, None if omega is None else omega.ctypes.data)
+        sigma = np.zeros(self.width, np.float64)
+        _check(lib().bpe_sgmodel_ppmi_svd(self._m, t.ctypes.data, c.ctypes.data, k.ctypes.data, t.size, ctypes.byref(o),
+                                          sigma.ctypes.data), 'bpe_sgmodel_ppmi_svd')
+        return sigma
+
+    def ppmi_svd_tensors(self, targets, contexts, counts, shift=1.0, cds=1.0, gamma=0.5, oversample=16, power_iters=4,
+                         seed=0, omega=None):
+        """Device form (bpe_sgmodel_ppmi_svd_device): planes, and `omega` if given, as torch tensors on the model's
+        device -> sigma, numpy float64 [embed]."""
+        import torch
+        if omega is not None:
+            if omega.dtype != torch.float32 or not omega.is_cuda or omega.device.index != self.device or not omega.is_contiguous():
+                raise BpeError('ppmi_svd_tensors takes omega as a contiguous float32 tensor on the model\'s device', ERR_ARG)
+            self._svd_omega_shape(omega.shape, oversample)
+        args = self._planes_tensors('ppmi_svd_tensors', targets, contexts, counts)
+        o = self._svd_opts(shift, cds, gamma, oversample, power_iters, seed, None if omega is None else omega.data_ptr())
+        sigma = np.zeros(self.width, np.float64)
+        _check(lib().bpe_sgmodel_ppmi_svd_device(self._m, *args, ctypes.byref(o), sigma.ctypes.data),
+               'bpe_sgmodel_ppmi_svd_device')
+        return sigma
+
+    def svd_stats(self):
+        s = SkipgramSvdStats()
+        _check(lib().bpe_sgmodel_get_svd_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_svd_stats')
+        return s.as_dict()
+
+    def reset_svd_stats(self):
+        _check(lib().bpe_sgmodel_reset_svd_stats(self._m), 'bpe_sgmodel_reset_svd_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

@@ -42,6 +42,7 @@
 // parameters trained with negative sampling instead of the full softmax in bpe_sgns.hip.h, both included below.
 // bpe_sgdense.hip.h, included with them, is the second form of both training steps: the counts as a dense
 // V x V tile source instead of CSR entries, chosen per model by bpe_sgmodel_set_counts_form.
+// bpe_glove.hip.h (GloVe) and bpe_svd.hip.h (PPMI and a truncated SVD of it, the closed form) come at the end.
 // No floating-point atomics; every reduction has a fixed order, so results are the same bytes on
 // every run and route.
 #include <hip/hip_runtime.h>
@@ -52,6 +53,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "bpe.h"
 #include "bpe_multi.h"   // bpe_fail
@@ -564,6 +566,12 @@ struct bpe_sgmodel {
     void *d_gs = nullptr;
     int64_t gs_cap = 0;
     bpe_sgmodel_glove_stats gstats = {};
+    // PPMI and SVD (bpe_svd.hip.h): the call's scratch, grow-only, and the events between its phases
+    void *d_ss = nullptr;
+    int64_t ss_cap = 0;
+    bool svd_attrs = false;
+    std::vector<hipEvent_t> sev;
+    bpe_sgmodel_svd_stats sstats = {};
 };
 
 namespace {
@@ -866,12 +874,13 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
                     M->d_io, M->d_qs, M->d_ns, (void *)M->d_W, M->d_ds, (void *)M->d_bt, (void *)M->d_gbt,
-                    (void *)M->d_mbt, (void *)M->d_vbt, M->d_gs})
+                    (void *)M->d_mbt, (void *)M->d_vbt, M->d_gs, M->d_ss})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
     for (hipEvent_t e : M->nev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : M->sev) (void)hipEventDestroy(e);
     if (M->stream) (void)hipStreamDestroy(M->stream);
     delete M;
     return BPE_OK;
@@ -986,3 +995,4 @@ int bpe_sgmodel_reset_stats(bpe_sgmodel *M) {
 }  // extern "C"
 
 #include "bpe_glove.hip.h"
+#include "bpe_svd.hip.h"

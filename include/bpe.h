@@ -1475,6 +1475,82 @@ int bpe_sgmodel_get_target_bias_device(bpe_sgmodel *m, float *d_bt, int64_t dim)
 int bpe_sgmodel_get_glove_stats(bpe_sgmodel *m, bpe_sgmodel_glove_stats *out);
 int bpe_sgmodel_reset_glove_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model, PPMI and SVD --------------------------------------------------------------------
+ * The closed-form consumer of the count planes (Levy & Goldberg 2014): the positive pointwise mutual
+ * information of the cells and a truncated SVD of it, written into the same parameters, so that embed and
+ * the queries answer at once and the Adam-trained rules may start from it (csrc/bpe_svd.hip.h).  No
+ * learning rate, no step count.  Planes, checks and messages as above; elements with C == 0 are not cells
+ * and change no byte of any result.  bpe_sgmodel_set_counts_form does not apply.
+ *
+ * PPMI: r_t = sum_c C[t,c] and k_c = sum_t C[t,c] in int64, Z = sum_c k_c^cds in double over ascending c
+ * with k_c > 0 (cds: context-distribution smoothing; Z = sum C at cds = 1; the sum is taken in 1024 slices of
+ * ceil(dim / 1024) consecutive c, each in ascending c, and the slices are added in order: one fixed order,
+ * the plain ascending sum for dim <= 1024), and in double from the int64
+ * count, rounded once,
+ *   m(t,c) = fl32(max(0, log C - log r_t - cds log k_c + log Z - log shift)).
+ * bpe_sgmodel_ppmi writes m of every element of the planes into out[U] (0 for an element with C == 0) and
+ * changes nothing in the model.
+ *
+ * bpe_sgmodel_ppmi_svd takes the SVD of the V x V matrix M of those values by randomized subspace
+ * iteration (Halko, Martinsson & Tropp 2011) with L = embed + oversample columns, rounded up to a multiple
+ * of 16:  Q = orth(M Omega);  power_iters times W = orth(M^T Q), Q = orth(M W);  B = M^T Q;
+ * B^T B = W^ Lambda W^^T (eigenvalues descending, ties to the lower index), sigma_i = sqrt(max(lambda_i, 0)),
+ * U = Q W^, Vm = B W^ Sigma^-1 with a column whose sigma_i <= 1e-7 sigma_1 zero.  orth(Y) is Y R^-1 for the
+ * Cholesky factor Y^T Y = R^T R, taken in double without pivoting; a pivot <= 1e-12 max_k (Y^T Y)_kk
+ * drops its column (zero in the result, counted), so a matrix of rank below L is served and its trailing
+ * sigma are 0.  Omega is opts->omega (fp32 [dim][L] row-major; a host pointer in the host form, a device
+ * pointer in the device form) or, when that is NULL, standard normal values that are a function of (seed,
+ * row, column) alone.  The call writes
+ *   Ein = U[:, :embed] Sigma^gamma,  Eout = Vm[:, :embed] Sigma^(1 - gamma),  b1 = b2 = 0,
+ * each column of U given the sign that makes its entry of largest magnitude positive (the lowest row on
+ * a tie) and Vm following, so Ein Eout^T is the rank-embed approximation of M and the bytes are a function
+ * of the inputs alone.  The target bias is left alone; the Adam moments and the step counter are reset as
+ * by bpe_sgmodel_reset_optimizer.  sigma[embed] (doubles, on the host in both forms) may be NULL.  Planes
+ * without cells are no error: the parameters become zero and every sigma 0.  opts == NULL means the
+ * defaults {shift 1, cds 1, gamma 0.5, oversample 16, power_iters 4, seed 0, omega NULL}.
+ *
+ * Errors are BPE_ERR_ARG, nothing is computed and neither the parameters nor the optimizer change: the
+ * plane messages above, `skip-gram model shift S is not positive or not finite`, `skip-gram model cds C
+ * outside (0, 1]`, `skip-gram model gamma G outside [0, 1]`, `skip-gram model oversample|power_iters N is
+ * negative`, and `skip-gram model svd width L (embed E + oversample O, in sixteens) above the limit 128`
+ * or `... above dim V`: L is never shrunk silently. */
+#define BPE_SVD_MAX_L 128
+typedef struct {
+    double shift;          /* > 0 */
+    double cds;            /* in (0, 1] */
+    double gamma;          /* in [0, 1] */
+    int32_t oversample;    /* >= 0 */
+    int32_t power_iters;   /* >= 0 */
+    uint64_t seed;         /* of Omega when omega == NULL */
+    const float *omega;    /* [dim][L], or NULL */
+} bpe_sgmodel_svd_opts;
+typedef struct {
+    int64_t calls;            /* ppmi and ppmi_svd calls (failed ones too) */
+    int64_t cells;            /* N of the calls that passed their checks */
+    int64_t positive_cells;   /* ... their cells with m > 0 */
+    int64_t L;                /* the width of the last ppmi_svd that passed its checks */
+    int64_t dropped_columns;  /* columns dropped by the orthonormalisations */
+    int64_t sweeps;           /* Jacobi sweeps of the eigenproblems */
+    double prep_ms;           /* HIP-event time of: the cells, the transposed planes, the tables, Omega (ppmi: all of it) */
+    double spmm_ms;           /* ... the sparse products */
+    double gram_ms;           /* ... the Grams Y^T Y and B^T B with the sums of their partials */
+    double chol_ms;           /* ... the Cholesky factorisations with R^-1 */
+    double apply_ms;          /* ... Y R^-1, and U and Vm of the finish */
+    double eig_ms;            /* ... the eigenproblem */
+    double finish_ms;         /* ... the signs and the store, the optimizer's reset */
+    double kernel_ms;         /* ... all kernels, the plane checks included */
+} bpe_sgmodel_svd_stats;
+int bpe_sgmodel_ppmi(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts, int64_t U,
+                     double shift, double cds, float *out);
+int bpe_sgmodel_ppmi_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts, const int64_t *d_counts,
+                            int64_t U, double shift, double cds, float *d_out);
+int bpe_sgmodel_ppmi_svd(bpe_sgmodel *m, const int32_t *targets, const int32_t *contexts, const int64_t *counts,
+                         int64_t U, const bpe_sgmodel_svd_opts *opts, double *sigma);
+int bpe_sgmodel_ppmi_svd_device(bpe_sgmodel *m, const int32_t *d_targets, const int32_t *d_contexts,
+                                const int64_t *d_counts, int64_t U, const bpe_sgmodel_svd_opts *opts, double *sigma);
+int bpe_sgmodel_get_svd_stats(bpe_sgmodel *m, bpe_sgmodel_svd_stats *out);
+int bpe_sgmodel_reset_svd_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
