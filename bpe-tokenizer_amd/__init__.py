@@ -89,6 +89,8 @@ C_API = [
     'bpe_sgmodel_reset_glove_stats',
     'bpe_sgmodel_ppmi', 'bpe_sgmodel_ppmi_device', 'bpe_sgmodel_ppmi_svd', 'bpe_sgmodel_ppmi_svd_device',
     'bpe_sgmodel_get_svd_stats', 'bpe_sgmodel_reset_svd_stats',
+    'bpe_sgmodel_embed_texts', 'bpe_sgmodel_embed_texts_device', 'bpe_sgmodel_score_texts',
+    'bpe_sgmodel_score_texts_device', 'bpe_sgmodel_get_text_stats', 'bpe_sgmodel_reset_text_stats',
     'bpe_encode_dropout_batch', 'bpe_encode_dropout_text_batch', 'bpe_encode_dropout_text_batch_device',
     'bpe_encoder_get_dropout_stats', 'bpe_encoder_reset_dropout_stats',
 ]
@@ -165,6 +167,10 @@ SGM_MAX_SPLITS = 256             # BPE_SGM_MAX_SPLITS: the most splits of the de
 SGM_DENSE_THETA = 1 / 64         # BPE_SGM_DENSE_THETA: 'auto' runs the dense form from this density U / dim^2 on
 GLOVE_RUN = 64                   # BPE_GLOVE_RUN: cells of a run, the unit of work of the GloVe kernels
 SVD_MAX_L = 128                  # BPE_SVD_MAX_L: the widest subspace of ppmi_svd (embed + oversample, in sixteens)
+SGM_POOL_SUM, SGM_POOL_MEAN, SGM_POOL_UNIT = 0, 1, 2   # BPE_SGM_POOL_*: how embed_texts scales a text's sum
+SGM_TEXT_CHUNK = 256             # BPE_SGM_TEXT_CHUNK: values of a text one lane group of the text kernels walks
+SGM_TEXT_FOLD = 64               # BPE_SGM_TEXT_FOLD: a text of more chunks has its chunks added in two levels
+_SGM_POOLS = {'sum': SGM_POOL_SUM, 'mean': SGM_POOL_MEAN, 'unit': SGM_POOL_UNIT}
 _SGM_METRICS = {'dot': SGM_DOT, 'cosine': SGM_COSINE}
 _SGM_FORMS = {'csr': SGM_FORM_CSR, 'dense': SGM_FORM_DENSE, 'auto': SGM_FORM_AUTO}
 _LINES_MODES = {'trim': LINES_TRIM, 'keep': LINES_KEEP, 'file': LINES_FILE,
@@ -387,6 +393,15 @@ class SkipgramSvdStats(ctypes.Structure):
                 ('prep_ms', ctypes.c_double), ('spmm_ms', ctypes.c_double), ('gram_ms', ctypes.c_double),
                 ('chol_ms', ctypes.c_double), ('apply_ms', ctypes.c_double), ('eig_ms', ctypes.c_double),
                 ('finish_ms', ctypes.c_double), ('kernel_ms', ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SkipgramTextStats(ctypes.Structure):
+    """bpe_sgmodel_text_stats (include/bpe.h)."""
+    _fields_ = [('calls', ctypes.c_int64), ('texts', ctypes.c_int64), ('values', ctypes.c_int64),
+                ('items', ctypes.c_int64), ('pairs', ctypes.c_int64), ('kernel_ms', ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -699,6 +714,12 @@ def lib():
                                         ctypes.c_int),
         'bpe_sgmodel_get_svd_stats': ([vp, ctypes.POINTER(SkipgramSvdStats)], ctypes.c_int),
         'bpe_sgmodel_reset_svd_stats': ([vp], ctypes.c_int),
+        'bpe_sgmodel_embed_texts': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int, vp], ctypes.c_int),
+        'bpe_sgmodel_embed_texts_device': ([vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int, vp], ctypes.c_int),
+        'bpe_sgmodel_score_texts': ([vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_score_texts_device': ([vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp], ctypes.c_int),
+        'bpe_sgmodel_get_text_stats': ([vp, ctypes.POINTER(SkipgramTextStats)], ctypes.c_int),
+        'bpe_sgmodel_reset_text_stats': ([vp], ctypes.c_int),
         'bpe_digest': ([i32p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int),
         'bpe_synth_zipf': ([ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint64,
                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64], ctypes.c_int),
@@ -3146,6 +3167,100 @@ class SkipgramModel:
 
     def reset_svd_stats(self):
         _check(lib().bpe_sgmodel_reset_svd_stats(self._m), 'bpe_sgmodel_reset_svd_stats')
+
+    # ---- texts (include/bpe.h, "skip-gram model over texts"; csrc/bpe_sgtext.hip.h) ----
+    @staticmethod
+    def _pool(pool):
+        """'sum' / 'mean' / 'unit' or the library's number; the library refuses anything else (an unknown name goes as -1)."""
+        return _SGM_POOLS.get(pool, -1) if isinstance(pool, str) else int(pool)
+
+    @staticmethod
+    def _texts(texts_or_vals, off):
+        """(vals int32, off int64) of a list of int sequences (flattened as Encoder.skipgram does) or of a flat pair."""
+        if off is None:
+            parts = [_i32(t).ravel() for t in texts_or_vals]
+            off = np.zeros(len(parts) + 1, dtype=np.int64)
+            np.cumsum([len(x) for x in parts], out=off[1:])
+            vals = np.concatenate(parts) if parts and off[-1] else np.zeros(0, np.int32)
+            return vals, off
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        if off.size < 1:
+            raise BpeError('text offsets need at least one entry', ERR_ARG)
+        return _i32(texts_or_vals).ravel(), off
+
+    def _texts_tensors(self, what, vals, off, weights=None):
+        import torch
+        for x, dt in ((vals, torch.int32), (off, torch.int64), (weights, torch.float32)):
+            if x is not None and (x.dtype != dt or not x.is_cuda or x.device.index != self.device
+                                  or not x.is_contiguous() or x.dim() != 1):
+                raise BpeError('%s takes contiguous (int32 values, int64 offsets, float32 weights) vectors on the '
+                               'model\'s device' % what, ERR_ARG)
+        if off.numel() < 1 or (weights is not None and weights.numel() != self.dim):
+            raise BpeError('%s takes n_texts + 1 offsets and dim weights' % what, ERR_ARG)
+        torch.cuda.synchronize(off.device)   # (the model runs on a stream of its own)
+        return vals.data_ptr() if vals.numel() else None, off.data_ptr(), off.numel() - 1
+
+    def embed_texts(self, texts_or_vals, off=None, weights=None, pool='mean'):
+        """-> float32 [n_texts][embed]: one pooled vector per text, s_k * sum_i w[v_i] (Ein[v_i] + b1), with
+        pool 'sum' (s = 1), 'mean' (s = 1 / sum of the weights) or 'unit' (s = 1 / the sum's norm).  texts: a
+        list of int sequences, or flat values with `off`; weights: dim token weights or None for ones
+        (bpe_sgmodel_embed_texts)."""
+        vals, off = self._texts(texts_or_vals, off)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            if w.size != self.dim:
+                raise BpeError('embed_texts takes dim weights', ERR_ARG)
+        out = np.empty((off.size - 1, self.width), np.float32)
+        _check(lib().bpe_sgmodel_embed_texts(self._m, vals.ctypes.data if vals.size else None, off.ctypes.data, off.size - 1,
+                                             None if w is None else w.ctypes.data, self._pool(pool), out.ctypes.data),
+               'bpe_sgmodel_embed_texts')
+        return out
+
+    def embed_texts_tensors(self, vals, off, weights=None, pool='mean', out=None):
+        """Device form (bpe_sgmodel_embed_texts_device): what Encoder.encode_text_tensors / encode_utf8_tensors
+        return (int32 values, int64 offsets), and the weights, as torch tensors on the model's device -> a
+        float32 [n_texts][embed] tensor there (`out`, if given, is filled and returned)."""
+        import torch
+        vp, op, n = self._texts_tensors('embed_texts_tensors', vals, off, weights)
+        if out is None:
+            out = torch.empty((n, self.width), dtype=torch.float32, device=off.device)
+        elif (out.dtype != torch.float32 or not out.is_cuda or out.device.index != self.device or not out.is_contiguous()
+              or tuple(out.shape) != (n, self.width)):
+            raise BpeError('embed_texts_tensors takes out as a contiguous float32 [n_texts][embed] tensor on the '
+                           'model\'s device', ERR_ARG)
+        _check(lib().bpe_sgmodel_embed_texts_device(self._m, vp, op, n, None if weights is None else weights.data_ptr(),
+                                                    self._pool(pool), out.data_ptr() if n else None),
+               'bpe_sgmodel_embed_texts_device')
+        return out
+
+    def score_texts(self, texts_or_vals, off=None, window=2):
+        """-> (sum_logp float64 [n_texts], pairs int64 [n_texts]): the log-likelihood of every text's skip-gram
+        pairs over `window` values on each side under the model's softmax, and their number; the mean per pair
+        is sum_logp / pairs and the perplexity exp of its negative (bpe_sgmodel_score_texts)."""
+        vals, off = self._texts(texts_or_vals, off)
+        s, p = np.empty(off.size - 1, np.float64), np.empty(off.size - 1, np.int64)
+        _check(lib().bpe_sgmodel_score_texts(self._m, vals.ctypes.data if vals.size else None, off.ctypes.data, off.size - 1,
+                                             int(window), s.ctypes.data, p.ctypes.data), 'bpe_sgmodel_score_texts')
+        return s, p
+
+    def score_texts_tensors(self, vals, off, window=2):
+        """Device form (bpe_sgmodel_score_texts_device) -> (float64, int64) tensors on the model's device."""
+        import torch
+        vp, op, n = self._texts_tensors('score_texts_tensors', vals, off)
+        s = torch.empty(n, dtype=torch.float64, device=off.device)
+        p = torch.empty(n, dtype=torch.int64, device=off.device)
+        _check(lib().bpe_sgmodel_score_texts_device(self._m, vp, op, n, int(window), s.data_ptr() if n else None,
+                                                    p.data_ptr() if n else None), 'bpe_sgmodel_score_texts_device')
+        return s, p
+
+    def text_stats(self):
+        s = SkipgramTextStats()
+        _check(lib().bpe_sgmodel_get_text_stats(self._m, ctypes.byref(s)), 'bpe_sgmodel_get_text_stats')
+        return s.as_dict()
+
+    def reset_text_stats(self):
+        _check(lib().bpe_sgmodel_reset_text_stats(self._m), 'bpe_sgmodel_reset_text_stats')
 
 
 def encode_samples(samples, merges, len16=None, device=0):

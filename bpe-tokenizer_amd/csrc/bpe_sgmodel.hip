@@ -42,7 +42,8 @@
 // parameters trained with negative sampling instead of the full softmax in bpe_sgns.hip.h, both included below.
 // bpe_sgdense.hip.h, included with them, is the second form of both training steps: the counts as a dense
 // V x V tile source instead of CSR entries, chosen per model by bpe_sgmodel_set_counts_form.
-// bpe_glove.hip.h (GloVe) and bpe_svd.hip.h (PPMI and a truncated SVD of it, the closed form) come at the end.
+// bpe_glove.hip.h (GloVe) and bpe_svd.hip.h (PPMI and a truncated SVD of it, the closed form) come at the end,
+// and behind them bpe_sgtext.hip.h: what a trained model says about texts (pooled embeddings, log-likelihood).
 // No floating-point atomics; every reduction has a fixed order, so results are the same bytes on
 // every run and route.
 #include <hip/hip_runtime.h>
@@ -572,6 +573,10 @@ struct bpe_sgmodel {
     bool svd_attrs = false;
     std::vector<hipEvent_t> sev;
     bpe_sgmodel_svd_stats sstats = {};
+    // texts (bpe_sgtext.hip.h): the scanned item counts and the partials of the long texts, grow-only
+    void *d_ts = nullptr, *d_tp = nullptr;
+    int64_t ts_cap = 0, tp_cap = 0;
+    bpe_sgmodel_text_stats tstats = {};
 };
 
 namespace {
@@ -874,7 +879,7 @@ int bpe_sgmodel_destroy(bpe_sgmodel *M) {
     for (void *p : {(void *)M->d_p, (void *)M->d_g, (void *)M->d_m, (void *)M->d_v, (void *)M->d_rowptr, (void *)M->d_nt,
                     (void *)M->d_lse, (void *)M->d_db1_part, (void *)M->d_loss_part, (void *)M->d_hdr, M->d_planes,
                     M->d_io, M->d_qs, M->d_ns, (void *)M->d_W, M->d_ds, (void *)M->d_bt, (void *)M->d_gbt,
-                    (void *)M->d_mbt, (void *)M->d_vbt, M->d_gs, M->d_ss})
+                    (void *)M->d_mbt, (void *)M->d_vbt, M->d_gs, M->d_ss, M->d_ts, M->d_tp})
         if (p) (void)hipFree(p);
     if (M->ev0) (void)hipEventDestroy(M->ev0);
     if (M->ev1) (void)hipEventDestroy(M->ev1);
@@ -996,3 +1001,4 @@ int bpe_sgmodel_reset_stats(bpe_sgmodel *M) {
 
 #include "bpe_glove.hip.h"
 #include "bpe_svd.hip.h"
+#include "bpe_sgtext.hip.h"

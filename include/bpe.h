@@ -1551,6 +1551,66 @@ int bpe_sgmodel_ppmi_svd_device(bpe_sgmodel *m, const int32_t *d_targets, const 
 int bpe_sgmodel_get_svd_stats(bpe_sgmodel *m, bpe_sgmodel_svd_stats *out);
 int bpe_sgmodel_reset_svd_stats(bpe_sgmodel *m);
 
+/* ---- skip-gram model over texts: pooled embeddings and log-likelihood -----------------------------------
+ * What the embeddings are trained for (the reference's example/skip-gram-test.ts encodes a text and looks
+ * its tokens up in the net): one vector per text, and how well the model explains a text, as ragged
+ * reductions over the encoder's (vals, off) output on the device (csrc/bpe_sgtext.hip.h).  Inputs are as
+ * bpe_encoder_skipgram takes them: text k is vals[off[k] .. off[k+1]), off[0] need not be 0 and values
+ * before it are never read; values lie in [0, V).  With X_v = fl32(Ein[v] + b1), the row bpe_sgmodel_embed
+ * returns:
+ *
+ * bpe_sgmodel_embed_texts: out[k][0..E) = s_k * sum_i w[v_i] X_{v_i} over the text's values in order.
+ * `weights` is V fp32 token weights (a / (a + p(v)) for SIF pooling, 0 to drop a token), NULL for all ones.
+ *   BPE_SGM_POOL_SUM   s_k = 1
+ *   BPE_SGM_POOL_MEAN  s_k = 1 / sum_i w[v_i], the sum taken in fp32 in the same order, and 0 when it is 0
+ *   BPE_SGM_POOL_UNIT  s_k = 1 / |sum|_2, and 0 for a zero sum: rows for neighbors_vectors with BPE_SGM_DOT
+ * An empty text gives a zero row.
+ *
+ * bpe_sgmodel_score_texts: over the pairs of the "skip-gram pairs" section above (target v_i, context v_j,
+ * 0 < |i - j| <= window, inside the text; window in [1, BPE_SKIPGRAM_MAX_WINDOW]),
+ *   sum_logp[k] = sum_pairs fl32(fl32(X_t . Eout[c] + b2[c]) - lse_t),  pairs[k] = that section's closed form,
+ * each term fp32 with the dot in one fixed order over e, the terms added in double in (target, context)
+ * order.  lse_t is what bpe_sgmodel_predict writes as out_lse for the ids 0 .. V - 1 in one call: the call
+ * runs that forward once.  Texts of 0 or 1 values give 0 and 0.  The mean per pair and the perplexity are
+ * the caller's division.
+ *
+ * A text is cut into chunks of BPE_SGM_TEXT_CHUNK of its own values counted from its start; the sums of a
+ * chunk run in value order and a text's chunks are added in an order fixed by their number.  So a text's
+ * row and sum_logp are the same bytes whatever else is in the batch, whatever off[0] is, in both forms and
+ * on every run.  No floating-point atomics.
+ *
+ * Errors are BPE_ERR_ARG with nothing written to the caller: decreasing or negative offsets (`text offsets
+ * must not decrease or be negative`), a value outside the table (`skip-gram model value D outside [0, V)
+ * (text K, value I)`, the one at the smallest flat position), an unknown pool (`skip-gram model pool N is
+ * none of ...`), a window outside its range (`skip-gram model window W outside [1, 64]`).  n_texts == 0 is
+ * BPE_OK and writes nothing.  Neither call changes the parameters, the optimizer or the query statistics.
+ * The `_device` forms take device pointers (out 16-byte aligned for the widest stores; any 4-byte alignment
+ * is served), run on the model's stream and synchronise before returning; the host forms are the device
+ * forms plus the copies. */
+#define BPE_SGM_POOL_SUM 0
+#define BPE_SGM_POOL_MEAN 1
+#define BPE_SGM_POOL_UNIT 2
+#define BPE_SGM_TEXT_CHUNK 256
+#define BPE_SGM_TEXT_FOLD 64   /* a text of more chunks has them added in two levels (exported for the tests) */
+typedef struct {
+    int64_t calls;      /* embed_texts and score_texts calls (failed ones too) */
+    int64_t texts;      /* texts of the calls that wrote their results */
+    int64_t values;     /* ... their values */
+    int64_t items;      /* ... the (text, chunk) items they were cut into */
+    int64_t pairs;      /* ... the pairs of the score_texts calls among them */
+    double kernel_ms;   /* HIP-event time of all kernels, the checks and the lse forward included */
+} bpe_sgmodel_text_stats;
+int bpe_sgmodel_embed_texts(bpe_sgmodel *m, const int32_t *vals, const int64_t *off, int64_t n_texts,
+                            const float *weights, int pool, float *out);
+int bpe_sgmodel_embed_texts_device(bpe_sgmodel *m, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                   const float *d_weights, int pool, float *d_out);
+int bpe_sgmodel_score_texts(bpe_sgmodel *m, const int32_t *vals, const int64_t *off, int64_t n_texts, int window,
+                            double *sum_logp, int64_t *pairs);
+int bpe_sgmodel_score_texts_device(bpe_sgmodel *m, const int32_t *d_vals, const int64_t *d_off, int64_t n_texts,
+                                   int window, double *d_sum_logp, int64_t *d_pairs);
+int bpe_sgmodel_get_text_stats(bpe_sgmodel *m, bpe_sgmodel_text_stats *out);
+int bpe_sgmodel_reset_text_stats(bpe_sgmodel *m);
+
 #ifdef __cplusplus
 }
 #endif
